@@ -13,7 +13,12 @@ the ranks (strong scaling) with RCCL halo exchange.  Rank 0 prints one JSON line
 `roofline`: the dominant kernel (k_spmm_rows, the sum-aggregation) timed live with HIP events on its
 launch stream inside the timed steps; achieved = algorithmic bytes (SURVEY.md §8d:
 E*(d*4+4) + N*(d*4+4) [+4N row scale] [+d*4 bias]) / average launch duration.
-`cpu_baseline`: the oracle (CPU restatement, kind "port") timed on the host cores on a bounded sample.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own:
+`dense_backward` / `all_rows_forward` (the same trainer restarted under other switches), the reference epoch rate,
+`cpu_baseline` (the oracle, CPU restatement, kind "port", timed on the host cores), `roofline.traffic` (rocprofv3 PMC
+passes), the eager profiled pass before a hipGraph capture and, with N > 1, `sharding.loss_matches_n1`.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (step_outputs).
 """
 import argparse
 import contextlib
@@ -53,7 +58,15 @@ def parse():
     ap.add_argument('--dense-backward', type=int, default=1, help='also time K steps with the dense backward (CB_LOSS_ROWS=0) after the timed region (N=1, eager)')
     ap.add_argument('--check-n1', type=int, default=1, help='N > 1: rank 0 first computes the single-GPU training loss of the same model / seeds; '
                                                              'the sharded forward must reproduce it (sharding.loss_matches_n1)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline figure (--dense-backward, --ref-epochs, --cpu-baseline, --pmc-traffic, --check-n1 and '
+                         'the eager profiled pass of --hip-graph 1); without it those switches do nothing')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one handed its caller (loss, updated parameters, their gradients) as DIR/<name>.npy')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def make_args(dataset, extra=(), se='000', layers=3):
@@ -87,8 +100,16 @@ def _oracle_modules():
 
 
 def _cpu_threads():
-    n = os.cpu_count() or 1
-    return max(1, min(n // 2 if n >= 16 else n, 128))      # one thread per physical core (SMT siblings only add contention)
+    # the CPUs this process may run on (not the whole host's count), and no more than OMP_NUM_THREADS where the host sets it
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    n = max(1, min(n // 2 if n >= 16 else n, 128))      # one thread per physical core (SMT siblings only add contention)
+    cap = os.environ.get('OMP_NUM_THREADS', '')
+    return min(n, int(cap)) if cap.isdigit() and int(cap) > 0 else n
+
+
+# one full-size S-pl10M oracle step took 192 - 216 s on 128 threads: ~2.6e4 thread-seconds per 10^7 nodes
+CPU_FULL_THREAD_S_PER_NODE = 200.0 * 128 / 1e7
+CPU_FULL_MAX_S = 300.0          # auto mode measures at full size only when one step is predicted to take at most this long
 
 
 def cpu_baseline_sample(a, args, full_nodes):
@@ -188,7 +209,9 @@ def cpu_baseline(a, args, trainer, sd0, graph_obj, full_nodes):
     if mode == 'auto':
         _, avail = _host_info()
         need = 45 * full_nodes * max(args.dim_hidden, args.num_feats) * 4 * 1.5
-        mode = 'full' if (avail >= need and (os.cpu_count() or 1) >= 32) else 'sample'
+        threads = _cpu_threads()
+        fast_enough = CPU_FULL_THREAD_S_PER_NODE * full_nodes / threads <= CPU_FULL_MAX_S
+        mode = 'full' if (avail >= need and threads >= 16 and fast_enough) else 'sample'
     if mode == 'full':
         return cpu_baseline_full(a, args, trainer, sd0, graph_obj, a.cpu_budget_s)
     return cpu_baseline_sample(a, args, full_nodes)
@@ -407,6 +430,43 @@ def roofline_families(recs, steps):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 20          # per array (4 MB): larger ones (the [N, H] tables of --se 111) are written as a fixed sample of their rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(loss, model):
+    """What the timed step hands its caller, copied to the host right after the timed region: the loss of the last step (float32 [1]),
+    and every parameter after its Adam update ('param.<name>') with the gradient its backward left on it ('grad.<name>').  An array of
+    more than DUMP_MAX_ELEMS elements keeps DUMP_MAX_ELEMS // row-size rows drawn by numpy's default_rng(0) in ascending order (the same rows
+    for a parameter and its gradient; the ids are stored as '<name>.rows', float64).  Returns {name: float32 / float64 ndarray}."""
+    import numpy as np
+    out = {'loss': loss.detach().float().reshape(1).cpu().numpy()}
+
+    def put(name, t):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS and t.dim() >= 1:
+            k = max(1, DUMP_MAX_ELEMS // max(1, t[0].numel()))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=min(k, t.shape[0]), replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+            out[name + '.rows'] = rows.astype(np.float64)
+        out[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    for name, p in model.named_parameters():
+        put('param.' + name, p)
+        if p.grad is not None:
+            put('grad.' + name, p.grad)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit')
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 KERNEL_OF = {'plain': 'k_spmm_rows (+hub kernels)', 'colscale': 'k_spmm_rows<colscale> (+hub kernels)', 'fused_store': 'k_spmm_rows<fused store> (+hub kernels)',
              'agg_gemm': 'k_agg_gemm2<false> (+hub kernels): aggregation + the dX 256x256 contraction on the matrix cores in one kernel',
              'agg_gemm_fused': 'k_agg_gemm2<true> (+hub kernels): aggregation with the trunk store + the next 256x256 dense transform on the matrix cores in one kernel',
@@ -421,8 +481,22 @@ def main():
     a = parse()
     relaunch = self_launch_argv(a, sys.argv[1:], os.environ, torch.cuda.device_count() if torch.cuda.is_available() else 0)
     if relaunch is not None:
+        # the ranks run as a child process (this one has already opened the GPU to count the devices: it must not exec another program)
+        import subprocess
         sys.stdout.flush()
-        os.execv(relaunch[0], relaunch)
+        raise SystemExit(subprocess.run(relaunch).returncode)
+    # the trainer creates its model directory (saved_models/<task>/<dataset>) under the working directory, which may be read-only (a
+    # checkout run by another user): run in a scratch directory of this process, removed at exit
+    import atexit
+    import shutil
+    import tempfile
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
+    work = tempfile.mkdtemp(prefix='cb_bench_')
+    atexit.register(shutil.rmtree, work, True)
+    if os.path.isdir('data'):                # data.load_data reads data/<dataset>.pt relative to the working directory when it is there
+        os.symlink(os.path.abspath('data'), os.path.join(work, 'data'))
+    os.chdir(work)
     # Libraries (RCCL banner, rocm notices) write to the C stdout and flush it at exit, i.e. AFTER Python's
     # prints; keep a private copy of fd 1 for the JSON line and route everything else to stderr.
     sys.stdout.flush()
@@ -458,7 +532,7 @@ def main():
         if sharded:
             from gnn_tail_generalization_amd import dist as cbdist
             data0 = None
-            if a.check_n1 and a.se == '000':
+            if a.full and a.check_n1 and a.se == '000':
                 n1, data0 = n1_reference(a, local_rank, rank)          # rank 0: single-GPU loss on the whole graph; its data is reused below
             t = cbdist.ShardedTrainer(args, 0, data=data0)
             del data0
@@ -469,7 +543,7 @@ def main():
     graph_obj = t.graph()
     n_nodes, n_edges = t.global_nodes(), t.global_edges()
     L = args.num_layers
-    sd0 = {k: v.detach().cpu().clone() for k, v in t.teacherGNN.state_dict().items()} if not sharded else None
+    sd0 = {k: v.detach().cpu().clone() for k, v in t.teacherGNN.state_dict().items()} if a.full and not sharded else None
     torch.cuda.reset_peak_memory_stats(dev)
 
     def sync():
@@ -484,13 +558,15 @@ def main():
     sync()
     use_graph = bool(a.hip_graph) and not sharded
     if use_graph:
-        # kernel events cannot be recorded inside a captured graph: time the aggregation in an eager pass of the
-        # same K steps first, then capture and time the replays
-        graph_obj.profile = []
-        for _ in range(a.steps):
-            t.train_step()
-        sync()
-        prof, graph_obj.profile = graph_obj.profile, None
+        # kernel events cannot be recorded inside a captured graph: with --full, time the aggregation in an eager pass of the
+        # same K steps first; then capture and time the replays
+        prof = []
+        if a.full:
+            graph_obj.profile = []
+            for _ in range(a.steps):
+                t.train_step()
+            sync()
+            prof, graph_obj.profile = graph_obj.profile, None
         t.enable_hip_graph(warmup=1)
         t.train_step()
         sync()
@@ -505,6 +581,8 @@ def main():
     dt = time.perf_counter() - t0
     if not use_graph:
         prof, graph_obj.profile = graph_obj.profile, None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs(loss, t.teacherGNN))      # (before any --full leg moves the weights)
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         cbdist._all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -565,7 +643,7 @@ def main():
     dense_bwd = all_rows_fwd = None
     # (the graph counts the training forwards that evaluated their last layer on the loss rows: trunk._last_layer_on_loss_rows, stack.py)
     rows_only_fwd = bool(row_sparse and getattr(graph_obj, 'rows_only_forwards', 0) > 0)
-    if a.dense_backward and row_sparse and not use_graph and os.environ.get('CB_LOSS_ROWS', '1') != '0':
+    if a.full and a.dense_backward and row_sparse and not use_graph and os.environ.get('CB_LOSS_ROWS', '1') != '0':
         if rows_only_fwd and os.environ.get('CB_ROWS_ONLY_FWD', '1') != '0':
             all_rows_fwd = restarted_leg({'CB_ROWS_ONLY_FWD': '0'},
                                          'the same trainer restarted from the initial weights / moments / RNG state with CB_ROWS_ONLY_FWD=0: every row of every '
@@ -576,7 +654,7 @@ def main():
                                   'forward, every backward aggregation over all rows: the reference\'s amount of work), warm-up + K steps, outside the timed '
                                   'region; final_loss is bit-comparable with the final_loss of rounds 2 - 4', n_edges * 2 * L)
     ref_epoch = None
-    if a.ref_epochs > 0 and not sharded and not use_graph:
+    if a.full and a.ref_epochs > 0 and not sharded and not use_graph:
         ref_epoch = reference_epoch_rate(t, args, a.ref_epochs, sync)
     if sharded:
         xlog, graph_obj.exchange_log = graph_obj.exchange_log, None
@@ -678,9 +756,9 @@ def main():
         out['sharding'] = sharding
     if ref_epoch is not None:
         out.update(ref_epoch)
-    if a.cpu_baseline and world == 1 and not sharded:
+    if a.full and a.cpu_baseline and world == 1 and not sharded:
         out['cpu_baseline'] = cpu_baseline(a, args, t, sd0, graph_obj, n_nodes)
-    if a.pmc_traffic and world == 1 and not sharded:
+    if a.full and a.pmc_traffic and world == 1 and not sharded:
         del t, graph_obj                     # the PMC passes build their own copy of the graph in a child process
         torch.cuda.empty_cache()
         traffic, note = pmc_traffic(a.dataset, fused=fam_main['kind'].startswith('agg_gemm'))

@@ -7,6 +7,8 @@ copied.  Each file: {'cfg': {...}, 'x', 'edge_index', 'y', 'train_mask', 'sd': s
 'eval_out', 'se_reg_all', 'les', 'train_loss', 'grads': {...}, 'bn_after': {...}}.
 """
 import argparse
+import contextlib
+import io
 import os
 import sys
 
@@ -445,6 +447,24 @@ def edge_weight_fixture(ns):
     return out
 
 
+INIT_SEED = 123
+INIT_CASES = ('nr_se111_L3', 'r_initialbn_se111_L2', 'r_dense_concat_L3', 'norm_groupnorm', 'r_jumping_attention_L2', 'teacher_learnable_input')
+
+
+def init_fixture(ns):
+    """The reference's freshly constructed TeacherGNN under torch.manual_seed(INIT_SEED) for a few trunk shapes: {case: {'cfg', 'sd'}}
+    (construction order and initialisers; tests/test_host_logic.py::test_same_seed_same_init_as_reference)."""
+    out = {'seed': INIT_SEED}
+    for c in CASES:
+        if c['name'] not in INIT_CASES:
+            continue
+        rargs, _, _, _, _, _ = build(ns, c)
+        torch.manual_seed(INIT_SEED)
+        ref_model = ns.GNN_normalizations.TeacherGNN(rargs)
+        out[c['name']] = dict(cfg=cfg_of(rargs, c), sd={k: v.detach().clone() for k, v in ref_model.state_dict().items()})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default='')
@@ -452,7 +472,7 @@ def main():
     ns = ref_import.load_reference()
     torch.set_num_threads(1)
     for c in CASES:
-        if a.only and (a.only in ('utils', 'options', 'trainer', 'lp', 'semlp', 'proj2class', 'edge_weight') or a.only not in c['name']):
+        if a.only and (a.only in ('utils', 'options', 'trainer', 'lp', 'semlp', 'proj2class', 'edge_weight', 'init') or a.only not in c['name']):
             continue
         out = run_case(ns, c)
         torch.save(out, os.path.join(HERE, f'case_{c["name"]}.pt'))
@@ -476,6 +496,11 @@ def main():
     if not a.only or 'proj2class' in a.only:
         torch.save(proj2class_fixture(ns), os.path.join(HERE, 'proj2class_fixture.pt'))
         print('wrote proj2class_fixture.pt')
+    if not a.only or a.only == 'init':
+        with contextlib.redirect_stdout(io.StringIO()):
+            fx = init_fixture(ns)
+        torch.save(fx, os.path.join(HERE, 'init_seed123_fixture.pt'))
+        print('wrote init_seed123_fixture.pt')
     if not a.only or a.only == 'lp':
         torch.save(lp_fixture(ns), os.path.join(HERE, 'lp_fixture.pt'))
         print('wrote lp_fixture.pt')

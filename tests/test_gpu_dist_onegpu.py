@@ -381,7 +381,7 @@ def test_bench_gpus_n_without_a_launcher_runs_n_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['COLDBREW_DIST_BACKEND'] = 'gloo'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dataset', 'S-arxiv', '--steps', '3', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dataset', 'S-arxiv', '--steps', '3', '--warmup', '1', '--full',
                         '--cpu-baseline', '0', '--pmc-traffic', '0', '--ref-epochs', '0'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -68,29 +68,20 @@ def test_state_dict_contract(name):
 
 def test_same_seed_same_init_as_reference():
     """Construction order / initialisers match: with the same torch seed the fresh parameters are
-    bit-identical to the reference's (needs /root/reference; skipped on the GPU box)."""
-    import ref_import
-    if not ref_import.reference_available():
-        pytest.skip('reference tree not present')
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
-    import make_golden
+    bit-identical to the reference's (tests/golden/init_seed123_fixture.pt: the reference's state_dicts, make_golden.init_fixture)."""
     from gnn_tail_generalization_amd.GNN_model import TeacherGNN
-    ns = ref_import.load_reference()
-    for c in make_golden.CASES:
-        if c['name'] not in ('nr_se111_L3', 'r_initialbn_se111_L2', 'r_dense_concat_L3', 'norm_groupnorm',
-                             'r_jumping_attention_L2', 'teacher_learnable_input'):
-            continue
+    fx = torch.load(os.path.join(GOLDEN, 'init_seed123_fixture.pt'), weights_only=False)
+    cases = [k for k in fx if k != 'seed']
+    assert len(cases) == 6, cases
+    for name in cases:
+        args = product_args(fx[name]['cfg'])
+        torch.manual_seed(fx['seed'])
         with contextlib.redirect_stdout(io.StringIO()):
-            rargs, _, _, _, _, _ = make_golden.build(ns, c)
-            torch.manual_seed(123)
-            ref_model = ns.GNN_normalizations.TeacherGNN(rargs)
-        args = product_args(make_golden.cfg_of(rargs, c))
-        torch.manual_seed(123)
-        mine = TeacherGNN(args)
-        ref_sd = ref_model.state_dict()
+            mine = TeacherGNN(args)
+        ref_sd = fx[name]['sd']
+        assert list(mine.state_dict()) == list(ref_sd), name
         for k, v in mine.state_dict().items():
-            assert torch.equal(v, ref_sd[k]), f'{c["name"]}: {k}'
+            assert torch.equal(v, ref_sd[k]), f'{name}: {k}'
 
 
 def test_utils_match_reference_fixture():

@@ -6,7 +6,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line_S-pl10M_default_full_run.json 2> $O/bench_default.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line_S-pl10M_default_full_run.json 2> $O/bench_default.err
 rm -rf /tmp/prof_$TAG
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o $TAG -- python $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --ref-epochs 0 --pmc-traffic 0 --dense-backward 0 > $R/$O/bench_line_under_rocprof.json 2>/dev/null )
 DB=$(find /tmp/prof_$TAG -name "*.db" | head -1)

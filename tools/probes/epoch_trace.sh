@@ -1,7 +1,7 @@
 # Kernels of the reference epoch (bench.py --ref-epochs): aggregated by name over the LAST epoch -> gpurun_out/epoch_trace.txt
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d /tmp/prof_ep -- python $R/bench.py --steps 2 --warmup 1 --ref-epochs 2 --cpu-baseline 0 --pmc-traffic 0 > /tmp/ep_line.json 2>/dev/null
+rocprofv3 --kernel-trace -d /tmp/prof_ep -- python $R/bench.py --steps 2 --warmup 1 --full --ref-epochs 2 --cpu-baseline 0 --pmc-traffic 0 --dense-backward 0 > /tmp/ep_line.json 2>/dev/null
 DB=$(ls -t $(find /tmp/prof_ep -name "*.db") | head -1)
 python - "$DB" > $R/gpurun_out/epoch_trace.txt <<'PY'
 import sqlite3, sys, re, collections

@@ -3,7 +3,7 @@
 TAG=${1:-r06s}
 O=gpurun_out/$TAG
 mkdir -p $O
-B="--cpu-baseline 0 --ref-epochs 0 --pmc-traffic 0"
+B="--full --cpu-baseline 0 --ref-epochs 0 --pmc-traffic 0"
 python bench.py --steps 6 --warmup 2 --se 111 $B > $O/bench_line_S-pl10M_se111.json 2>/dev/null
 python bench.py --steps 6 --warmup 2 --agg-dtype bf16 $B > $O/bench_line_S-pl10M_bf16agg.json 2>/dev/null
 python bench.py --steps 6 --warmup 2 --extra "--force_set_to_best_config=0 --type_trick=Residual" $B > $O/bench_line_S-pl10M_Residual.json 2>/dev/null
