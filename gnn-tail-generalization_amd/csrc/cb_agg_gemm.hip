@@ -56,8 +56,21 @@ struct GemmTail {
   float* colsum_partial;   // [gridDim.x][256] or null
   int* err;                // device-visible error word (cb_error.hip): a tile hand-over that timed out is recorded here, never silent
   // NARROW kernels only (the output Linear as the tail of the last layer's aggregation, GCN.py:133-138): out[m][n] = acc + bias[n], n < n_out <= 64
-  const float* bias;       // [n_out] or null
+  const float* bias;       // [n_out] or null (SR kernels: [256] or null)
   int n_out;
+  // SR kernels only (rows-only forward, trunk.py _layer_on_rows: the trunk's store on a SUBSET of the node rows as the tail — the expression of
+  // cb_gemm_nn_store_rows_f32, cb_gemm_core.h nn_epilogue EPI == 2): with gm = row_ids[m],
+  //   act = relu(rowscale[m] * acc + bias) (-> out_act);  out = dropout_{seed, row0 + gm}(c_act * act + c_mix * mix_src[mix_index[m] | gm])
+  //   mask words bits_out[gm][4] (bits_relu_only: act > 0 alone); thresh / keep_scale / seed / seed_dev / row0 / c_act above
+  const int64_t* row_ids;
+  const float* mix_src;     // or null
+  int64_t ld_mix;
+  const int64_t* mix_index; // or null
+  float c_mix;
+  unsigned long long* bits_out;   // [all node rows][4] or null
+  int bits_relu_only;
+  float* out_act;           // [rows, ld_act] or null
+  int64_t ld_act;
 };
 
 // (declared in cb_tile_gemm.h)
@@ -137,7 +150,7 @@ __device__ __forceinline__ void ag_signal(int* flag, int lane) {
 constexpr int kNG = 8;       // gathering wavefronts (3 wavefronts per SIMD at <= 168 registers; 12 gathers in flight each)
 constexpr int kU = 12;       // gathers in flight per gathering wavefront (16: spills; 8: slower — profiles/r03_fused_agg_gemm.md)
 
-template <bool FUSED, int GP, bool ACC>
+template <bool FUSED, int GP, bool ACC, bool CS = false>
 __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile, int w, int lane, const int* __restrict__ rowptr,
                                                 const int* __restrict__ col, const float* __restrict__ h, int64_t ld_h, float* __restrict__ out,
                                                 int64_t ld_out, int n_rows, const Epilogue& ep, int hub_T, const FusedEpi& fe) {
@@ -171,7 +184,7 @@ __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile,
     const unsigned long long m = (hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
     const int nh = m ? r + (__ffsll((long long)m) - 1) : rb;
     if (nh > r)
-      stream_rows<4, kU, true, FUSED, ACC, float, GP, kTLD, true>(r, nh, nrt, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, true,
+      stream_rows<4, kU, true, FUSED, ACC, float, GP, kTLD, true, CS>(r, nh, nrt, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, true,
                                                                          ep.relu, bvec, fe, c0, init_lane, ep.ld_init, ep, tile_lane, ptr_hi);
     if (nh < rb) {      // hub row nh: finished by the hub kernels, which ran before this launch
       const float* src = FUSED ? fe.out_next + (int64_t)(r0 + nh) * fe.ld_next + c0 : out + (int64_t)(r0 + nh) * ld_out + c0;
@@ -284,7 +297,105 @@ __device__ __forceinline__ void ag2_mfma_tile_head(int t, const float* __restric
   }
 }
 
-template <bool FUSED, int GP, bool ACC, bool TB, bool NARROW = false>
+// SR tail (the trunk's store on a subset of the node rows): multiplying wavefront w owns columns 64 w .. 64 w + 63 of each row, i.e. 16 bits of
+// each of the row's four mask words (word e, bit L <-> column 4 L + e).  Its pieces go to the tile's 2 KB of LDS words (ushort w of word e of
+// tile row mt); the LAST of the four wavefronts to finish the tile (LDS counter mw_cnt, no barrier) writes the assembled words, one 16-byte
+// vector store per two words, and releases the buffer (mw_done: the pieces of buffer b's next tile wait for it).
+__device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restrict__ tile, float* __restrict__ cs, int w, int lane, int n_rows,
+                                                   const GemmTail& gt, uint64_t seed_eff, int* freed, unsigned short* __restrict__ words,
+                                                   int* mw_cnt, int* mw_done, int use) {
+  const int l31 = lane & 31, lh = lane >> 5;
+  f32x16 acc[2][2];
+  tile_times_image<kNS, kTLD>(tile, gt.image, w, lane, acc);
+  ag_signal(freed, lane);      // the tile has been read for the last time
+  if (gt.bits_out && use > 0) ag_wait(mw_done, use, gt.err);      // the words of this buffer's previous tile have left
+  const int r0 = t * kTM;
+  const int n = 64 * w + (lane & 15) * 4;
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (gt.bias) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bv[e] = gt.bias[n + e];
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) cs[(r4 + 4 * lh) * kCLD + 32 * j + l31] = acc[i][j][4 * q + r4];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int idx = lane + 64 * half, row = idx >> 4, c4 = (idx & 15) * 4;
+        const int mt = 32 * i + 8 * q + row;
+        const int64_t m = r0 + mt;
+        const float4 v = *reinterpret_cast<const float4*>(cs + row * kCLD + c4);
+        const bool live = m < n_rows;
+        float o[4] = {v.x, v.y, v.z, v.w}, mk[4] = {1.f, 1.f, 1.f, 1.f};
+        int64_t gm = 0;
+        if (live) {      // the arithmetic of nn_epilogue's EPI == 2 branch (cb_gemm_core.h), term by term
+          gm = gt.row_ids[m];
+          const float rs = gt.rowscale ? gt.rowscale[m] : 1.f;
+          const float ad[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            o[e] = o[e] * rs + ad[e] + bv[e];
+            o[e] = fmaxf(o[e], 0.f);
+          }
+          if (gt.thresh) keep4(seed_eff, ((gt.row0 + gm) * kND + n) >> 2, gt.thresh, gt.keep_scale, mk);
+        }
+        if (gt.bits_out) {
+          // ballot e: bits 16 k .. 16 k + 15 = row (lane >> 4 == k) of this pass, columns 64 w .. 64 w + 63 -> bits 16 w .. of word e
+          unsigned long long bal[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bal[e] = __ballot(live && o[e] > 0.f && (gt.bits_relu_only || mk[e] != 0.f));
+          if (lane < 16) {
+            const int k = lane >> 2, e = lane & 3;
+            unsigned long long be = bal[0];
+#pragma unroll
+            for (int f = 1; f < 4; ++f) if (e == f) be = bal[f];
+            const int mtk = 32 * i + 8 * q + 4 * half + k;
+            words[(mtk * 4 + e) * 4 + w] = (unsigned short)(be >> (16 * k));
+          }
+        }
+        if (live) {
+          if (gt.out_act) store_stream<4>(gt.out_act + m * gt.ld_act + n, o);
+          float x[4] = {o[0], o[1], o[2], o[3]};
+          if (gt.mix_src) {
+            const int64_t mr = gt.mix_index ? gt.mix_index[m] : gm;
+            const float4 qv = *reinterpret_cast<const float4*>(gt.mix_src + mr * gt.ld_mix + n);
+            x[0] = mix2(gt.c_act, o[0], gt.c_mix, qv.x); x[1] = mix2(gt.c_act, o[1], gt.c_mix, qv.y);
+            x[2] = mix2(gt.c_act, o[2], gt.c_mix, qv.z); x[3] = mix2(gt.c_act, o[3], gt.c_mix, qv.w);
+          }
+          if (gt.thresh) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] *= mk[e];
+          }
+          store_stream<4>(gt.out + m * gt.ld_out + n, x);
+        }
+      }
+    }
+  if (gt.bits_out) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wavefront's pieces are in LDS
+    int prev = 0;
+    if (lane == 0) prev = __hip_atomic_fetch_add(mw_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    prev = __shfl(prev, 0);
+    asm volatile("" ::: "memory");
+    if (prev == 4 * use + 3) {      // the last of the four: every piece of the tile is in place
+      const int64_t m = r0 + lane;
+      if (m < n_rows) {
+        const uint4* src = reinterpret_cast<const uint4*>(words + lane * 16);
+        const uint4 w01 = src[0], w23 = src[1];
+        uint4* dst = reinterpret_cast<uint4*>(gt.bits_out + gt.row_ids[m] * 4);
+        dst[0] = w01;
+        dst[1] = w23;
+      }
+      ag_signal(mw_done, lane);
+    }
+  }
+}
+
+template <bool FUSED, int GP, bool ACC, bool TB, bool NARROW = false, bool SR = false>
 __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                                             const float* __restrict__ h, int64_t ld_h, float* __restrict__ out,
                                                                             int64_t ld_out, int n_rows, Epilogue ep, int hub_T, FusedEpi fe,
@@ -292,19 +403,21 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
   __shared__ __attribute__((aligned(16))) float tiles[2][kTM * kTLD];
   __shared__ __attribute__((aligned(16))) float cstrip[4][8 * kCLD];
   __shared__ int ready[2], freed[2];
+  __shared__ __attribute__((aligned(16))) unsigned short mwords[SR ? 2 : 1][SR ? kTM * 16 : 8];      // SR: the tile's mask words, in pieces
+  __shared__ int mw_cnt[2], mw_done[2];
   const int lane = lane_id(), wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (wave-uniform by construction: tell the compiler, so that what derives from it stays in SGPRs)
   const bool gathers = wv < kNG;
   const int w = gathers ? wv : wv - kNG;
   const int n_it = ((int)blockIdx.x < n_tiles) ? (n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
   float colsum[4] = {0.f, 0.f, 0.f, 0.f};      // TB: sums of this lane's 4 output columns (64 w + 4 (lane & 15) ..) over the rows it stored
-  const uint64_t seed_eff = TB ? (gt.seed_dev ? gt.seed + *gt.seed_dev : gt.seed) : 0ull;
-  if (threadIdx.x < 2) ready[threadIdx.x] = freed[threadIdx.x] = 0;
+  const uint64_t seed_eff = (TB || SR) ? (gt.seed_dev ? gt.seed + *gt.seed_dev : gt.seed) : 0ull;
+  if (threadIdx.x < 2) ready[threadIdx.x] = freed[threadIdx.x] = mw_cnt[threadIdx.x] = mw_done[threadIdx.x] = 0;
   __syncthreads();
   if (gathers) {
     for (int it = 0; it < n_it; ++it) {
       const int b = it & 1, use = it >> 1;
       if (use > 0) ag_wait(&freed[b], 4 * use, gt.err);
-      ag2_gather_tile<FUSED, GP, ACC>(blockIdx.x + it * gridDim.x, tiles[b], w, lane, rowptr, col, h, ld_h, out, ld_out, n_rows, ep, hub_T, fe);
+      ag2_gather_tile<FUSED, GP, ACC, SR>(blockIdx.x + it * gridDim.x, tiles[b], w, lane, rowptr, col, h, ld_h, out, ld_out, n_rows, ep, hub_T, fe);
       ag_signal(&ready[b], lane);
     }
   } else {
@@ -312,6 +425,8 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
       const int b = it & 1, use = it >> 1;
       ag_wait(&ready[b], kNG * (use + 1), gt.err);
       if constexpr (NARROW) ag2_mfma_tile_head(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b]);
+      else if constexpr (SR)
+        ag2_mfma_tile_rows(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, seed_eff, &freed[b], mwords[b], &mw_cnt[b], &mw_done[b], use);
       else ag2_mfma_tile<TB>(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, colsum, seed_eff, &freed[b]);
     }
   }
@@ -377,7 +492,14 @@ static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N,
   if (n_hubs > 0) {      // hub rows first: the main kernel reads their finished rows back
     const int64_t ld_p = ag_partial_ld(d);
     const dim3 gridc((unsigned)((n_chunks + 3) / 4), 1);
-    if (ep.col_flags)
+    if (ep.col_scale) {      // SR: the source-row factor, as cb_spmm_csr_colscale_f32's hub kernels apply it
+      if (ep.col_flags)
+        hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2, true>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
+                           hub_chunk_ptr, partial, ld_p, ep);
+      else
+        hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 0, true>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
+                           hub_chunk_ptr, partial, ld_p, ep);
+    } else if (ep.col_flags)
       hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
                          hub_chunk_ptr, partial, ld_p, ep);
     else
@@ -394,10 +516,17 @@ static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N,
   const dim3 grid((unsigned)ag_n_blocks(n_tiles)), block(64 * (kNG + 4));
 #define CB_AG2(GP_, TB_) \
   hipLaunchKernelGGL((k_agg_gemm2<FUSED, GP_, ACC, TB_>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles)
-  bool tb = false, narrow = false;
+  bool tb = false, narrow = false, sr = false;
   if constexpr (!FUSED) tb = gt.out2 != nullptr;      // + the trunk backward of the layer below in the dense tail's epilogue
   if constexpr (!FUSED) {
     if (tb) { if (ep.col_flags) CB_AG2(2, true); else CB_AG2(0, true); }
+  }
+  if constexpr (!FUSED && !ACC) {      // the trunk's store on a subset of the node rows as the tail (source-row factor in the gathers)
+    sr = gt.row_ids != nullptr;
+    if (sr) {
+      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<false, 2, false, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+      else hipLaunchKernelGGL((k_agg_gemm2<false, 0, false, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+    }
   }
   if constexpr (FUSED) {      // the output Linear (<= 64 classes) as the tail: gt.n_out > 0
     narrow = gt.n_out > 0;
@@ -406,7 +535,7 @@ static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N,
       else hipLaunchKernelGGL((k_agg_gemm2<true, 0, ACC, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
     }
   }
-  if (!tb && !narrow) { if (ep.col_flags) CB_AG2(2, false); else CB_AG2(0, false); }
+  if (!tb && !narrow && !sr) { if (ep.col_flags) CB_AG2(2, false); else CB_AG2(0, false); }
 #undef CB_AG2
   CB_LAUNCH_CHECK();
   return CB_OK;
@@ -527,6 +656,36 @@ extern "C" int cb_spmm_gemm_trunkbwd_f32(const int32_t* rowptr, const int32_t* c
     CB_LAUNCH_CHECK();
   }
   return CB_OK;
+}
+
+// The sum-first layer of the rows-only forward (trunk.py _layer_on_rows) in one kernel: out = H = sum_u col_scale[u] * h[u] over each row's edges
+// (cb_spmm_csr_colscale_f32, stored: the backward's source-side level reads it) and, from the dense tail, the trunk's store on the node rows row_ids
+// of H's rows — g_out = dropout(c_act * relu(g_rowscale * (H @ B) + bias) + c_mix * mix_src[mix_index[m] | row_ids[m]]), out_act = the ReLU output,
+// relu_bits[row_ids[m]] = its mask words (cb_gemm_nn_store_rows_f32: the same values bit for bit).
+extern "C" int cb_spmm_gemm_store_rows_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
+                                           int64_t d, const float* col_scale, float* out, int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks,
+                                           const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
+                                           const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src, int64_t ld_mix,
+                                           const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                           int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* g_out,
+                                           int64_t ld_gout, void* stream) {
+  const int rc = agg_gemm_common_checks("cb_spmm_gemm_store_rows_f32", N, E, d, rowptr, col, h, ld_h, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
+                                        ws, ws_bytes, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
+  if (rc != CB_OK || N == 0) return rc;
+  CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids && (!mix_src || (ag_al16(mix_src) && ld_mix % 4 == 0 && ld_mix >= kND)) &&
+                   (!out_act || (ag_al16(out_act) && ld_act % 4 == 0 && ld_act >= kND)) && (!relu_bits || ag_al16(relu_bits)),
+               CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: null pointer or misaligned rows");
+  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: dropout p / row offset out of range");
+  if (n_hubs == 0) hub_T = INT32_MAX;
+  Epilogue ep{nullptr, nullptr, 0, nullptr, 0, col_flags};
+  ep.col_scale = col_scale;
+  GemmTail gt{(const uint4*)image, g_rowscale, nullptr, 0, g_out, ld_gout};
+  gt.c_act = c_act; gt.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u; gt.keep_scale = 1.f / (1.f - drop_p);
+  gt.seed = seed; gt.seed_dev = seed_dev; gt.row0 = row0; gt.bias = bias;
+  gt.row_ids = row_ids; gt.mix_src = mix_src; gt.ld_mix = ld_mix; gt.mix_index = mix_index; gt.c_mix = c_mix;
+  gt.bits_out = (unsigned long long*)relu_bits; gt.bits_relu_only = bits_relu_only; gt.out_act = out_act; gt.ld_act = ld_act;
+  return launch_agg_gemm<false, false>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
+                                       (hipStream_t)stream, FusedEpi{}, gt);
 }
 
 // Fused trunk store (cb_spmm_csr_fused_f32 / cb_spmm_csr_fused_acc_f32: ReLU / mix / dropout, mask words, out_next) + g_out = g_rowscale *

@@ -310,7 +310,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
   // MIXB (FusedEpi): my_xp0 / my_xp1: lane i holds the position of local row i in the compact operands; cs_acc: the wavefront's 4 running column sums
   static_assert(!MIXB || (FUSED && VEC == 4 && FULL && !ACC && TLD == 0 && !P65), "folded mix gradients: the fused d % 256 == 0 kernel on all node rows");
   static_assert(TLD == 0 || (VEC == 4 && FULL), "on-chip row tile: d == 256, float4 lanes");
-  static_assert(!CS || (!P65 && !FUSED && !ACC && sizeof(HT) == 4), "source-row factor: plain fp32 aggregation only");
+  static_assert(!CS || (!FUSED && !ACC && sizeof(HT) == 4), "source-row factor: plain fp32 aggregation only");
   struct PtrAt {      // rowptr of local row i (wave-uniform i)
     int v, hi;
     __device__ __forceinline__ int operator()(int i) const {
@@ -470,8 +470,14 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
           if (u < nb) {
             const int e = base + k + u;
             while (e == cur_end) flush();
+            if constexpr (CS) {
+              const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k + u));
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[i] += v[u][i];
+              for (int i = 0; i < VEC; ++i) acc[i] += cs * v[u][i];
+            } else {
+#pragma unroll
+              for (int i = 0; i < VEC; ++i) acc[i] += v[u][i];
+            }
           }
         }
         k = cnt;

@@ -634,6 +634,57 @@ class CSRGraph:
                                  self.N * 256 * 4 * (2 if g_addend is not None else 1) + (4 * self.N if g_rowscale is not None else 0)))
         return out, g_out
 
+    def spmm_gemm_store_rows(self, h, col_scale, image, rowscale, bias, row_ids, mix, mix_index, c_act, c_mix, p, seed, row0, bits, relu_only,
+                             want_act=False):
+        """(H, out, act | None) of cb_spmm_gemm_store_rows_f32: H = spmm(h, col_scale=col_scale) (stored) and, from the same kernel, the trunk's
+        store on the node rows row_ids (int64 [N]) of this CSR's rows — act = relu(rowscale * (H @ B) + bias), out = dropout(c_act * act + c_mix *
+        mix[mix_index | row_ids]), mask words in bits (the full [n_nodes, 1, 4] array, rows row_ids written) — with B the 256 x 256 matrix behind
+        `image` (weight_image): the values of spmm(col_scale=...) followed by gemm.mm_nn_store_rows, bit for bit."""
+        import ctypes
+        from . import ops
+        lib = _lib.load()
+        _lib.require_device(h, col_scale, image, rowscale, bias, row_ids, mix, mix_index, bits)
+        d = h.shape[1] if h.dim() == 2 else -1
+        if h.dtype != torch.float32 or d != 256 or h.shape[0] != self.n_cols or h.stride(1) != 1:
+            raise ValueError(f'spmm_gemm_store_rows: float32 [{self.n_cols}, 256] rows expected, got {tuple(h.shape)} {h.dtype}')
+        if col_scale.dtype != torch.float32 or col_scale.numel() != self.n_cols:
+            raise ValueError('spmm_gemm_store_rows: one float32 source-row factor per column expected')
+        if row_ids.dtype != torch.int64 or row_ids.numel() != self.N or (mix_index is not None and (mix_index.dtype != torch.int64 or mix_index.numel() != self.N)):
+            raise ValueError('spmm_gemm_store_rows: int64 row_ids / mix_index with one entry per row expected')
+        if bits.dtype != torch.int64 or bits.dim() != 3 or tuple(bits.shape[1:]) != (1, 4) or not bits.is_contiguous():
+            raise ValueError('spmm_gemm_store_rows: int64 [n_nodes, 1, 4] mask words expected')
+        if mix is not None and mix.stride(1) != 1:
+            mix = mix.contiguous()
+        dev = h.device
+        out = torch.empty((self.N, d), dtype=torch.float32, device=dev)
+        g_out = torch.empty((self.N, 256), dtype=torch.float32, device=dev)
+        act = torch.empty_like(g_out) if want_act else None
+        col_k = self.flagged_cols(False, d * 4)
+        flags = int(col_k is not None and h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
+        rowptr, col, plan = self.rowptr, col_k if flags else self.col, self._plan
+        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
+        ws = self._workspace(ws_bytes)
+        prof = self.profile
+        if prof is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_spmm_gemm_store_rows_f32(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
+                                                       _lib.ptr(col_scale.contiguous()), _lib.ptr(out), d, self.hub_threshold, plan.n_hubs, plan.n_chunks,
+                                                       _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes, _lib.ptr(image),
+                                                       _lib.ptr(rowscale), _lib.ptr(bias), _lib.ptr(row_ids), _lib.ptr(mix),
+                                                       mix.stride(0) if mix is not None else 0, _lib.ptr(mix_index), float(c_act), float(c_mix), float(p),
+                                                       ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(bits), int(bool(relu_only)),
+                                                       _lib.ptr(act), 256, _lib.ptr(g_out), 256, _lib.stream_ptr()),
+                       'cb_spmm_gemm_store_rows_f32')
+        if prof is not None:
+            ev1.record()
+            # SURVEY §8(d) bytes of the aggregation (+ the source-row factors); the store's own streams (mix rows in, stored rows / ReLU output
+            # out, row ids, row scales, mask words) are kept apart
+            tail = self.N * 256 * 4 * (1 + int(mix is not None) + int(want_act)) + 12 * self.N + 32 * self.N
+            prof.append(prof_rec(ev0, ev1, self, 'agg_gemm_store_rows', self.algorithmic_bytes(d, row_scale=False, bias=False) + 4 * self.E, 0, tail))
+        return out, g_out, act
+
     def _acc_out(self, acc_init, d, device):
         """Output matrix of an aggregation that starts from partial sums: the sums themselves (in place), else a fresh [N, d] matrix."""
         if acc_init is None:

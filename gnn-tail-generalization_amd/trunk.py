@@ -470,15 +470,22 @@ def _layer_on_rows(graph, space, fwd, col_scale, cur, w, b, mix, mix_index, alph
     table on all node rows, GCN.py:230-232: Z = a * (X W) + le): its rows are summed the same way, Y = b * (H W + (A le)[space]) + bias, over fwd_le —
     the same orientation with node-row sources.  Returns (mask words [N, d/256, 4] with the rows of `space` written, stored rows, ReLU output | None, H)."""
     fwd.profile = getattr(graph, 'profile', None)
-    h_agg = fwd.spmm(cur, col_scale=col_scale)
     b_rows = getattr(space, '_norm_in', None)
     if b_rows is None:
         b_rows = space._norm_in = graph.norm_in[space.idx].contiguous()
+    bits = torch.empty((graph.N, w.shape[1] // 256, 4), dtype=torch.int64, device=cur.device)
+    if (le is None and tuple(w.shape) == (256, 256) and hasattr(fwd, 'spmm_gemm_store_rows') and fwd.E >= T.agg_gemm_store_rows_min_edges
+            and agg_gemm_eligible(graph, 256, False)):
+        # the three in one kernel (cb_spmm_gemm_store_rows_f32): the transform and the store run on the matrix cores under the gathers, H is not re-read
+        from .graph import weight_image
+        h_agg, x_next, act = fwd.spmm_gemm_store_rows(cur, col_scale, weight_image(w), b_rows, b, space.idx, mix, mix_index, 1 - alpha, alpha, p, seed,
+                                                      row0, bits, residual, want_act)
+        return bits, x_next, act, h_agg
+    h_agg = fwd.spmm(cur, col_scale=col_scale)
     le_sum = None
     if le is not None:
         fwd_le.profile = fwd.profile
         le_sum = fwd_le.spmm(le, row_scale=b_rows)
-    bits = torch.empty((graph.N, w.shape[1] // 256, 4), dtype=torch.int64, device=cur.device)
     # the store as the epilogue of the transform where that form exists (hidden 256), else the transform and then the elementwise pass: same values
     fused = gemm.mm_nn_store_rows(h_agg, w, b_rows, le_sum, b, space.idx, mix, mix_index, 1 - alpha, alpha, p, seed, row0, bits, residual, want_act)
     if fused is not None:

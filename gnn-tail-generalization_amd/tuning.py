@@ -36,6 +36,10 @@ class Tuning:
     # the source rows' side) once S_1's rows are entered by at least this many edges — below, the Z-first form on S_1 (one kernel) wins on launches.
     # S-arxiv (1.7 * 10^6 edges into S_1): 2.94 -> 3.11 ms/step with the sum first; S-products: 90.1 -> 89.4; S-pl10M (7.4 * 10^7): 125.3 -> 120.9
     sum_first_below_min_edges: int = 1 << 24
+    # rows-only forward: a sum-first layer (no structural-embedding table, hidden 256) runs its aggregation, transform and store as ONE kernel
+    # (CSRGraph.spmm_gemm_store_rows) once its orientation has at least this many edges; below, the aggregation and then the transform with the store
+    # in its epilogue.  Same values either way.  S-pl10M: both layers (7.4 * 10^7 and 9.9 * 10^6 edges) faster as one kernel (profiles/r07_agg_gemm_store_rows.md)
+    agg_gemm_store_rows_min_edges: int = 0
     # rows-only forward: not below this many nodes, even where a replayed step (graph.rowsparse_small_ok) takes the row-sparse backward — the last layer
     # as aggregate + transform + store + head on the loss rows is four launches for one.  S-pubmed config 2 (19 717 nodes, bf16 rows, hipGraph replay):
     # 0.795 ms/step with it, 0.752 without (round 6, one box, alternating runs; the round-5 tree the same: 0.803 / 0.748); S-arxiv (169 343): 3.38 -> 2.94 with it

@@ -621,6 +621,22 @@ int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const uint64_t* x
                            float g_drop_p, uint64_t g_seed, float x_drop_p, uint64_t x_seed, const uint64_t* seed_dev, int64_t row0, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* The sum-first GCNConv + store of the rows-only training forward in one persistent kernel (replaces GCN.py:213-256 with the sum taken first,
+ * then :127-133 on a subset of the node rows: cb_spmm_csr_colscale_f32 followed by cb_gemm_nn_store_rows_f32 — the same values bit for bit):
+ *     out   = H[v] = sum_{u in row v} col_scale[u] * h[u]                  [N, 256] (stored: the backward's source-side level reads it)
+ *     act   = relu(g_rowscale[m] * (H @ B)[m] + bias)                      -> out_act [N, ld_act] if given
+ *     g_out = dropout_{seed, node row}(c_act * act + c_mix * mix_src[mix_index[m] | row_ids[m]])
+ *     relu_bits[row_ids[m]][0..3] = the mask words of act > 0 (AND kept by the dropout unless bits_relu_only), as cb_gemm_nn_store_rows_f32
+ * row_ids (int64 [N]): the node row of each CSR row; the dropout mask is drawn at (row0 + row_ids[m]).  d must be 256, fp32 rows, 16-byte aligned;
+ * image: cb_agg_gemm_image_f32 of W.  A tile hand-over that times out is recorded in the device error word (cb_device_status). */
+int cb_spmm_gemm_store_rows_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
+                                int64_t d, const float* col_scale, float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
+                                const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
+                                const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src, int64_t ld_mix,
+                                const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* g_out,
+                                int64_t ld_gout, void* stream);
+
 /* cb_spmm_gemm_f32 (reverse aggregation + dX contraction) + the trunk backward of the layer below from the same epilogue: g_out is
  * dL/dx of the stage above layer l-1; gr_out = c_act * dropout_bwd_{seed}(g_out) * relu_bits * rowscale2 (input of the next reverse
  * aggregation) and colsum = the column sums of the same without rowscale2 (bias gradient of layer l-1) — what cb_trunk_layer_bwd_f32
