@@ -122,8 +122,6 @@ SIGNATURES = {
     'cb_spmm_gemm_store_rows_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P,
                                                    _P, _P, _P, _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P,
                                                    _I64, _P, _I32, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_trunkbwd_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P, _P,
-                                                 _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _P, _I64, _P, _P, _SZ, _P]),
     'cb_spmm_csr_weighted_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P]),
     'cb_spmm_edge_dot_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P]),
     'cb_gemm_nn_indrop_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64]),
@@ -139,7 +137,6 @@ SIGNATURES = {
                                           ctypes.c_uint64, ctypes.c_uint64, _P, _I64, _P]),
     'cb_gemm_tn_gdrop_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64]),
     'cb_gemm_tn_gdrop_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _SZ, _P]),
-    'cb_spmm_gemm_trunkbwd_workspace_bytes': (_SZ, []),
     'cb_spmm_csr_lp_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, _P, _P, _I64, _I32, _I32, _I32, _P, _P,
                                           _P, _SZ, _P]),
     'cb_trunk_input_bwd_multi_f32': (ctypes.c_int, [_P, ctypes.c_uint64, _I32, _P, _P, ctypes.c_float, _P, _P, _I64, _I64, ctypes.c_float,
@@ -147,7 +144,7 @@ SIGNATURES = {
     'cb_trunk_input_bwd_multi_cs_f32': (ctypes.c_int, [_P, ctypes.c_uint64, _I32, _P, _P, ctypes.c_float, _P, _P, _I64, _I64, ctypes.c_float,
                                                        _P, _I64, _P, _P, _SZ, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     'cb_spmm_csr_store_bwd_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
-                                                 _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P, _P]),
+                                                 _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
     'cb_spmm_store_bwd_mix_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
     'cb_spmm_csr_store_bwd_mix_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
                                                      _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _I32, _P, _P, _P, ctypes.c_float, _P, _P, _SZ, _P]),

@@ -40,20 +40,13 @@ struct GemmTail {
   int64_t ld_add;
   float* out;              // [rows, ld_out]
   int64_t ld_out;
-  // TB kernels only (trunk backward): the value just computed is dL/dx of the stage above layer l-1; the backward of that layer's fused
-  // store — what cb_trunk_layer_bwd_f32 does in a pass of its own — leaves the same epilogue:
-  //   out2 = c_act * keep(seed, m, n) * g * relu_bit_{l-1}(m, n) * rowscale2[m];   colsum partial[block][n] += (the same without rowscale2)
-  const unsigned long long* bits;   // [rows][4] mask words of the forward store of layer l-1 (d = 256: one tile)
+  // SR kernels only (described below): the store's factor and dropout
   float c_act;
   uint32_t thresh;
   float keep_scale;
   uint64_t seed;
   const uint64_t* seed_dev;
   int64_t row0;
-  const float* rowscale2;
-  float* out2;
-  int64_t ld_out2;
-  float* colsum_partial;   // [gridDim.x][256] or null
   int* err;                // device-visible error word (cb_error.hip): a tile hand-over that timed out is recorded here, never silent
   // NARROW kernels only (the output Linear as the tail of the last layer's aggregation, GCN.py:133-138): out[m][n] = acc + bias[n], n < n_out <= 64
   const float* bias;       // [n_out] or null (SR kernels: [256] or null)
@@ -199,9 +192,8 @@ __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile,
 
 // One K step of B fragments in flight per multiplying wavefront (two register buffers, K loop unrolled by two): next to wavefronts that
 // keep dozens of gathers outstanding, a load of this CU — L2 hit or not — comes back after microseconds.
-template <bool TB>
 __device__ __forceinline__ void ag2_mfma_tile(int t, const float* __restrict__ tile, float* __restrict__ cs, int w, int lane, int n_rows,
-                                              const GemmTail& gt, float (&colsum)[4], uint64_t seed_eff, int* freed) {
+                                              const GemmTail& gt, int* freed) {
   const int l31 = lane & 31, lh = lane >> 5;
   f32x16 acc[2][2];
   tile_times_image<kNS, kTLD>(tile, gt.image, w, lane, acc);
@@ -235,29 +227,7 @@ __device__ __forceinline__ void ag2_mfma_tile(int t, const float* __restrict__ t
           float o[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = o[e] * rs + ad[e] + zero_bias;
-          float gm[4] = {o[0], o[1], o[2], o[3]};
-          if constexpr (TB) {      // the arithmetic of k_trunk_bwd<0> (cb_elementwise.hip), element for element
-            if (gt.thresh) {
-              float mk[4];
-              keep4(seed_eff, ((gt.row0 + m) * kND + n) >> 2, gt.thresh, gt.keep_scale, mk);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) gm[e] *= mk[e];
-            }
-          }
           store_stream<4>(gt.out + m * gt.ld_out + n, o);
-          if constexpr (TB) {
-            const unsigned long long* bw = gt.bits + m * 4;      // word e, bit L <-> column 4 L + e
-            const int L = n >> 2;
-            const float sc2 = gt.rowscale2 ? gt.rowscale2[m] : 1.f;
-            float gy[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              gy[e] = ((bw[e] >> L) & 1ull) ? gt.c_act * gm[e] : 0.f;
-              colsum[e] += gy[e];
-              gy[e] *= sc2;
-            }
-            store_stream<4>(gt.out2 + m * gt.ld_out2 + n, gy);
-          }
         }
       }
     }
@@ -395,7 +365,7 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
   }
 }
 
-template <bool FUSED, int GP, bool ACC, bool TB, bool NARROW = false, bool SR = false>
+template <bool FUSED, int GP, bool ACC, bool NARROW = false, bool SR = false>
 __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                                             const float* __restrict__ h, int64_t ld_h, float* __restrict__ out,
                                                                             int64_t ld_out, int n_rows, Epilogue ep, int hub_T, FusedEpi fe,
@@ -409,8 +379,7 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
   const bool gathers = wv < kNG;
   const int w = gathers ? wv : wv - kNG;
   const int n_it = ((int)blockIdx.x < n_tiles) ? (n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-  float colsum[4] = {0.f, 0.f, 0.f, 0.f};      // TB: sums of this lane's 4 output columns (64 w + 4 (lane & 15) ..) over the rows it stored
-  const uint64_t seed_eff = (TB || SR) ? (gt.seed_dev ? gt.seed + *gt.seed_dev : gt.seed) : 0ull;
+  const uint64_t seed_eff = SR ? (gt.seed_dev ? gt.seed + *gt.seed_dev : gt.seed) : 0ull;
   if (threadIdx.x < 2) ready[threadIdx.x] = freed[threadIdx.x] = mw_cnt[threadIdx.x] = mw_done[threadIdx.x] = 0;
   __syncthreads();
   if (gathers) {
@@ -427,35 +396,9 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
       if constexpr (NARROW) ag2_mfma_tile_head(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b]);
       else if constexpr (SR)
         ag2_mfma_tile_rows(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, seed_eff, &freed[b], mwords[b], &mw_cnt[b], &mw_done[b], use);
-      else ag2_mfma_tile<TB>(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, colsum, seed_eff, &freed[b]);
+      else ag2_mfma_tile(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b]);
     }
   }
-  if constexpr (TB) {
-    // column sums of the block's rows: the four lanes that own the same column quad are added in a fixed order, then one partial row per
-    // block (summed over the blocks by k_agg_colsum_finish in block order: no float atomics, bit-reproducible)
-    if (!gathers && gt.colsum_partial) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = colsum[e];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        colsum[e] = v;
-      }
-      if (lane < 16) {
-        float* pp = gt.colsum_partial + (int64_t)blockIdx.x * kND + 64 * w + 4 * lane;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pp[e] = colsum[e];
-      }
-    }
-  }
-}
-
-// out[c] = sum over blocks of partial[block][c], blocks in ascending order (one thread per column)
-__global__ void __launch_bounds__(256) k_agg_colsum_finish(const float* __restrict__ partial, int n_blocks, float* __restrict__ out) {
-  const int c = threadIdx.x;
-  float s = 0.f;
-  for (int b = 0; b < n_blocks; ++b) s += partial[(int64_t)b * kND + c];
-  out[c] = s;
 }
 
 // Fault injection for the hand-over's failure path (tests only reach it through cb_agg_gemm_handover_selftest): one wavefront waits, with a
@@ -468,7 +411,7 @@ __global__ void __launch_bounds__(64) k_agg_handover_selftest(int* err) {
 }
 
 static inline int64_t ag_partial_ld(int64_t d) { return (d + 3) / 4 * 4; }
-constexpr int kMaxBlocks = 1024;      // (cb_spmm_gemm_trunkbwd_workspace_bytes: one partial row per block)
+constexpr int kMaxBlocks = 1024;      // cap of the persistent grid
 
 // blocks of the persistent kernel: one per CU of the current device (139 KB of LDS each)
 static int ag_n_blocks(int n_tiles) {
@@ -514,29 +457,25 @@ static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N,
   }
   const int n_tiles = (int)((N + kTM - 1) / kTM);
   const dim3 grid((unsigned)ag_n_blocks(n_tiles)), block(64 * (kNG + 4));
-#define CB_AG2(GP_, TB_) \
-  hipLaunchKernelGGL((k_agg_gemm2<FUSED, GP_, ACC, TB_>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles)
-  bool tb = false, narrow = false, sr = false;
-  if constexpr (!FUSED) tb = gt.out2 != nullptr;      // + the trunk backward of the layer below in the dense tail's epilogue
-  if constexpr (!FUSED) {
-    if (tb) { if (ep.col_flags) CB_AG2(2, true); else CB_AG2(0, true); }
-  }
+  bool narrow = false, sr = false;
   if constexpr (!FUSED && !ACC) {      // the trunk's store on a subset of the node rows as the tail (source-row factor in the gathers)
     sr = gt.row_ids != nullptr;
     if (sr) {
-      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<false, 2, false, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-      else hipLaunchKernelGGL((k_agg_gemm2<false, 0, false, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<false, 2, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+      else hipLaunchKernelGGL((k_agg_gemm2<false, 0, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
     }
   }
   if constexpr (FUSED) {      // the output Linear (<= 64 classes) as the tail: gt.n_out > 0
     narrow = gt.n_out > 0;
     if (narrow) {
-      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<true, 2, ACC, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-      else hipLaunchKernelGGL((k_agg_gemm2<true, 0, ACC, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<true, 2, ACC, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+      else hipLaunchKernelGGL((k_agg_gemm2<true, 0, ACC, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
     }
   }
-  if (!tb && !narrow && !sr) { if (ep.col_flags) CB_AG2(2, false); else CB_AG2(0, false); }
-#undef CB_AG2
+  if (!narrow && !sr) {
+    if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<FUSED, 2, ACC>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+    else hipLaunchKernelGGL((k_agg_gemm2<FUSED, 0, ACC>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+  }
   CB_LAUNCH_CHECK();
   return CB_OK;
 }
@@ -612,50 +551,6 @@ extern "C" int cb_spmm_gemm_f32(const int32_t* rowptr, const int32_t* col, int32
                                         (hipStream_t)stream, FusedEpi{}, gt);
   return launch_agg_gemm<false, false>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
                                        (hipStream_t)stream, FusedEpi{}, gt);
-}
-
-// cb_spmm_gemm_f32 + the trunk backward of the layer below from the dense tail's epilogue (TB): g_out = g_rowscale * (out @ B) is dL/dx of
-// the stage above layer l-1, and gr_out = c_act * dropout_bwd_{seed}(g_out) * relu_bits * rowscale2 (the input of the next reverse
-// aggregation) with colsum = column sums of the same without rowscale2 (that layer's bias gradient) — cb_trunk_layer_bwd_f32 without
-// its 10 GB read of g_out.  ws2: cb_spmm_gemm_trunkbwd_workspace_bytes() for the per-block partial column sums.
-extern "C" size_t cb_spmm_gemm_trunkbwd_workspace_bytes(void) { return (size_t)kMaxBlocks * kND * sizeof(float); }
-
-extern "C" int cb_spmm_gemm_trunkbwd_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h,
-                                         int64_t ld_h, int64_t d, const float* acc_init, int64_t ld_init, float* out, int64_t ld_out, int32_t hub_T,
-                                         int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                                         size_t ws_bytes, const void* image, const float* g_rowscale, float* g_out, int64_t ld_gout,
-                                         const uint64_t* relu_bits, float c_act, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                                         const float* rowscale2, float* gr_out, int64_t ld_gr, float* colsum, void* ws2, size_t ws2_bytes,
-                                         void* stream) {
-  const int rc = agg_gemm_common_checks("cb_spmm_gemm_trunkbwd_f32", N, E, d, rowptr, col, h, ld_h, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
-                                        ws, ws_bytes, image, nullptr, 0, g_out, ld_gout, acc_init, ld_init);
-  if (rc != CB_OK) return rc;
-  if (N == 0) {
-    if (colsum) CB_HIP(hipMemsetAsync(colsum, 0, kND * sizeof(float), (hipStream_t)stream));
-    return CB_OK;
-  }
-  CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d && relu_bits && gr_out && ag_al16(gr_out) && ld_gr % 4 == 0 && ld_gr >= kND &&
-                   drop_p >= 0.f && drop_p < 1.f && row0 >= 0,
-               CB_E_INVALID, "cb_spmm_gemm_trunkbwd_f32: null pointer, misaligned rows or bad p");
-  CB_CHECK_ARG(!colsum || (ws2 && ws2_bytes >= cb_spmm_gemm_trunkbwd_workspace_bytes()), CB_E_WORKSPACE, "cb_spmm_gemm_trunkbwd_f32: workspace too small");
-  if (n_hubs == 0) hub_T = INT32_MAX;
-  Epilogue ep{nullptr, nullptr, 0, acc_init, ld_init, col_flags};
-  GemmTail gt{(const uint4*)image, g_rowscale, nullptr, 0, g_out, ld_gout};
-  gt.bits = (const unsigned long long*)relu_bits; gt.c_act = c_act; gt.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
-  gt.keep_scale = 1.f / (1.f - drop_p); gt.seed = seed; gt.seed_dev = seed_dev; gt.row0 = row0; gt.rowscale2 = rowscale2;
-  gt.out2 = gr_out; gt.ld_out2 = ld_gr; gt.colsum_partial = colsum ? (float*)ws2 : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const int rc2 = acc_init ? launch_agg_gemm<false, true>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
-                                                           (float*)ws, st, FusedEpi{}, gt)
-                           : launch_agg_gemm<false, false>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
-                                                            (float*)ws, st, FusedEpi{}, gt);
-  if (rc2 != CB_OK) return rc2;
-  if (colsum) {
-    const int n_tiles = (int)((N + kTM - 1) / kTM);
-    hipLaunchKernelGGL(k_agg_colsum_finish, dim3(1), dim3(256), 0, st, (const float*)ws2, ag_n_blocks(n_tiles), colsum);
-    CB_LAUNCH_CHECK();
-  }
-  return CB_OK;
 }
 
 // The sum-first layer of the rows-only forward (trunk.py _layer_on_rows) in one kernel: out = H = sum_u col_scale[u] * h[u] over each row's edges

@@ -322,16 +322,15 @@ int launch_tn_limb3(const float* A, int64_t lda, const float* G, int64_t ldg, co
     // Round 5: the whole 256 x 256 weight gradient of a hidden layer as ONE tile of eight wavefronts (wave tile 64 x 128 as before): each operand
     // element is staged — split into limbs — once, where the 128 x 256 tile staged the gradient operand twice: 2.1 instead of 3.1 staging VALU per
     // MFMA on a kernel whose SIMDs are issue-bound (PMC: matrix pipe 62 % + VALU 39 % of the cycles, profiles/r05_gemm_tn_pmc_raw.txt).
-    // 7.29 -> 6.55 ms at M = 10^7, bit-identical (same K order per output element).  CB_GEMM_TN_WIDE=0 keeps the 128 x 256 tile.
-    static const bool wide = !(getenv("CB_GEMM_TN_WIDE") && getenv("CB_GEMM_TN_WIDE")[0] == '0');
-    if (wide && !ad.thresh && !gd.thresh && K1 == 256 && K2 == 256 && nsplit >= 256) {      // (fewer slabs than CUs — a Pubmed-sized M —: the 128 x 256 tile has twice the blocks)
+    // 7.29 -> 6.55 ms at M = 10^7, bit-identical (same K order per output element).
+    if (!ad.thresh && !gd.thresh && K1 == 256 && K2 == 256 && nsplit >= 256) {      // (fewer slabs than CUs — a Pubmed-sized M —: the 128 x 256 tile has twice the blocks)
       launch_tn_l3_t<4, 2, 4>(A, lda, G, ldg, rowscale, partial, M, K1, K2, nsplit, rows_per_split, st, gd, ad);
       CB_LAUNCH_CHECK();
       return CB_OK;
     }
     // the same for the input Linear's weight gradient (256 x F, F <= 128, the dropout mask of the features regenerated while they are staged): one
     // 256 x 128 tile of eight wavefronts draws every mask quad once instead of once per 128-row tile
-    if (wide && gd.thresh && !ad.thresh && !rowscale && K1 == 256 && K2 <= 128 && K2 > 64 && nsplit >= 256) {
+    if (gd.thresh && !ad.thresh && !rowscale && K1 == 256 && K2 <= 128 && K2 > 64 && nsplit >= 256) {
       launch_tn_l3_t<4, 2, 2>(A, lda, G, ldg, rowscale, partial, M, K1, K2, nsplit, rows_per_split, st, gd, ad);
       CB_LAUNCH_CHECK();
       return CB_OK;

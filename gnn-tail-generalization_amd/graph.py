@@ -198,12 +198,11 @@ class CSRGraph:
         builds, hits = getattr(self, '_support_builds', 0), getattr(self, '_support_hits', 0)
         return builds < 4 or hits >= 3 * builds
 
-    def spmm_store_bwd(self, h, row_scale, bits, bwd_rowscale, c_act, p, seed, row0, row_ids=None, mix=None):
+    def spmm_store_bwd(self, h, row_scale, bits, bwd_rowscale, c_act, p, seed, row0, mix=None):
         """(g, gr) of cb_spmm_csr_store_bwd_f32 over this (forward-orientation) CSR: g = row_scale * sum of the gathered rows, gr = the backward of the
         trunk's store applied to g (mask words `bits` of the written rows, dropout mask of `seed`, factor c_act, row factor bwd_rowscale) — the plain
-        aggregation followed by cb_trunk_layer_bwd_f32 without the pass's read of g.  h float32 [n_cols, d], d % 256 == 0.  row_ids (int32 [N]): this CSR's rows
-        are a subset of the node rows (a compact level) — bits / bwd_rowscale / the dropout mask at the node row, row_scale and the results compact.
-        mix = (operands, positions, seeds, c_mix, want_colsum) (all node rows only; <= 2 compact operands [n_q, d] with int32 position maps [N]): the first
+        aggregation followed by cb_trunk_layer_bwd_f32 without the pass's read of g.  h float32 [n_cols, d], d % 256 == 0.
+        mix = (operands, positions, seeds, c_mix, want_colsum) (<= 2 compact operands [n_q, d] with int32 position maps [N]): the first
         result is the FOLDED mix gradient c_mix * (dropout_bwd(g) + sum_q dropout_bwd_q(operand_q)) instead of g, and a third result = the column sums of
         gr / bwd_rowscale (the store's bias gradient) or None (cb_spmm_csr_store_bwd_mix_f32)."""
         import ctypes
@@ -228,8 +227,8 @@ class CSRGraph:
             ev0.record()
         if mix is not None:
             ops_, pos_, seeds_, c_mix, want_cs = mix
-            if row_ids is not None or len(ops_) > 2 or any(q is None for q in pos_):
-                raise ValueError('spmm_store_bwd(mix=...): all node rows, at most two compact operands with position maps')
+            if len(ops_) > 2 or any(q is None for q in pos_):
+                raise ValueError('spmm_store_bwd(mix=...): at most two compact operands with position maps')
             k = len(ops_)
             colsum = torch.empty(d, dtype=torch.float32, device=h.device) if want_cs else None
             ws2b = lib.cb_spmm_store_bwd_mix_workspace_bytes(self.N, plan.n_hubs, d) if want_cs else 0
@@ -251,7 +250,7 @@ class CSRGraph:
             _lib.check(lib.cb_spmm_csr_store_bwd_f32(_lib.ptr(self.rowptr), _lib.ptr(col_k if flags else self.col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
                                                      _lib.ptr(row_scale), _lib.ptr(bits), _lib.ptr(bwd_rowscale), float(c_act), float(p), ctypes.c_uint64(seed),
                                                      ops.seed_dev_ptr(), int(row0), _lib.ptr(g), d, _lib.ptr(gr), d, self.hub_threshold, plan.n_hubs, plan.n_chunks,
-                                                     _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), wsb, _lib.ptr(row_ids), _lib.stream_ptr()),
+                                                     _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), wsb, _lib.stream_ptr()),
                        'cb_spmm_csr_store_bwd_f32')
         if prof is not None:
             ev1.record()
@@ -473,51 +472,6 @@ class CSRGraph:
             prof.append(prof_rec(ev0, ev1, self, 'colscale' if col_scale is not None else 'plain',
                                  self.algorithmic_bytes(d, row_scale=row_scale is not None, bias=bias is not None, src_elem=2 if bf16 else 4)))
         return out
-
-    def spmm_gemm_trunkbwd(self, h, image, g_rowscale, bits, c_act, p, seed, row0, rowscale2, want_colsum, transpose=True, acc_init=None):
-        """(out, g, gr, colsum) of cb_spmm_gemm_trunkbwd_f32: out = A h (raw sums), g = g_rowscale * (out @ B) and, from the same epilogue, the
-        trunk backward of the layer below: gr = c_act * dropout_bwd(g) * bits * rowscale2, colsum = column sums of the unscaled gr.
-        acc_init: partial sums of the earlier passes of a node-sharded aggregation (the row sums start from them; overwritten by `out`)."""
-        import ctypes
-        from . import ops
-        lib = _lib.load()
-        _lib.require_device(h, image, g_rowscale, bits, rowscale2, acc_init)
-        d = h.shape[1] if h.dim() == 2 else -1
-        if h.dtype != torch.float32 or d != 256 or h.shape[0] != self.n_cols or h.stride(1) != 1:
-            raise ValueError(f'spmm_gemm_trunkbwd: float32 [{self.n_cols}, 256] rows expected, got {tuple(h.shape)} {h.dtype}')
-        if bits.dtype != torch.int64 or tuple(bits.shape) != (self.N, 1, 4) or not bits.is_contiguous():
-            raise ValueError('spmm_gemm_trunkbwd: int64 [N, 1, 4] mask words expected')
-        dev = h.device
-        out = self._acc_out(acc_init, d, dev)
-        g = torch.empty((self.N, 256), dtype=torch.float32, device=dev)
-        gr = torch.empty((self.N, 256), dtype=torch.float32, device=dev)
-        colsum = torch.empty(256, dtype=torch.float32, device=dev) if want_colsum else None
-        rowptr, col, plan = (self.rowptr_t, self.col_t, self._plan_t) if transpose else (self.rowptr, self.col, self._plan)
-        col_k = self.flagged_cols(transpose, d * 4)
-        flags = int(col_k is not None and h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
-        if flags:
-            col = col_k
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
-        ws2b = lib.cb_spmm_gemm_trunkbwd_workspace_bytes() if want_colsum else 0
-        ws2 = torch.empty(max(ws2b, 16), dtype=torch.uint8, device=dev)
-        prof = self.profile
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        with torch.cuda.device(dev):
-            _lib.check(lib.cb_spmm_gemm_trunkbwd_f32(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
-                                                     _lib.ptr(acc_init), acc_init.stride(0) if acc_init is not None else 0, _lib.ptr(out), d,
-                                                     self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr),
-                                                     _lib.ptr(ws), ws_bytes, _lib.ptr(image), _lib.ptr(g_rowscale), _lib.ptr(g), 256, _lib.ptr(bits),
-                                                     float(c_act), float(p), ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(rowscale2),
-                                                     _lib.ptr(gr), 256, _lib.ptr(colsum), _lib.ptr(ws2), ws2b, _lib.stream_ptr()),
-                       'cb_spmm_gemm_trunkbwd_f32')
-        if prof is not None:
-            ev1.record()
-            prof.append(prof_rec(ev0, ev1, self, 'agg_gemm_trunkbwd', self.algorithmic_bytes(d, row_scale=False, bias=False), 0,
-                                 self.N * 256 * 4 * 2 + 4 * self.N + 32 * self.N))
-        return out, g, gr, colsum
 
     def spmm_lp(self, h, row_scale, mix, c_mix, post_scale=None, out=None):
         """out = post_scale * clamp(row_scale * (A h) + c_mix * mix, 0, 1): one label-propagation step with both elementwise passes in the

@@ -148,10 +148,8 @@ def head_tail_enabled(bwd):
     (the metrics and evaluation forwards: two of the three forwards of the reference's epoch) — there the last layer's activations are not
     written at all and the head's 10 GB re-read disappears (reference epoch 318.2 / 315.9 -> 313.3 / 314.5 ms, A/B on one box).  In the training
     forward the activations must be stored anyway and the persistent kernel moves its bytes slower than the plain aggregation kernel it would
-    replace (5.9 against 7.5 TB/s): 160.6 / 160.5 against 159.7 / 160.1 ms per step, so it stays two kernels there.  CB_AGG_GEMM_HEAD=0: never;
-    =2: also in the training forward."""
-    mode = os.environ.get('CB_AGG_GEMM_HEAD', '1')
-    return mode == '2' or (mode == '1' and not bwd)
+    replace (5.9 against 7.5 TB/s): 160.6 / 160.5 against 159.7 / 160.1 ms per step, so it stays two kernels there."""
+    return not bwd
 
 
 def agg_gemm_eligible(graph, hidden, agg_bf16):
@@ -334,15 +332,6 @@ def _input_bwd_multi(g, seed, g_mix, seeds_mix, c_mix, act, p, row0, act_bits=No
     return out, colsum
 
 
-# The trunk backward of the layer below (dropout / mix / ReLU backward, row scale, bias column sums: cb_trunk_layer_bwd_f32's pass over dL/dx)
-# in the epilogue of the reverse aggregation + dX kernel (cb_spmm_gemm_trunkbwd_f32): opt-in, CB_AGG_GEMM_TRUNKBWD=1.  Measured neutral on one
-# GPU (202.0-203.2 vs 201.8-202.2 ms per step on S-pl10M, profiles/r03_fused_agg_gemm.md) and slower as the last halo pass of a sharded
-# aggregation (2.40 vs 1.62 + 0.48 ms at P = 8, profiles/r04_shard_probe_S-pl10M.txt): whatever leaves through the multiplying wavefronts'
-# epilogue is paid at their store rate.  Bias gradients are summed in another order than by the pass: equal to rounding, not bit for bit.
-def tail_trunk_bwd(graph):
-    return os.environ.get('CB_AGG_GEMM_TRUNKBWD', '0') == '1'
-
-
 # Thresholds of the row-sparse backward and the gather mode: tuning.T (rowsparse_*, fwd0_*, mix_max, gather_mem_frac), each documented there with
 # the graph it was tuned on.
 
@@ -382,26 +371,25 @@ def _chunked(graph, agg_bf16):
             and not graph.f.plan.cover and os.environ.get('COLDBREW_CHUNKED_PRODUCERS', '1') != '0')
 
 
-def _gather_and_tail(graph, L, residual, h, x0):
-    """(gather, tail_tb) of a backward: gather mode of the gradients that reach X0 through the mixes; the trunk backward in the dX kernel's epilogue."""
-    gather = residual or (L <= T.mix_max and _gather_fits(L, x0, graph))
-    return gather, agg_gemm_eligible(graph, h, False) and gather and not residual and tail_trunk_bwd(graph)
+def _gather(graph, L, residual, x0):
+    """Gather mode of a backward's gradients that reach X0 through the mixes."""
+    return residual or (L <= T.mix_max and _gather_fits(L, x0, graph))
 
 
 def _support_plan(graph, loss_rows, n_rows, L, residual, h, x0, committed=False):
-    """(plan, gather, tail_tb) of a backward — and of a rows-only forward — under the caller's loss_rows promise: ONE decision for both, so that a
+    """The row-support plan of a backward — and of a rows-only forward — under the caller's loss_rows promise: ONE decision for both, so that a
     forward that evaluated its last layer on the loss rows finds the same plan in its backward.  plan: CSRGraph.grad_support_plan or None (dense).
     committed (the backward of a rows-only forward): the plan's build / hit bookkeeping (support_plan_pays) is not asked again — the forward's own
     build may just have tipped it."""
-    gather, tail_tb = _gather_and_tail(graph, L, residual, h, x0)
+    gather = _gather(graph, L, residual, x0)
     hint = loss_rows if (not hasattr(graph, 'part') and hasattr(graph, 'grad_support_plan') and graph.rowptr_t is not None) else None
     if hint is not None and (not ops.loss_rows_enabled() or hint[0].shape[0] != n_rows):
         hint = None
     if not (hint is not None and 1 <= hint[1] <= T.rowsparse_s0_limit * n_rows
             and (n_rows >= T.rowsparse_min_nodes or getattr(graph, 'rowsparse_small_ok', False)) and gather
-            and agg_gemm_eligible(graph, h, False) and not tail_tb and (committed or graph.support_plan_pays())):
-        return None, gather, tail_tb
-    return hint, gather, tail_tb
+            and agg_gemm_eligible(graph, h, False) and (committed or graph.support_plan_pays())):
+        return None
+    return hint
 
 
 def rows_only_enabled():
@@ -433,14 +421,14 @@ def _rows_only_decision(graph, cfg, x, x0, h, ag, bwd, layer_params):
     if sharded:
         if not (hasattr(graph, 'loss_rows_forward') and ops.loss_rows_enabled() and loss_rows[0].shape[0] == x.shape[0]):
             return none
-        gather, tail_tb = _gather_and_tail(graph, L, residual, h, x0)
-        levels = graph.support_levels(loss_rows[0], L, compact=ag and gather and not tail_tb, cumulative=residual)
+        gather = _gather(graph, L, residual, x0)
+        levels = graph.support_levels(loss_rows[0], L, compact=ag and gather, cumulative=residual)
         if not (levels and levels[0].src is not None):
             return none
         return None, None, (levels[0].src, graph.loss_rows_forward(levels)), False
     if not T.rowsparse_loss_side:
         return none
-    hint = _support_plan(graph, loss_rows, x.shape[0], L, residual, h, x0)[0]
+    hint = _support_plan(graph, loss_rows, x.shape[0], L, residual, h, x0)
     if hint is None:
         return none
     plan = graph.grad_support_plan(hint[0], L, max_frac=T.rowsparse_max_frac, cumulative=residual)
@@ -774,7 +762,6 @@ class _Backward:
         self.grads_layers = [None] * (3 * L)
         self.ag = agg_gemm_eligible(graph, self.h, agg_bf16)
         self.chunked = (self.gather and _chunked(graph, agg_bf16) and graph.b.plan.n_slices > 1 and not self.ag)
-        self.tail_tb = self.ag and self.gather and not residual and tail_trunk_bwd(graph)      # (the accumulate-in-place form needs the pass: it also adds into gx0)
         # Round 6 — the input stage without a pass of its own: the reverse aggregation that writes all rows and applies layer 0's store backward in its epilogue
         # (_layer_source_side) FOLDS every mix gradient known by then into one matrix (cb_spmm_csr_store_bwd_mix_f32: it holds layer 0's in registers, the
         # compact ones of the layers above are gathered per row) and takes layer 0's bias gradient; the input Linear's weight gradient then computes
@@ -912,19 +899,11 @@ class _Backward:
             fwd_j.profile = level[0].profile
         t = gemm.mm_nn(gr, w.t().contiguous())
         self._fused_store_bwd = None
-        # 0: never; 1 (default): levels that write all rows; 2: compact levels too (measured equal on S-pl10M: 119.2 - 119.4 ms per step either way)
-        mode = os.environ.get('CB_SPMM_STORE_BWD', '1')
-        if (l > 0 and not self.residual and self.gather and len(getattr(self, '_cs', [])) < 2 and (mode == '2' or (mode == '1' and dst is None))
+        if (l > 0 and not self.residual and self.gather and len(getattr(self, '_cs', [])) < 2 and dst is None
                 and hasattr(level[0], 'spmm_store_bwd') and t.shape[1] % 256 == 0):
-            # the store backward of the layer below (its dropout / mix / ReLU backward and row factor) leaves this reverse aggregation's own epilogue —
-            # the separate pass's read of g disappears; its bias gradient is taken by the input stage, which reads g anyway.  A compact destination:
-            # mask words, row factor and dropout mask at the node rows dst.idx
-            ids = None
-            if dst is not None:
-                ids = getattr(dst, '_ids32', None)
-                if ids is None:
-                    ids = dst._ids32 = dst.idx.to(torch.int32).contiguous()
-            fold = (self.fold_ok and l == 1 and dst is None and len(self.g_mix) <= 2 and all(q is not None for q in self.mix_pos)
+            # a level that writes all rows: the store backward of the layer below (its dropout / mix / ReLU backward and row factor) leaves this
+            # reverse aggregation's own epilogue — the separate pass's read of g disappears; its bias gradient is taken by the input stage, which reads g anyway
+            fold = (self.fold_ok and l == 1 and len(self.g_mix) <= 2 and all(q is not None for q in self.mix_pos)
                     and not getattr(self, '_cs', []))
             if fold:      # (g_mix holds the mix gradients of the layers above, compact on their supports; layer 0's own is this aggregation's sum)
                 self.mfold, gr_below, db0 = level[0].spmm_store_bwd(t, self.a, self.saved_bits[0], self.bnorm, 1 - self.alpha, self.p, self.seed(2), self.row0,
@@ -933,8 +912,7 @@ class _Backward:
                 self.g_mix, self.mix_pos, self.seeds_mix = [], [], []      # folded: the input stage reads self.mfold instead
                 g_new = None
             else:
-                g_new, gr_below = level[0].spmm_store_bwd(t, dst.a if dst is not None else self.a, self.saved_bits[l - 1], self.bnorm, 1 - self.alpha, self.p,
-                                                          self.seed(l + 1), self.row0, row_ids=ids)
+                g_new, gr_below = level[0].spmm_store_bwd(t, self.a, self.saved_bits[l - 1], self.bnorm, 1 - self.alpha, self.p, self.seed(l + 1), self.row0)
             self._fused_store_bwd = (gr_below, l - 1)
         else:
             g_new = level[0].spmm(t, row_scale=dst.a if dst is not None else self.a)
@@ -963,31 +941,19 @@ class _Backward:
         return gz, g_new
 
     def _layer_fused(self, l, gr, handle, dst=None):
-        """dL/dZ_l = A (b * dY') and a * (dL/dZ_l @ W_l^T) from one kernel (cb_spmm_gemm_f32) on all rows; for l > 0 and tail_tb the trunk backward
-        of layer l-1's store leaves the same epilogue (cb_spmm_gemm_trunkbwd_f32).  Node-sharded: the kernel is the LAST halo pass of the reverse
-        aggregation, on top of the running sums of the earlier passes; dst (a compact level of the rank, dist.SupportLevel): its rows are the
-        positions of the level's destination support.  Returns (gz, g_new, (gr_next, dbias_next) | None)."""
+        """dL/dZ_l = A (b * dY') and a * (dL/dZ_l @ W_l^T) from one kernel (cb_spmm_gemm_f32) on all rows.  Node-sharded: the kernel is the LAST
+        halo pass of the reverse aggregation, on top of the running sums of the earlier passes; dst (a compact level of the rank, dist.SupportLevel):
+        its rows are the positions of the level's destination support.  Returns (gz, g_new)."""
         from .graph import weight_image
         graph = self.graph
         a = dst.a if dst is not None else self.a
-        w = self.lp[l][0]
-        img = weight_image(w, transpose=True)
-        use_tb = l > 0 and self.tail_tb
-        sd_b = self.seed(l + 1)
+        img = weight_image(self.lp[l][0], transpose=True)
 
         def tail(csr, src, acc, tr):
             csr.profile = getattr(graph, 'profile', None)
-            if use_tb:
-                return csr.spmm_gemm_trunkbwd(src, img, a, self.saved_bits[l - 1], 1 - self.alpha, self.p, sd_b, self.row0, self.bnorm, self.need_b(l - 1),
-                                              transpose=tr, acc_init=acc)
             return csr.spmm_gemm(src, img, transpose=tr, g_rowscale=a, acc_init=acc)
-        res = (graph.aggregate_finish(handle, True, last_pass=lambda csr, recv, acc: tail(csr, recv, acc, False)) if self.sharded
-               else tail(graph, gr, None, True))
-        if use_tb:
-            gz, g_new, gr_n, db_n = res
-            return gz, g_new, (gr_n, db_n)
-        gz, g_new = res
-        return gz, g_new, None
+        return (graph.aggregate_finish(handle, True, last_pass=lambda csr, recv, acc: tail(csr, recv, acc, False)) if self.sharded
+                else tail(graph, gr, None, True))
 
     def _layer_plain(self, gr, handle):
         """dL/dZ_l = A (b * dY') by the plain aggregation (the dX GEMM is a kernel of its own)."""
@@ -1008,7 +974,7 @@ class _Backward:
         if sharded and hasattr(graph, 'support_levels') and self.loss_rows is not None:
             ops.check_rows_zero(gout, self.loss_rows[0])
             # ('Residual': CUMULATIVE supports, as on one GPU below)
-            self.sh_levels = graph.support_levels(self.loss_rows[0], L, compact=self.ag and gather and not self.tail_tb, cumulative=self.residual)
+            self.sh_levels = graph.support_levels(self.loss_rows[0], L, compact=self.ag and gather, cumulative=self.residual)
         # Row-sparse backward (one GPU): when the caller promised that only the loss rows of gout carry gradient, what the backward makes of it
         # stays zero outside the rows those can reach: after the j-th reverse aggregation only the rows with a neighbour in the previous support
         # carry gradient (CSRGraph.grad_support_plan: S_0 = loss rows, S_1, ... — 10 % / 45 % / 94 % of the rows on the bench's graph with its
@@ -1017,7 +983,7 @@ class _Backward:
         # (ops.check_rows_zero: a violation ends in the device error word and stops the optimiser launch, never in silent wrong gradients).
         # Hidden 256, gathered per-layer gradients, loss rows <= rowsparse_s0_limit of the nodes.
         plan = None
-        hint = None if sharded else _support_plan(graph, self.loss_rows, self.n_rows, L, self.residual, self.h, self.x0, committed=self.xl_compact)[0]
+        hint = None if sharded else _support_plan(graph, self.loss_rows, self.n_rows, L, self.residual, self.h, self.x0, committed=self.xl_compact)
         # (with bf16-stored rows the compact levels still run on fp32 matrices through the aggregation + GEMM kernel; the dense levels below
         # them go on as the bf16 path does)
         if hint is not None:
@@ -1053,7 +1019,6 @@ class _Backward:
             if deferred is not None:
                 self.grads_layers[3 * deferred[0]] = self._dw_rows(*deferred)
                 deferred = None
-            tb_next = None
             fwd_j = plan.fwd[j] if (level is not None and j < len(plan.fwd)) else None
             source_side = (self.rows_only and l == L - 1) or (self.h_below is not None and l == L - 2) or (T.rowsparse_loss_side and fwd_j is not None and not self.need_le(l)
                                                               and not (self.need_w(l) and self.saved_in[l] is None)      # (layer 0 without a stored dropped copy of X0)
@@ -1063,7 +1028,7 @@ class _Backward:
             elif level is not None:
                 gz, g_new = self._layer_compact(l, gr, level)
             elif self.ag:
-                gz, g_new, tb_next = self._layer_fused(l, gr, handle, dst)
+                gz, g_new = self._layer_fused(l, gr, handle, dst)
                 if self.need_w(l):
                     if sharded:
                         deferred = (l, self.saved_in[l], gz, dst)
@@ -1094,8 +1059,6 @@ class _Backward:
                 gr, dbias = _layer_bwd_rows(g, dst.idx, self.saved_bits[l - 1], self.bnorm, p, self.seed(l + 1), self.row0, 1 - alpha, self.need_b(l - 1),
                                             out=_exchanged(graph, g.shape[0], g.shape[1]) if sharded else None,
                                             **self._second(l - 1, g_above, pos_above))
-            elif l > 0 and tb_next is not None:
-                g, (gr, dbias) = g_new, tb_next
             elif l > 0:      # dL/d(dropped X_l) and the backward of layer l-1's store
                 g, gr, dbias, handle = self._dx_and_store_bwd(gz, w.t().contiguous(), a, l - 1, g_new, g_above, orient=self._orient_of(l - 1),
                                                               pos_above=pos_above)

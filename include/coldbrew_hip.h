@@ -333,13 +333,12 @@ int cb_trunk_input_bwd_multi_cs_f32(const float* g, uint64_t seed, int32_t n_mix
  *   g = row_scale * sum_{u in row v} h[u]              -> out_g (may be NULL): dL/d(stored, dropped activation), the input stage's mix operand
  *   out_gr = bwd_rowscale[v] * c_act * dropout_bwd_seed(g) where relu_bits (READ: the forward store's mask words) has the element's bit, else 0
  * = cb_spmm_csr_f32 followed by cb_trunk_layer_bwd_f32 (gx0 = NULL, no second gradient) without that pass's read of g; values bit-identical.  The
- * pass's column sums (the bias gradient) come from cb_trunk_input_bwd_multi_cs_f32.  d % 256 == 0, fp32 rows, 16-byte aligned.  row_ids (may be NULL): the
- * CSR's rows are a subset of the node rows (row r = node row_ids[r]): relu_bits, the dropout mask and bwd_rowscale are taken at the node row. */
+ * pass's column sums (the bias gradient) come from cb_trunk_input_bwd_multi_cs_f32.  d % 256 == 0, fp32 rows, 16-byte aligned. */
 int cb_spmm_csr_store_bwd_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
                               int64_t d, const float* row_scale, const uint64_t* relu_bits, const float* bwd_rowscale, float c_act, float drop_p,
                               uint64_t seed, const uint64_t* seed_dev, int64_t row0, float* out_g, int64_t ld_g, float* out_gr, int64_t ld_gr,
                               int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                              size_t ws_bytes, const int32_t* row_ids, void* stream);
+                              size_t ws_bytes, void* stream);
 /* The same on ALL node rows, with the mix gradients FOLDED (round 6): the first output is not the raw g but everything this store and the layers above
  * send to X0 through their residual mixes (InitialConnection, res_tricks.py:19-23: X = (1 - alpha) X_l + alpha X_0, each under its own store's dropout
  * GCN.py:110,133):
@@ -636,20 +635,6 @@ int cb_spmm_gemm_store_rows_f32(const int32_t* rowptr, const int32_t* col, int32
                                 const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev,
                                 int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* g_out,
                                 int64_t ld_gout, void* stream);
-
-/* cb_spmm_gemm_f32 (reverse aggregation + dX contraction) + the trunk backward of the layer below from the same epilogue: g_out is
- * dL/dx of the stage above layer l-1; gr_out = c_act * dropout_bwd_{seed}(g_out) * relu_bits * rowscale2 (input of the next reverse
- * aggregation) and colsum = the column sums of the same without rowscale2 (bias gradient of layer l-1) — what cb_trunk_layer_bwd_f32
- * computes in a pass of its own (autograd of GCN.py:127-133,250-253), without its 10 GB read of g_out.  relu_bits: the mask words
- * cb_spmm_csr_fused_f32 wrote for layer l-1 ([N][4], d = 256).  ws2: cb_spmm_gemm_trunkbwd_workspace_bytes() (partial column sums).
- * acc_init: as for cb_spmm_gemm_f32 (node-sharded: the last halo pass of the reverse aggregation). */
-size_t cb_spmm_gemm_trunkbwd_workspace_bytes(void);
-int cb_spmm_gemm_trunkbwd_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                              int64_t d, const float* acc_init, int64_t ld_init, float* out, int64_t ld_out, int32_t hub_threshold,
-                              int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes,
-                              const void* image, const float* g_rowscale, float* g_out, int64_t ld_gout, const uint64_t* relu_bits, float c_act,
-                              float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, const float* rowscale2, float* gr_out,
-                              int64_t ld_gr, float* colsum, void* ws2, size_t ws2_bytes, void* stream);
 
 /* One label-propagation step, elementwise passes folded into the aggregation's store (Label_propagation_model/outcome_correlation.py:137-143
  * with alpha_term and post_step = clamp(0, 1), as trainer_node_classification.py:33-63 drives it):

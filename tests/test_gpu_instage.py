@@ -138,7 +138,6 @@ def test_training_step_with_the_folded_input_stage(n_loss_rows, sum_first, monke
     # else (S-pl1M's own form: it sits below the break-even of the sum-first layer) the store backward is a pass, which folds (cb_trunk_layer_bwd_fold_f32)
     if sum_first:
         monkeypatch.setattr(tuning.T, 'sum_first_below_min_edges', 0)
-    monkeypatch.setenv('CB_SPMM_STORE_BWD', '1')
     calls = []
     real = gemm.mm_tn_instage
     monkeypatch.setattr(gemm, 'mm_tn_instage', lambda *a, **k: (calls.append(1), real(*a, **k))[1])

@@ -8,7 +8,7 @@ Two pipelines are probed side by side (--mode both):
          pass, per-slice halo passes (cb_spmm_csr_acc_f32), the last one with the epilogue; the layer GEMM is a kernel of its own.
   cover  this round's default: push / pull vertex cover per rank pair (dist.choose_cover; pack = aggregation over the send CSR),
          positional slices, and the LAST halo pass is the aggregation + GEMM kernel on top of the running sums (cb_spmm_gemm_f32 /
-         cb_spmm_gemm_fused_f32 / cb_spmm_gemm_trunkbwd_f32 with acc_init) — the next stage's matrix exists when that kernel ends.
+         cb_spmm_gemm_fused_f32 with acc_init) — the next stage's matrix exists when that kernel ends.
 
     python tools/shard_probe.py [--name S-pl10M] [--worlds 1,2,4,8] [--rank 0] [--slices 4] [--link-gbs 153] [--link-eff 0.8]
                                 [--n1-ms <the driver's 1-GPU ms/step>] [--mode both|pull|cover] [--halo-only 1]
@@ -350,8 +350,6 @@ def main():
                     'fused_store_gemm': timed(lambda: trunk._fused_gemm_launch(gl, halos[K - 1], bias, x0, 0.9, 0.1, 0.1, 7, img, scale, None, g=gl,
                                                                                 acc=acc.clone())),
                     'reverse_gemm': timed(lambda: gl.spmm_gemm(halos[K - 1], img_t, g_rowscale=scale, acc_init=acc.clone())),
-                    'reverse_gemm_trunkbwd': timed(lambda: gl.spmm_gemm_trunkbwd(halos[K - 1], img_t, scale, bits, 0.9, 0.1, 7, 0, scale, True,
-                                                                                  transpose=False, acc_init=acc.clone())),
                     'clone_only': timed(lambda: acc.clone()),
                 }
                 t_link = [link_rows[k] * bpr / link for k in range(K)]
@@ -360,8 +358,7 @@ def main():
                 def exposed(last_ms):
                     return pipeline(zero, t_pack, t_link, t_int_cover, t_pass + [last_ms - last['clone_only']])
                 # forward: layers 0 .. L-2 store + next GEMM, layer L-1 store only; backward: every layer the dX tail; the trunk backward of the
-                # layer below stays a pass of its own (its time is part of --dense-cover-ms; in the tail's epilogue it measures slower:
-                # 'reverse_gemm_trunkbwd' against 'reverse_gemm' + t_trunk_bwd)
+                # layer below is a pass of its own (its time is part of --dense-cover-ms)
                 gb = torch.rand(n_local, d, device=dev)
                 t_tb = timed(lambda: trunk._layer_bwd(gb, bits, scale, None, False, 0.1, 7, 0, 0.9, 0.1, True))
                 last['trunk_bwd_pass'] = t_tb
