@@ -164,6 +164,12 @@ SIGNATURES = {
     'cb_symmetrize_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_symmetrize_i64': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     'cb_trunk_input_bwd_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _P, _SZ, _P]),
+    'cb_ln_gelu_drop_fwd_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _P, _P, _P]),
+    'cb_ln_gelu_drop_bwd_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_ln_gelu_drop_bwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _P, ctypes.c_float, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    'cb_mse_rows_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
+    'cb_part2_assemble_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
+    'cb_part2_assemble_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _P, _P, _SZ, _P]),
 }
 
 _lib = None

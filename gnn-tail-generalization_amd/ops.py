@@ -8,6 +8,10 @@ Stage map (reference lines are GNN_model/GCN.py unless noted):
   aggregate   Y  = act(b * (A^T Z) + bias)           :238,:250,:253(+:128)  (sparse, HBM-bound)
   res_mix     X' = (1-alpha) * Y + alpha * R         res_tricks.py:14,23
   nll_logsoftmax  mean nll(log_softmax(out[mask]))   trainer_node_classification.py:390-391
+Student MLPs (reference lines are MLP_model/__init__.py / utils.py / the trainer):
+  ln_gelu_dropout   dropout(gelu(layer_norm(z)))     utils.py:898-903 (one row kernel per getMLP group; linear_ln_gelu_dropout: + its Linear)
+  mse_rows          mse(pred, target[row_index])     trainer_node_classification.py:96,108
+  semlp_part2_input [x | a1 * replaced | a0 * guess] MLP_model/__init__.py:102-108
 """
 import ctypes
 import os
@@ -524,3 +528,197 @@ def se_topk_replace(le_guess, teacher_se, k, return_selection=False):
                                            int(k), _lib.ptr(out), _lib.ptr(idx), _lib.ptr(wgt), _lib.ptr(ws), wsb, _lib.stream_ptr()),
                    'cb_topk_replace_f32')
     return (out, idx, wgt) if return_selection else out
+
+
+# ---------------------------------------------------------------------------------------------
+# student MLPs (MLP_model/__init__.py): the [LayerNorm, GELU, Dropout] row stage, the part-1 loss, the part-2 input
+# ---------------------------------------------------------------------------------------------
+def _ln_gelu_drop_fwd_raw(z, gamma, beta, eps, p, seed, want_stats):
+    lib = _lib.load()
+    rows, d = z.shape
+    out = torch.empty_like(z)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=z.device) if want_stats else None
+    with torch.cuda.device(z.device):
+        _lib.check(lib.cb_ln_gelu_drop_fwd_f32(_lib.ptr(z), rows, d, _lib.ptr(gamma), _lib.ptr(beta), float(eps), float(p), ctypes.c_uint64(seed),
+                                               seed_dev_ptr(), _lib.ptr(out), _lib.ptr(stats), _lib.stream_ptr()), 'cb_ln_gelu_drop_fwd_f32')
+    return out, stats
+
+
+def _ln_gelu_drop_bwd_raw(dy, z, stats, gamma, beta, p, seed, want_dbias=False):
+    """(dz, dgamma, dbeta, colsum(dz) or None) — one pass + the fixed-order finish of the column sums."""
+    lib = _lib.load()
+    rows, d = z.shape
+    dy = _c(dy)
+    dz = torch.empty_like(z)
+    dgamma = torch.empty(d, dtype=torch.float32, device=z.device)
+    dbeta = torch.empty(d, dtype=torch.float32, device=z.device)
+    dbias = torch.empty(d, dtype=torch.float32, device=z.device) if want_dbias else None
+    wsb = lib.cb_ln_gelu_drop_bwd_workspace_bytes(rows, d)
+    ws = _ws(wsb, z.device)
+    with torch.cuda.device(z.device):
+        _lib.check(lib.cb_ln_gelu_drop_bwd_f32(_lib.ptr(dy), _lib.ptr(z), _lib.ptr(stats), rows, d, _lib.ptr(gamma), _lib.ptr(beta), float(p),
+                                               ctypes.c_uint64(seed), seed_dev_ptr(), _lib.ptr(dz), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dbias),
+                                               _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_ln_gelu_drop_bwd_f32')
+    return dz, dgamma, dbeta, dbias
+
+
+def _ln_args(d, gamma, beta, p, training, seed):
+    _lib.require_device(gamma, beta)
+    if gamma.shape != (d,) or beta.shape != (d,) or gamma.dtype != torch.float32 or beta.dtype != torch.float32:
+        raise ValueError(f'ln_gelu_dropout expects float32 [{d}] LayerNorm parameters')
+    p = float(p) if training else 0.0
+    if p >= 1.0:
+        raise ValueError('ln_gelu_dropout: p must be < 1')
+    if p > 0.0 and seed is None:
+        seed = next_seed()
+    return p, int(seed or 0)
+
+
+class _LnGeluDropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, gamma, beta, eps, p, seed):
+        z, gamma, beta = _c(z), _c(gamma), _c(beta)
+        need = any(ctx.needs_input_grad[:3])
+        out, stats = _ln_gelu_drop_fwd_raw(z, gamma, beta, eps, p, seed, need)
+        ctx.p, ctx.seed = p, seed
+        if need:
+            ctx.save_for_backward(z, stats, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        z, stats, gamma, beta = ctx.saved_tensors
+        dz, dgamma, dbeta, _ = _ln_gelu_drop_bwd_raw(g, z, stats, gamma, beta, ctx.p, ctx.seed)
+        return dz, dgamma, dbeta, None, None, None
+
+
+def ln_gelu_dropout(z, gamma, beta, eps=1e-5, p=0.0, training=True, seed=None):
+    """dropout(gelu(layer_norm(z))) — `nn.LayerNorm(d), nn.GELU(), nn.Dropout(p)` of a getMLP group (utils.py:898-903) in one pass over z
+    (cb_ln_gelu_drop_fwd_f32); the backward recomputes the normalised row and the keep mask from z, 8 bytes of row statistics and the seed
+    (cb_ln_gelu_drop_bwd_f32).  The mask is ops.dropout_keep_mask(z.shape, p, seed, device)."""
+    _lib.require_device(z)
+    if z.dim() != 2 or z.dtype != torch.float32:
+        raise ValueError('ln_gelu_dropout expects a float32 [rows, d] matrix')
+    p, seed = _ln_args(z.shape[1], gamma, beta, p, training, seed)
+    return _LnGeluDropFn.apply(z, gamma, beta, float(eps), p, seed)
+
+
+class _LinearLnGeluDropFn(torch.autograd.Function):
+    """One [Linear, LayerNorm, GELU, Dropout] group: GEMM (bias in its epilogue) + the row kernel; the backward's row kernel also leaves
+    colsum(dz) = the Linear's bias gradient, then the two backward contractions of gemm.linear."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, eps, p, seed):
+        from . import gemm
+        z = gemm.mm_nn(x, weight.t().contiguous(), bias=bias)
+        gamma, beta = _c(gamma), _c(beta)
+        need = any(ctx.needs_input_grad[:5])
+        out, stats = _ln_gelu_drop_fwd_raw(z, gamma, beta, eps, p, seed, need)
+        ctx.p, ctx.seed, ctx.has_bias = p, seed, bias is not None
+        if need:
+            ctx.save_for_backward(x, weight, z, stats, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import gemm
+        x, weight, z, stats, gamma, beta = ctx.saved_tensors
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        dz, dgamma, dbeta, dbias = _ln_gelu_drop_bwd_raw(g, z, stats, gamma, beta, ctx.p, ctx.seed, want_dbias=need_b)
+        dx = gemm.mm_nn(dz, weight) if ctx.needs_input_grad[0] else None
+        dw = gemm.mm_tn(dz, x) if ctx.needs_input_grad[1] else None
+        return dx, dw, dbias, dgamma, dbeta, None, None, None
+
+
+def linear_ln_gelu_dropout(x, weight, bias, gamma, beta, eps=1e-5, p=0.0, training=True, seed=None):
+    """ln_gelu_dropout(x @ weight.T + bias, ...) as one autograd node (see _LinearLnGeluDropFn)."""
+    _lib.require_device(x, weight, bias)
+    if x.dim() != 2 or x.dtype != torch.float32 or weight.shape[1] != x.shape[1]:
+        raise ValueError('linear_ln_gelu_dropout expects a float32 [rows, in] matrix and an [out, in] weight')
+    p, seed = _ln_args(weight.shape[0], gamma, beta, p, training, seed)
+    return _LinearLnGeluDropFn.apply(x, weight, bias, gamma, beta, float(eps), p, seed)
+
+
+class _MseRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, row_index):
+        lib = _lib.load()
+        pred = _c(pred)
+        B, D = pred.shape
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        grad = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        wsb = lib.cb_reduce_workspace_bytes()
+        ws = _ws(wsb, pred.device)
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.cb_mse_rows_f32(_lib.ptr(pred), B, D, _lib.ptr(target), target.stride(0) if target.shape[0] > 1 else D, target.shape[0],
+                                           _lib.ptr(row_index), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_mse_rows_f32')
+        ctx.save_for_backward(grad)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def mse_rows(pred, target, row_index=None):
+    """nn.MSELoss()(pred, target[row_index]) (trainer_node_classification.py:96,108) without the gathered copy; the gradient
+    2 (pred - target[row_index]) / numel is written by the same pass.  target is not differentiated (the reference's targets are detached)."""
+    _lib.require_device(pred, target, row_index)
+    if pred.dim() != 2 or target.dim() != 2 or pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.shape[1] != target.shape[1]:
+        raise ValueError('mse_rows expects float32 [B, D] predictions and [N, D] targets')
+    if target.stride(1) != 1:
+        target = target.contiguous()
+    if row_index is not None:
+        if row_index.dtype != torch.int64 or row_index.numel() != pred.shape[0]:
+            raise ValueError('mse_rows: row_index must be an int64 vector with one entry per prediction row')
+        row_index = _c(row_index)
+    elif target.shape[0] != pred.shape[0]:
+        raise ValueError('mse_rows: without row_index the targets need one row per prediction row')
+    return _MseRowsFn.apply(pred, target.detach(), row_index)
+
+
+def _part2_assemble_raw(out, x, replaced, part1_out, alphas, F, D):
+    lib = _lib.load()
+    with torch.cuda.device(out.device):
+        _lib.check(lib.cb_part2_assemble_f32(_lib.ptr(x), F, _lib.ptr(replaced), _lib.ptr(part1_out), D, _lib.ptr(alphas), out.shape[0], _lib.ptr(out),
+                                             _lib.stream_ptr()), 'cb_part2_assemble_f32')
+
+
+class _Part2InputFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, alphas, x, part1_out, teacher_se, k):
+        B, F = x.shape
+        D = part1_out.shape[1]
+        a = _c(alphas.detach())
+        out = torch.empty((B, F + 2 * D), dtype=torch.float32, device=x.device)
+        _part2_assemble_raw(out, x, None, part1_out, a, F, D)               # x and alphas[0] * part1_out
+        replaced = se_topk_replace(out[:, F + D:], teacher_se, k)           # replacement() reads the scaled guess (:103-104)
+        _part2_assemble_raw(out, None, replaced, None, a, F, D)             # alphas[1] * replaced
+        ctx.F, ctx.D = F, D
+        ctx.save_for_backward(replaced, part1_out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        replaced, part1_out = ctx.saved_tensors
+        g = _c(g)
+        dal = torch.empty(2, dtype=torch.float32, device=g.device)
+        wsb = 2 * lib.cb_reduce_workspace_bytes()
+        ws = _ws(wsb, g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(lib.cb_part2_assemble_bwd_f32(_lib.ptr(g), ctx.F, _lib.ptr(replaced), _lib.ptr(part1_out), ctx.D, g.shape[0], _lib.ptr(dal),
+                                                     _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_part2_assemble_bwd_f32')
+        return dal, None, None, None, None
+
+
+def semlp_part2_input(alphas, x, part1_out, teacher_se, k):
+    """torch.cat([x, replacement(alphas[0] * part1_out) * alphas[1], alphas[0] * part1_out], -1) (MLP_model/__init__.py:102-108) written
+    into one [B, F + 2 D] matrix: the scaled guess goes straight into its block, the top-K kernel reads its queries from there, the scaled
+    virtual neighbours fill the middle.  Gradient reaches `alphas` only (x, part1_out and the replacement are detached in the reference;
+    the path of alphas[0] through the replacement is cut by its detach())."""
+    _lib.require_device(alphas, x, part1_out, teacher_se)
+    if x.dim() != 2 or part1_out.dim() != 2 or x.shape[0] != part1_out.shape[0] or alphas.shape != (2,):
+        raise ValueError('semlp_part2_input expects x [B, F], part1_out [B, D] and the two alphas')
+    return _Part2InputFn.apply(alphas, _c(x.detach().float()), _c(part1_out.detach().float()), teacher_se, int(k))

@@ -1,11 +1,11 @@
-"""Training harness of the TeacherGNN path — drop-in for the TeacherGNN part of the reference's
-trainer_node_classification.py (trainer.__init__ :252-301, train_teacherGNN :303-369,
-run_trainSet :382-432, run_testSet :453-495, evaluate :672-681, cal_acc_rounded100 :683-687).
+"""Training harness — drop-in for the reference's trainer_node_classification.py (trainer.__init__ :252-301, main :10-31,
+train_teacherGNN :303-369, run_trainSet :382-432, run_testSet :453-495, train_seMLP_part1 :66-127, train_seMLP_part2 :129-210,
+eval_headtail__traintest_v2 :226-236, evaluate :672-681, cal_acc_rounded100 :683-687).
 
-Same class/method names, same per-epoch record layout and return shapes; the forward/backward
-runs on the HIP path.  --train_which=LP (pure label propagation) and the TEACHER side of --train_which=SEMLP (train -> best
-checkpoint -> collect_SE -> top-K replacement hand-off) are built on the same kernels; the student MLP trainers (StudentBaseMLP,
-GraphMLP, the student half of SEMLP) are outside this path.
+Same class/method names, same per-epoch record layout and return shapes; the forward/backward runs on the HIP path.
+--train_which=TeacherGNN, LP (pure label propagation), SEMLP (teacher -> best checkpoint -> collect_SE -> part 1: regression of the
+student onto the teacher's structural embeddings -> part 2: classification on [x | virtual neighbours | guess]) and StudentBaseMLP (the
+residual MLP on the features alone) are built; GraphMLP is not (MLP_model/__init__.py says why).
 """
 import contextlib
 import os
@@ -14,10 +14,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from . import optim as cb_optim
 from .data import load_data
 from .GNN_model.GNN_normalizations import TeacherGNN
+from .MLP_model import SEMLP
 from .utils import (getMLP, join, load_model, save_graph_analyze, save_model, set_arch_configs, toitem)
 
 
@@ -45,24 +46,34 @@ class trainer:
             return self.train_teacherGNN()
         if self.args.train_which in ['LP']:
             return self.run_pureLP()
+        if self.args.train_which in ['StudentBaseMLP']:
+            self.args.SEMLP__downgrade_to_MLP = 1
+            return self.train_seMLP_part2()
         if self.args.train_which in ['SEMLP']:
-            return self.train_seMLP_part1()
-        raise NotImplementedError(f'--train_which={self.args.train_which}: only the TeacherGNN path is built '
-                                  'and the pure label-propagation baseline (--train_which=LP) are built; the student MLP '
-                                  'trainers are out of scope (SURVEY.md §8f)')
+            if not self.args.SEMLP__downgrade_to_MLP:
+                self.train_seMLP_part1()
+            return self.train_seMLP_part2()
+        raise NotImplementedError(f'--train_which={self.args.train_which}: TeacherGNN, LP, SEMLP and StudentBaseMLP are built; GraphMLP needs a '
+                                  'sparse adjacency power and an N_b x N_b neighbour-contrastive loss that have no kernel here')
+
+    def _new_student(self, teacher):
+        self.seMLP = SEMLP(self.args, self.data, teacher).to(self.device)
+        # the batches are drawn on the host (np.random.choice over CPU index arrays, :76-78)
+        self.seMLP.train_idx = self.seMLP.train_idx.to('cpu')
+        self.seMLP.train_mask = self.seMLP.train_mask.to('cpu')
+        self.seMLP.test_idx = self.seMLP.test_idx.to('cpu')
 
     def train_seMLP_part1(self):
-        """TEACHER SIDE of the reference's train_seMLP_part1 (:66-87) — everything up to the point where the student MLP takes over:
+        """The reference's train_seMLP_part1 (:66-127).  Teacher side:
             train_teacherGNN()                       (:71; with 'SEMLP' in train_which the best-test-accuracy weights are saved, :331-334)
             load_teacherGNN('best checkpoint')       (:72)
             teacherSE = collect_SE(x, edge_index)    (:87, GCN.py:148-150: per-layer pre-activation outputs, [N, sum d_l]; TRAIN mode,
                                                       as in the reference: the freshly built module is never put into eval mode)
-        and the hand-off the student consumes: `self.teacherSE`, written to <modeldir>/teacherSE.pt, and `self.replacement(le_guess)`
-        = SEMLP.replacement (MLP_model/__init__.py:143-156) on the fused scores + top-K + softmax-combine kernel.  The student MLP
-        trainers themselves (part-1 regression onto teacherSE, part 2) are outside this path; returns the teacher's
-        record rows, as train_teacherGNN does."""
+        left behind as `self.teacherSE`, <modeldir>/teacherSE.pt and `self.replacement(le_guess)`.  Student side (:74-127): per epoch one
+        training batch (MSE of forward_part1(x, batch) against teacherSE[batch], one optimiser step) and one eval-mode test batch; records
+        [log loss_train, log loss_test]; the weights go to <modeldir>/seMLP-part-1.  Returns the test-loss row [1, epochs]."""
         print('-' * 30, '\n         Training TeacherGNN before train SEMLP\n', '-' * 30)
-        rows = self.train_teacherGNN()
+        self.train_teacherGNN()
         self.load_teacherGNN('best checkpoint')
         # The reference never calls eval() here: load_teacherGNN builds a NEW module (train mode), so the targets are drawn with the
         # dropout of GCN.py:104,110,133 ACTIVE (:87).  Same mode here (ADVICE r03); the masks come from the product's counter-based
@@ -74,8 +85,96 @@ class trainer:
         self.topK_2_replace = int(self.args.SEMLP_topK_2_replace)
         path = join(self.modeldir, 'teacherSE.pt')
         torch.save({'teacherSE': self.teacherSE.cpu(), 'topK_2_replace': self.topK_2_replace}, path)
-        print(f'teacher -> student hand-off: teacherSE {tuple(self.teacherSE.shape)} @ {path}; the student MLP trainers are not part of this path')
-        return rows
+        print(f'teacher -> student hand-off: teacherSE {tuple(self.teacherSE.shape)} @ {path}')
+
+        print('-' * 30, '\n         Start training part-1 of SEMLP\n', '-' * 30)
+        self._new_student(self.teacherGNN)
+        self.optimizer = None
+        self.seMLP.optfun = self.optfun
+        self.seMLP.teacherSE = lrn_targ = self.teacherSE.float().contiguous()
+        results_arr2D = []
+        for epoch in range(self.epochs):
+            self.seMLP.train()
+            batch_idx_train = np.random.choice(self.seMLP.train_idx, self.args.batch_size)
+            part1_out = self.seMLP.forward_part1(self.data.x, batch_idx=batch_idx_train)
+            if self.optimizer is None:
+                self.optimizer = self.seMLP.opt
+            loss_train = ops.mse_rows(part1_out, lrn_targ, self.seMLP.index_on_device(batch_idx_train, part1_out.device))
+            self.optimizer.zero_grad()
+            loss_train.backward()
+            self.optimizer.step()
+
+            self.seMLP.eval()
+            batch_idx_train = np.random.choice(self.seMLP.test_idx, self.args.batch_size)
+            with torch.no_grad():
+                part1_out = self.seMLP.forward_part1(self.data.x, batch_idx=batch_idx_train)
+                loss_test = ops.mse_rows(part1_out, lrn_targ, self.seMLP.index_on_device(batch_idx_train, part1_out.device))
+            results_arr2D.append([np.log(toitem(loss_train)), np.log(toitem(loss_test))])
+            if epoch % 20 == 0:
+                print(f'epoch {epoch}, train/test loss {toitem(loss_train):.2}, {toitem(loss_test):.2}')
+        _lib.device_status()
+        save_model(self.seMLP, join(self.modeldir, 'seMLP-part-1'))
+        results_arr2D = np.array(results_arr2D).T
+        npy_dir = f'{self.resdir}/seMLP'
+        wzRec(results_arr2D[0], f'loss_train@{npy_dir.replace("/", "@")}', want_save_npy=1, npy_dir=npy_dir)
+        wzRec(results_arr2D[1], f'loss_test@{npy_dir.replace("/", "@")}', want_save_npy=1, npy_dir=npy_dir)
+        return results_arr2D[[1]]      # [1, epochs]
+
+    def train_seMLP_part2(self):
+        """The reference's train_seMLP_part2 (:129-210): the student's classifier on [x | alpha1 * virtual neighbours | alpha0 * guess] (on x
+        alone when downgraded: --SEMLP_topK_2_replace=-99 or --train_which=StudentBaseMLP, which also makes part 2 a BlockResMLP).  Per epoch
+        one training batch (nn.CrossEntropyLoss = mean NLL of log_softmax over the batch rows, one optimiser step; part 1 is detached, so
+        only part2 and the two alphas move), one eval-mode test batch and — with --want_headtail — the head / tail (/ isolated) node sets.
+        Records [acc_test, test_head, test_tail(, test_iso)]; returns rows [[0]] or [[0, -3, -2, -1]]; weights -> <modeldir>/seMLP."""
+        if self.args.SEMLP__downgrade_to_MLP:
+            self._new_student(None)
+        print('-' * 30, '\n         Start training part2 of SEMLP\n', '-' * 30)
+        self.optimizer = None
+        self.seMLP.optfun = self.optfun
+        results_arr2D = []
+        lrn_targ = self.data.y
+        x, ei = self.data.x, self.data.edge_index
+        for epoch in range(self.epochs):
+            self.seMLP.train()
+            batch_idx_train = np.random.choice(self.seMLP.train_idx, self.args.batch_size)
+            part2_out_train = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx_train)
+            if self.optimizer is None:
+                self.optimizer = self.seMLP.opt
+            idx = self.seMLP.index_on_device(batch_idx_train, part2_out_train.device)
+            loss_train = ops.nll_logsoftmax(part2_out_train, lrn_targ[idx].contiguous(), None, int(idx.numel()))
+            self.optimizer.zero_grad()
+            loss_train.backward()
+            self.optimizer.step()
+
+            self.seMLP.eval()
+            with torch.no_grad():
+                batch_idx_train = np.random.choice(self.seMLP.test_idx, self.args.batch_size)
+                part2_out_test = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx_train)
+                idx = self.seMLP.index_on_device(batch_idx_train, part2_out_test.device)
+                acc_test = evaluate(part2_out_test, lrn_targ[idx], None) * 100
+                result = [toitem(acc_test)]
+                if self.args.want_headtail:
+                    subsets = [self.data.large_deg_idx, self.data.small_deg_idx] + ([self.data.zero_deg_idx] if self.args.use_special_split else [])
+                    for batch_idx in subsets:
+                        out = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx)
+                        idx = self.seMLP.index_on_device(batch_idx, out.device)
+                        _train, test = self.eval_headtail__traintest_v2(out, lrn_targ[idx], idx, cal_acc_rounded100)
+                        result.append(test)
+            results_arr2D.append(result)
+            if epoch % 20 == 0:
+                if self.args.use_special_split:
+                    print(f'epoch {epoch}, acc test {toitem(acc_test):.2f}, head_tail_iso = {result[-3:]}')
+                else:
+                    print(f'epoch {epoch}, acc test {toitem(acc_test):.2}')
+        torch.cuda.synchronize(self.device)
+        _lib.device_status()
+        save_model(self.seMLP, join(self.modeldir, 'seMLP'))
+        results_arr2D = np.array(results_arr2D).T
+        npy_dir = f'{self.resdir}/seMLP'
+        wzRec(results_arr2D[0], f'acc_test@{npy_dir.replace("/", "@")}', want_save_npy=1, npy_dir=npy_dir)
+        if not self.args.want_headtail:
+            return results_arr2D[[0]]              # [1, epochs]
+        return results_arr2D[[0, -3, -2, -1]]      # [4, epochs]
 
     def replacement(self, le_guess, node_idx=None, return_selection=False):
         """SEMLP.replacement (MLP_model/__init__.py:143-156) for the rows `node_idx` of le_guess (all rows by default): softmax-weighted

@@ -673,6 +673,48 @@ int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const float* B, int64
                               const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int bits_relu_only, float* out_act, int64_t ld_act, void* ws,
                               size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * Student MLPs (MLP_model/__init__.py:1-156; cb_mlp.hip).  HBM-bound row kernels and losses; the Linear layers are cb_gemm_*.
+ * ---------------------------------------------------------------------------------- */
+
+/* The [LayerNorm, GELU, Dropout] tail of one getMLP group (utils.py:898-903: `nn.LayerNorm(d), nn.GELU(), nn.Dropout(p)`) in one pass over
+ * z [rows, d] contiguous (the Linear's output, bias added by the GEMM epilogue):
+ *     mean / rstd per row (biased variance, rstd = 1 / sqrt(var + eps));  u = gamma * (z - mean) * rstd + beta;
+ *     out = keep(seed, r * d + c) / (1 - p) * 0.5 u (1 + erf(u / sqrt 2))          (exact GELU, nn.GELU()'s default)
+ * keep() is cb_dropout_f32's draw for (seed, seed_dev, flat index r * d + c): no mask is stored; p == 0 (also: eval mode) draws nothing.
+ * stats (may be NULL; 8-byte aligned) receives {mean, rstd} per row for the backward.  1 <= d <= 512; d == 256 with 16-byte aligned
+ * pointers is the unmasked fast path, d % 4 == 0 with aligned pointers uses 16-byte accesses, anything else scalar ones.
+ * Traffic: 8 d + 8 bytes per row + 8 d bytes of parameters. */
+int cb_ln_gelu_drop_fwd_f32(const float* z, int64_t rows, int64_t d, const float* gamma, const float* beta, float eps, float p,
+                            uint64_t seed, const uint64_t* seed_dev, float* out, float* stats, void* stream);
+/* Its backward (autograd of the three modules) in one pass: recomputes x_hat, u and the keep mask from z, stats and the seed and writes
+ *     dz = rstd * (dx_hat - mean_c(dx_hat) - x_hat * mean_c(dx_hat * x_hat)),  dx_hat = gamma * keep / (1 - p) * gelu'(u) * dy;
+ *     dgamma[c] = sum_r du * x_hat,  dbeta[c] = sum_r du,  dbias[c] = sum_r dz[r, c]  (the bias gradient of the Linear in front).
+ * Any of the three may be NULL.  The column sums leave as one partial row per wavefront in ws (cb_ln_gelu_drop_bwd_workspace_bytes) and are
+ * summed in a fixed order: no atomics, two calls give the same bits.  Traffic: 12 d + 8 bytes per row. */
+size_t cb_ln_gelu_drop_bwd_workspace_bytes(int64_t rows, int64_t d);
+int cb_ln_gelu_drop_bwd_f32(const float* dy, const float* z, const float* stats, int64_t rows, int64_t d, const float* gamma,
+                            const float* beta, float p, uint64_t seed, const uint64_t* seed_dev, float* dz, float* dgamma,
+                            float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream);
+
+/* `nn.MSELoss()(part1_out, lrn_targ[batch_idx])` (trainer_node_classification.py:96,108) without materialising the gathered targets:
+ *     loss[0] = mean_{b, c} (pred[b, c] - target[row_index[b], c])^2;   grad[b, c] = 2 (pred - target) / (B D)   (grad may be NULL).
+ * pred / grad [B, D] contiguous, target [n_target_rows, ld_t]; row_index int64 (NULL: row b).  A row index outside [0, n_target_rows) is
+ * never dereferenced; the loss is then NaN.  Fixed-order reduction (ws: cb_reduce_workspace_bytes()). */
+int cb_mse_rows_f32(const float* pred, int64_t B, int64_t D, const float* target, int64_t ld_t, int64_t n_target_rows,
+                    const int64_t* row_index, float* loss, float* grad, void* ws, size_t ws_bytes, void* stream);
+
+/* Input of SEMLP's part 2 (MLP_model/__init__.py:102-108): out [B, F + 2 D] = [ x | alphas[1] * replaced | alphas[0] * part1_out ] with
+ * x [B, F], replaced / part1_out [B, D] contiguous and alphas a DEVICE pointer to the two learnable scales.  A block whose source pointer
+ * is NULL is not written: the reference's replacement() reads alphas[0] * part1_out (:103-104), so the caller fills x and that block first,
+ * hands out[:, F+D:] to cb_topk_replace_f32 as the queries, and fills the middle block with a second call.  The backward of the
+ * only differentiable inputs (x, replaced and part1_out are detached in the reference), in one launch + a one-wavefront finish:
+ *     dalphas[0] = <g[:, F+D:], part1_out>,  dalphas[1] = <g[:, F:F+D], replaced>      (ws: 2 * cb_reduce_workspace_bytes()). */
+int cb_part2_assemble_f32(const float* x, int64_t F, const float* replaced, const float* part1_out, int64_t D, const float* alphas,
+                          int64_t B, float* out, void* stream);
+int cb_part2_assemble_bwd_f32(const float* g, int64_t F, const float* replaced, const float* part1_out, int64_t D, int64_t B,
+                              float* dalphas, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
