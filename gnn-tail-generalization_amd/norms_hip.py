@@ -57,9 +57,16 @@ def _c(t):
 PRIMS = None
 
 
-def _colstats(x, w=None):
+def _colstats(x, w=None, shift=None):
+    """w None: sum(x - shift), sum((x - shift)^2);  w given: sum(x), sum(x * (w - shift))   (column sums; shift [d] or None = 0)."""
     if PRIMS is not None:
-        return PRIMS.colstats(x, w)
+        # The seam keeps its three methods: the pivot is taken off by its affine pass, the same float32 x - shift.  This restates the
+        # kernel's `x * (w - shift)` / `(x - shift)^2` for the CPU tests only; the device form is checked in tests/test_gpu_norm_kernels.py.
+        if shift is None:
+            return PRIMS.colstats(x, w)
+        if w is not None:
+            return PRIMS.colstats(x, PRIMS.affine(w, shift, None, None, 1.0))
+        return PRIMS.colstats(PRIMS.affine(x, shift, None, None, 1.0), None)
     lib = _lib.load()
     rows, d = x.shape
     s1 = torch.empty(d, dtype=torch.float32, device=x.device)
@@ -67,7 +74,7 @@ def _colstats(x, w=None):
     wsb = lib.cb_colstats_workspace_bytes(max(rows, 1), d)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.cb_colstats_f32(_lib.ptr(x), _lib.ptr(w), rows, d, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), wsb,
+        _lib.check(lib.cb_colstats_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(shift), rows, d, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), wsb,
                                        _lib.stream_ptr()), 'cb_colstats_f32')
     return s1, s2
 
@@ -83,13 +90,16 @@ def _affine(x, shift=None, scale=None, bias=None, gscale=1.0):
     return y
 
 
-def _combine(g, xh=None, a=None, b=None, e=None):
-    if PRIMS is not None:
+def _combine(g, xh=None, a=None, b=None, e=None, xshift=None):
+    """a * g + b * (xh - xshift) + e"""
+    if PRIMS is not None:                  # (as in _colstats: xh - xshift through the seam's affine pass)
+        if xshift is not None:
+            xh = PRIMS.affine(xh, xshift, None, None, 1.0)
         return PRIMS.combine(g, xh, a, b, e)
     lib = _lib.load()
     dx = torch.empty_like(g)
     with torch.cuda.device(g.device):
-        _lib.check(lib.cb_col_bwd_combine_f32(_lib.ptr(g), _lib.ptr(xh), _lib.ptr(a), _lib.ptr(b), _lib.ptr(e), 1.0, 1.0, _lib.ptr(dx),
+        _lib.check(lib.cb_col_bwd_combine_f32(_lib.ptr(g), _lib.ptr(xh), _lib.ptr(xshift), _lib.ptr(a), _lib.ptr(b), _lib.ptr(e), 1.0, 1.0, _lib.ptr(dx),
                                               g.shape[0], g.shape[1], _lib.stream_ptr()), 'cb_col_bwd_combine_f32')
     return dx
 
@@ -131,13 +141,28 @@ def node_norm(x, kind='n', eps=1e-5, power=0.5):
     return _NodeNormFn.apply(x, float(c), float(q), float(eps))
 
 
+def _centred_stats(x):
+    """Column mean and squared deviations of x [rows, d] over ALL rows (all ranks under row_sharding), safe for a column whose mean
+    is large against its spread (one-pass s2/n - mu^2 loses (mu/std)^2 of its digits there): the mean first, global, then the sums
+    of (x - mu) and (x - mu)^2 about that shared pivot.  Returns n, mu, delta, m2: the mean is mu + delta (two floats: delta = the
+    rounding left in mu, never added into it), m2 = sum_r (x - mean)^2 = c2 - c1 * delta exactly.  Two passes over x (the first
+    one's sum of squares is not used).
+    MeanNorm takes both passes too, for delta alone: its y then carries about one ulp of error where a float32-rounded mean, torch's
+    included, leaves hundreds to thousands of 2^-24 on columns with mean >> std (profiles/norm_kernels.md)."""
+    n = _rows(x)
+    (s1,) = _global(_colstats(x)[0])
+    mu = s1 / n
+    c1, c2 = _global(*_colstats(x, shift=mu))
+    delta = c1 / n
+    return n, mu, delta, (c2 - c1 * delta).clamp_(min=0)
+
+
 class _MeanNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         x = _c(x)
-        (s1,) = _global(_colstats(x)[0])
-        ctx.n = _rows(x)
-        return _affine(x, shift=s1 / ctx.n)
+        ctx.n, mu, delta, _m2 = _centred_stats(x)
+        return _affine(x, shift=mu, bias=-delta)                       # (x - mu) - delta
 
     @staticmethod
     def backward(ctx, g):
@@ -154,12 +179,10 @@ class _PairNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         x = _c(x)
-        n = _rows(x)
-        s1, s2 = _global(*_colstats(x))
-        mu = s1 / n
-        r = torch.sqrt(1e-6 + ((s2 - n * mu * mu).sum() / n))          # sqrt(1e-6 + mean_rows sum_c (x - mu)^2)
+        n, mu, delta, m2 = _centred_stats(x)
+        r = torch.sqrt(1e-6 + m2.sum() / n)                            # sqrt(1e-6 + mean_rows sum_c (x - mean)^2)
         inv = (1.0 / r).expand(x.shape[1]).contiguous()
-        y = _affine(x, shift=mu, scale=inv)
+        y = _affine(x, shift=mu, scale=inv, bias=-delta * inv)
         ctx.save_for_backward(y, r)
         ctx.n = n
         return y
@@ -184,34 +207,33 @@ class _BatchNormTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         x = _c(x)
-        n = _rows(x)
-        s1, s2 = _global(*_colstats(x))
-        mu = s1 / n
-        var = (s2 / n - mu * mu).clamp_(min=0)
+        n, mu, delta, m2 = _centred_stats(x)
+        var = m2 / n
         rstd = torch.rsqrt(var + eps)
         scale = rstd * weight if weight is not None else rstd
-        y = _affine(x, shift=mu, scale=scale, bias=bias)
-        ctx.save_for_backward(x, weight, mu, rstd)
+        y = _affine(x, shift=mu, scale=scale, bias=(bias - delta * scale if bias is not None else -delta * scale))
+        ctx.save_for_backward(x, weight, mu, delta, rstd)
         ctx.has_bias, ctx.n = bias is not None, n
-        ctx.mark_non_differentiable(mu, var)
-        return y, mu, var
+        mean = mu + delta
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
 
     @staticmethod
     def backward(ctx, g, _gmu, _gvar):
-        x, weight, mu, rstd = ctx.saved_tensors
+        x, weight, mu, delta, rstd = ctx.saved_tensors
         g = _c(g)
         n = ctx.n
-        sg_l, sgx_l = _colstats(g, w=x)                  # this rank's rows
+        sg_l, sgx_l = _colstats(g, w=x, shift=mu)        # this rank's rows: sum g, sum g * (x - mu)
         sg, sgx = _global(sg_l, sgx_l)                   # all rows
-        dgamma = rstd * (sgx - mu * sg)                  # sum_r g * xhat
+        dgamma = rstd * (sgx - delta * sg)               # sum_r g * xhat, with xhat = (x - mu - delta) * rstd
         gam = weight if weight is not None else torch.ones_like(rstd)
-        a = gam * rstd                                   # dx = a*g + b*xhat + e, with xhat = (x - mu) * rstd
-        b_hat = -a * dgamma / n
-        e = -a * sg / n - b_hat * rstd * mu
-        dx = _combine(g, xh=x, a=a, b=b_hat * rstd, e=e)
+        a = gam * rstd                                   # dx = a*g + b*(x - mu) + e: written on the centred x, nothing cancels
+        b = -a * rstd * dgamma / n
+        e = -a * sg / n - b * delta
+        dx = _combine(g, xh=x, a=a, b=b, e=e, xshift=mu)
         # the affine parameters are replicated and their gradients are summed over the ranks afterwards (dist.allreduce_grads):
         # hand back this rank's share (linear in the sums, so the shares add up to dgamma / sg)
-        return dx, (rstd * (sgx_l - mu * sg_l) if weight is not None else None), (sg_l if ctx.has_bias else None), None
+        return dx, (rstd * (sgx_l - delta * sg_l) if weight is not None else None), (sg_l if ctx.has_bias else None), None
 
 
 def batch_norm(layer, x):
@@ -248,8 +270,8 @@ class _AffineEvalFn(torch.autograd.Function):
         g = _c(g)
         dscale = dbias = None
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            sg, sgx = _colstats(g, w=x)                  # sum_r g, sum_r g * x  (this rank's rows: replicated-parameter share)
-            dscale = sgx - shift * sg if ctx.needs_input_grad[2] else None
+            sg, sgx = _colstats(g, w=x, shift=shift.contiguous())      # sum_r g, sum_r g * (x - shift)  (this rank's rows: replicated-parameter share)
+            dscale = sgx if ctx.needs_input_grad[2] else None
             dbias = sg if (ctx.has_bias and ctx.needs_input_grad[3]) else None
         dx = _combine(g, a=scale.contiguous()) if ctx.needs_input_grad[0] else None
         return dx, None, dscale, dbias

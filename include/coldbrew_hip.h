@@ -386,16 +386,20 @@ int cb_node_norm_bwd_f32(const float* x, const float* g, const float* stats2, fl
                          void* stream);
 /* Column statistics in one pass: colsum[c] = sum_r x[r,c]; colsum2[c] = sum_r x[r,c]^2 (w == NULL) or
  * sum_r x[r,c]*w[r,c] — the reductions behind mean_norm / pair_norm / BatchNorm1d (norm_tricks.py:25-41,106,132)
- * and their backward; fixed-order two-stage reduce (ws: cb_colstats_workspace_bytes). */
+ * and their backward; fixed-order two-stage reduce (ws: cb_colstats_workspace_bytes).
+ * shift [d] (may be NULL) centres them about a per-column pivot, so that a column mean that is large against the
+ * column's spread does not cancel:  w == NULL: colsum = sum_r (x - shift), colsum2 = sum_r (x - shift)^2;
+ * w != NULL: colsum = sum_r x, colsum2 = sum_r x * (w - shift). */
 size_t cb_colstats_workspace_bytes(int64_t rows, int64_t d);
-int cb_colstats_f32(const float* x, const float* w, int64_t rows, int64_t d, float* colsum, float* colsum2, void* ws, size_t ws_bytes,
-                    void* stream);
+int cb_colstats_f32(const float* x, const float* w, const float* shift, int64_t rows, int64_t d, float* colsum, float* colsum2,
+                    void* ws, size_t ws_bytes, void* stream);
 /* y[r,c] = ((x[r,c] - shift[c]) * scale[c]) * gscale + bias[c]  (vectors may be NULL). */
 int cb_col_affine_f32(const float* x, const float* shift, const float* scale, const float* bias, float gscale, float* y, int64_t rows,
                       int64_t d, void* stream);
-/* dx[r,c] = a[c]*ga*g[r,c] + b[c]*gb*xh[r,c] + e[c]  (xh, a, b, e may be NULL: a,b default 1) — the backward of the column norms. */
-int cb_col_bwd_combine_f32(const float* g, const float* xh, const float* a, const float* b, const float* e, float ga, float gb,
-                           float* dx, int64_t rows, int64_t d, void* stream);
+/* dx[r,c] = a[c]*ga*g[r,c] + b[c]*gb*(xh[r,c] - xs[c]) + e[c]  (xh, xs, a, b, e may be NULL: a,b default 1, xs default 0) — the
+ * backward of the column norms. */
+int cb_col_bwd_combine_f32(const float* g, const float* xh, const float* xs, const float* a, const float* b, const float* e, float ga,
+                           float gb, float* dx, int64_t rows, int64_t d, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Teacher -> student hand-off: `SEMLP.replacement` (MLP_model/__init__.py:143-156), a per-node

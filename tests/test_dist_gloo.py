@@ -451,7 +451,7 @@ def test_edge_balanced_partition():
     assert empty.bounds[-1] == 3 and sum(empty.hi(p) - empty.lo(p) for p in range(8)) == 3
 
 
-def _norm_worker(rank, world, port, _unused, q):
+def _norm_worker(rank, world, port, extra, q):
     _setup(rank, world, port)
     try:
         import coldbrew_oracle as orc
@@ -498,6 +498,39 @@ def _norm_worker(rank, world, port, _unused, q):
                 torch.testing.assert_close(bn.bias.grad, bn_ref.bias.grad, atol=2e-5, rtol=1e-4)
                 torch.testing.assert_close(bn.running_mean, bn_ref.running_mean, atol=1e-6, rtol=1e-5)
                 torch.testing.assert_close(bn.running_var, bn_ref.running_var, atol=1e-6, rtol=1e-5)
+        # further inputs (tests/norm_cases.py: columns whose mean is large against their spread), uneven row blocks again: the shards'
+        # output against float64, by the project's rule against torch's own float32 on the whole matrix (student_ref.within)
+        import norm_cases as nc
+        import student_ref as sr
+        bad = []
+        for name in (extra or ()):
+            x, gout, w, b = nc.make(name)
+            n, d = x.shape
+            part = Partition(n, world, rank, bounds=[0, n // 6] + [n // 6 + (n - n // 6) * (r + 1) // (world - 1) for r in range(world - 1)])
+            for kind in nc.KINDS:
+                bn = torch.nn.BatchNorm1d(d)
+                with torch.no_grad():
+                    bn.weight.copy_(w)
+                    bn.bias.copy_(b)
+                xl = part.slice_rows(x).clone().requires_grad_(True)
+                with norms_hip.row_sharding(None, n):
+                    yl = {'batch': lambda t: norms_hip.batch_norm(bn, t), 'pair': norms_hip.pair_norm, 'mean': norms_hip.mean_norm}[kind](xl)
+                    yl.backward(part.slice_rows(gout))
+                got = [yl.detach(), xl.grad]
+                if kind == 'batch':
+                    allreduce_grads([bn.weight, bn.bias])
+                    got += [bn.weight.grad, bn.bias.grad]
+                ref = nc.torch_norm(kind, x.double(), gout, w, b)
+                t32 = nc.torch_norm(kind, x, gout, w, b)
+                for nm, u, v, r in zip(nc.NAMES, got, t32, ref):
+                    if nm in ('y', 'dx'):
+                        v, r = part.slice_rows(v), part.slice_rows(r)
+                    err, err32 = sr.rel_err(u, r), sr.rel_err(v, r)
+                    if rank == 0:
+                        print(f'sharded world={world} {name} {kind} {nm}: err={err / sr.EPS24:.2f} err32={err32 / sr.EPS24:.2f} (x 2^-24)', flush=True)
+                    if not sr.within(err, err32):
+                        bad.append((name, kind, nm, round(err / sr.EPS24, 2), round(err32 / sr.EPS24, 2)))
+        assert not bad, bad
         q.put((rank, 'ok'))
     except Exception:  # noqa: BLE001
         import traceback
