@@ -139,6 +139,11 @@ SIGNATURES = {
     'cb_gemm_tn_gdrop_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _SZ, _P]),
     'cb_spmm_csr_lp_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, _P, _P, _I64, _I32, _I32, _I32, _P, _P,
                                           _P, _SZ, _P]),
+    'cb_spmm_csr_prop_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _I64,
+                                            _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    'cb_cs_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_cs_residual_init_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    'cb_cs_correct_snap_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, ctypes.c_float, _P, _P, _I64, _P, _P, _P]),
     'cb_trunk_input_bwd_multi_f32': (ctypes.c_int, [_P, ctypes.c_uint64, _I32, _P, _P, ctypes.c_float, _P, _P, _I64, _I64, ctypes.c_float,
                                                     _P, _I64, _P, _P, _SZ, _P, _P, _P]),
     'cb_trunk_input_bwd_multi_cs_f32': (ctypes.c_int, [_P, ctypes.c_uint64, _I32, _P, _P, ctypes.c_float, _P, _P, _I64, _I64, ctypes.c_float,

@@ -12,7 +12,9 @@ Documented deviations:
   * `--dataset` additionally accepts 'ogbn-products' and the synthetic stand-ins of
     SURVEY.md §8(d) ('S-cora', 'S-pubmed', 'S-arxiv', 'S-products', 'S-pl10M', 'S-tiny');
   * extra flag `--agg_dtype {f32,bf16}` (build extension, BASELINE config 2): bf16 storage of the rows the
-    aggregation gathers, fp32 accumulation; the reference is fp32-only.
+    aggregation gathers, fp32 accumulation; the reference is fp32-only;
+  * extra flag `--correct_and_smooth {0,1}` (build extension): run the reference's Correct & Smooth (args.lpStep, set_labprop_configs) on the
+    trained model's probabilities after the `--train_which` run; the reference configures lpStep on every run but only its LP trainer uses it.
 """
 import argparse
 import os
@@ -136,6 +138,7 @@ def build_parser():
     a('--ckpt_every', type=int, default=0)   # build extension: write the resumable checkpoint every k epochs (0 = only at the end)
     a('--hip_graph', type=int, default=0)    # build extension: 1 = the epoch loop replays the training step (and the eval forward) as hipGraphs
     a('--agg_dtype', type=str, default='f32', choices=['f32', 'bf16'])   # build extension: storage type of the aggregated rows
+    a('--correct_and_smooth', type=int, default=0)   # build extension: 1 = after the --train_which run, Correct & Smooth (args.lpStep) post-processes the trained model's probabilities on the device (trainer.correct_and_smooth)
     a('--rows_only_forward', type=int, default=1)   # build extension: 1 = the trainer promises the model that its training forward's output is read in the train rows only (trunk.py "Rows-only forward"; the other rows come back as NaN); 0 = every row of every training forward
     # link-prediction (I2-GTL) flags: accepted for CLI compatibility, unused by this path
     a('--public_data_convert_overlapped_subgraph', type=bool, default=True)
@@ -280,8 +283,43 @@ def unify_mlps(args):                              # base_options.py:450-471
         args.train_which = 'GraphMLP'
 
 
+class _Cfg:
+    """Plain attribute bag (the reference's `class C: pass`)."""
+
+    def __repr__(self):
+        return f'{type(self).__name__}({vars(self)})'
+
+
 def set_labprop_configs(args):
-    """Label-propagation options (base_options.py:352-402) belong to the out-of-scope LP trainer;
-    only the attribute the TeacherGNN path could meet is defined."""
+    """Label-propagation / Correct & Smooth options (base_options.py:352-402): args.preStep, args.midStep and args.lpStep with the reference's
+    values, `LP__*` overrides included.  Build extension: --correct_and_smooth=1 turns lpStep.no_prep off (LPStep then runs lpStep.fn on a model's
+    probabilities instead of plain label propagation).  lpStep.lp_force_on_cpu keeps the reference's value and is ignored: C&S runs on the device."""
+    args.preStep = _Cfg()
+    args.lpStep = _Cfg()
+    args.midStep = _Cfg()
+
     args.lp_has_prep = 1
-    args.lpStep = None
+
+    args.preStep.num_propagations = 10
+    args.preStep.p = 1
+    args.preStep.alpha = 0.5
+    args.preStep.pre_methods = 'diffusion+spectral'
+
+    args.midStep.model = 'mlp'
+    args.midStep.hidden_channels = 256
+    args.midStep.num_layers = 3
+
+    args.lpStep.A = 'DAD' if args.LP__which_corr_and_DAD == '' else args.LP__which_corr_and_DAD
+    args.lpStep.num_propagations = 50 if args.LP__num_propagations == -1 else args.LP__num_propagations
+    args.lpStep.alpha = 0.5 if args.LP__alpha == -1. else args.LP__alpha
+
+    args.lpStep.fn = 'double_correlation_autoscale'      # applies to the 'with a model' case only, not to pure label propagation
+    args.lpStep.A1 = 'DA'
+    args.lpStep.A2 = 'AD'
+    args.lpStep.alpha1 = 0.9791632871592579
+    args.lpStep.alpha2 = 0.7564990804200602
+    args.lpStep.num_propagations1 = 50
+    args.lpStep.num_propagations2 = 50
+    args.lpStep.lp_force_on_cpu = True
+
+    args.lpStep.no_prep = 0 if int(getattr(args, 'correct_and_smooth', 0) or 0) else 1

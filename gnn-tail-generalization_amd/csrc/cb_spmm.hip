@@ -21,6 +21,7 @@
 //     so results are bit-reproducible run to run.
 //   * streaming data (indices, output rows) uses non-temporal accesses so the 4 MiB L2s and
 //     the 256 MiB Infinity Cache keep the re-used neighbour rows (hub sources).
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -202,22 +203,47 @@ extern "C" int cb_spmm_csr_colscale_f32(const int32_t* rowptr, const int32_t* co
 // With h = D^-1/2 result_t, row_scale = alpha D^-1/2, mix = y0, c_mix = 1 - alpha and post_scale = D^-1/2 the output IS the next step's
 // gather operand D^-1/2 result_{t+1}; post_scale = NULL on the last step returns result itself.  Narrow rows (d = number of classes):
 // one lane per column (the VEC = 1 instantiation of k_spmm_rows + hub kernels).
+static int spmm_prop_impl(const char* who, const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
+                          const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, int clamp, float lo, float hi, const uint8_t* fix_rows,
+                          const float* post_scale, float* out, int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
+                          const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream) {
+  CB_CHECK_ARG(N >= 0 && E >= 0 && d >= 0, CB_E_INVALID, "%s: negative size", who);
+  CB_CHECK_ARG(N < INT32_MAX && E < INT32_MAX && d < (1 << 20), CB_E_RANGE, "%s: size exceeds the int32 contract", who);
+  CB_CHECK_ARG(lo <= hi, CB_E_INVALID, "%s: clamp bounds must satisfy lo <= hi (and neither may be NaN)", who);
+  if (N == 0 || d == 0) return CB_OK;
+  CB_CHECK_ARG(rowptr && h && out && mix && (E == 0 || col), CB_E_INVALID, "%s: null pointer", who);
+  CB_CHECK_ARG(ld_h >= d && ld_out >= d && ld_mix >= d, CB_E_INVALID, "%s: leading dimension smaller than d", who);
+  CB_CHECK_ARG(hub_T > 0 && n_hubs >= 0 && n_chunks >= 0, CB_E_INVALID, "%s: bad hub plan", who);
+  CB_CHECK_ARG(n_hubs == 0 || (hub_rows && hub_chunk_ptr && ws && ws_bytes >= cb_spmm_workspace_bytes(n_chunks, d)), CB_E_WORKSPACE,
+               "%s: hub plan given but workspace missing/too small", who);
+  if (n_hubs == 0) hub_T = INT32_MAX;
+  Epilogue ep{row_scale, nullptr, 0, nullptr, 0, 0};
+  ep.lp_mix = mix; ep.ld_lp = ld_mix; ep.lp_c_mix = c_mix; ep.lp_post = post_scale;
+  ep.lp_clamp = clamp; ep.lp_lo = lo; ep.lp_hi = hi; ep.lp_fix = fix_rows;
+  return launch_spmm<1>(rowptr, col, N, h, ld_h, d, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws, (hipStream_t)stream);
+}
+
 extern "C" int cb_spmm_csr_lp_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
                                   const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, const float* post_scale, float* out,
                                   int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
                                   const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(N >= 0 && E >= 0 && d >= 0, CB_E_INVALID, "cb_spmm_csr_lp_f32: negative size");
-  CB_CHECK_ARG(N < INT32_MAX && E < INT32_MAX && d < (1 << 20), CB_E_RANGE, "cb_spmm_csr_lp_f32: size exceeds the int32 contract");
-  if (N == 0 || d == 0) return CB_OK;
-  CB_CHECK_ARG(rowptr && h && out && mix && (E == 0 || col), CB_E_INVALID, "cb_spmm_csr_lp_f32: null pointer");
-  CB_CHECK_ARG(ld_h >= d && ld_out >= d && ld_mix >= d, CB_E_INVALID, "cb_spmm_csr_lp_f32: leading dimension smaller than d");
-  CB_CHECK_ARG(hub_T > 0 && n_hubs >= 0 && n_chunks >= 0, CB_E_INVALID, "cb_spmm_csr_lp_f32: bad hub plan");
-  CB_CHECK_ARG(n_hubs == 0 || (hub_rows && hub_chunk_ptr && ws && ws_bytes >= cb_spmm_workspace_bytes(n_chunks, d)), CB_E_WORKSPACE,
-               "cb_spmm_csr_lp_f32: hub plan given but workspace missing/too small");
-  if (n_hubs == 0) hub_T = INT32_MAX;
-  Epilogue ep{row_scale, nullptr, 0, nullptr, 0, 0};
-  ep.lp_mix = mix; ep.ld_lp = ld_mix; ep.lp_c_mix = c_mix; ep.lp_post = post_scale;
-  return launch_spmm<1>(rowptr, col, N, h, ld_h, d, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws, (hipStream_t)stream);
+  return spmm_prop_impl("cb_spmm_csr_lp_f32", rowptr, col, N, E, h, ld_h, d, row_scale, mix, ld_mix, c_mix, 1, 0.f, 1.f, nullptr, post_scale, out, ld_out,
+                        hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws, ws_bytes, stream);
+}
+
+// The propagation step of general_outcome_correlation (outcome_correlation.py:128-145) for every normalisation and post-step the reference uses:
+//     out[v, :] = post_scale[v] * fix_v(clamp(row_scale[v] * sum_{u in row v} h[u, :] + c_mix * mix[v, :], lo, hi))
+// A_norm = diag(R) A diag(S) (DAD: R = S = D^-1/2; DA: R = D^-1, S = 1; AD: R = 1, S = D^-1) needs no per-edge factor when the state carried from step
+// to step is s_t = S (.) result_t: row_scale = alpha R, post_scale = S (NULL on the last step), c_mix = 1 - alpha (alpha_term) or 1.  lo = -inf and
+// hi = +inf: no clamp (a NaN then stays a NaN).  fix_rows ([N] bytes or NULL): a row with a non-zero byte becomes mix[v, :] (fix_inputs, :194-199).
+// The kernel, the hub plan and every expression are those of cb_spmm_csr_lp_f32: lo = 0, hi = 1, fix_rows = NULL gives its results bit for bit.
+extern "C" int cb_spmm_csr_prop_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
+                                    const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, float lo, float hi, const uint8_t* fix_rows,
+                                    const float* post_scale, float* out, int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks,
+                                    const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream) {
+  const int clamp = !(lo == -INFINITY && hi == INFINITY);
+  return spmm_prop_impl("cb_spmm_csr_prop_f32", rowptr, col, N, E, h, ld_h, d, row_scale, mix, ld_mix, c_mix, clamp, lo, hi, fix_rows, post_scale, out,
+                        ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws, ws_bytes, stream);
 }
 
 // out = act(row_scale * (acc_init + sum over this CSR's columns) + bias): the second (halo-column) pass of the node-sharded

@@ -126,19 +126,29 @@ struct Epilogue {
   // CS kernels (d % 256 == 0, fp32 rows, plain store): out[v] = row_scale[v] * sum_u col_scale[u] * h[u] — the factor of a SOURCE row applied
   // as the row is gathered (the row-sparse backward's A (a * X) on the loss rows: no scaled copy of X, trunk.py)
   const float* col_scale;   // [n_cols] or null
+  // generalised propagation step (cb_spmm_csr_prop_f32; the label-propagation entry sets lp_clamp = 1, lp_lo = 0, lp_hi = 1, lp_fix = null):
+  //   out[v] = lp_post[v] * fix_v(clamp(row_scale[v] * acc + lp_c_mix * lp_mix[v], lp_lo, lp_hi))
+  // lp_clamp = 0: no clamp (the identity post-step); lp_fix ([N] bytes or null): a row with a non-zero byte is replaced by lp_mix[v] itself
+  // (fix_inputs, outcome_correlation.py:194-199)
+  int lp_clamp;
+  float lp_lo, lp_hi;
+  const uint8_t* lp_fix;
 };
 
 template <int VEC>
 __device__ __forceinline__ void write_row_lp(float* __restrict__ out_row, const float (&acc)[VEC], float scale, const Epilogue& ep, int64_t row,
                                              int c0, bool (&on)[VEC]) {
   const float post = ep.lp_post ? ep.lp_post[row] : 1.f;
+  const bool fix = ep.lp_fix && ep.lp_fix[row];      // (wave-uniform)
   float r[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     if (!on[i]) continue;
+    const float m = ep.lp_mix[row * ep.ld_lp + c0 + i];
     float t = acc[i] * scale;
-    t = t + ep.lp_c_mix * ep.lp_mix[row * ep.ld_lp + c0 + i];
-    t = fminf(fmaxf(t, 0.f), 1.f);
+    t = t + ep.lp_c_mix * m;
+    if (ep.lp_clamp) t = fminf(fmaxf(t, ep.lp_lo), ep.lp_hi);
+    if (fix) t = m;
     r[i] = t * post;
     __builtin_nontemporal_store(r[i], out_row + i);
   }

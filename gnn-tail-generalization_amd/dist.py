@@ -1429,6 +1429,9 @@ class ShardedTrainer:
     def main(self):
         if self.args.train_which != 'TeacherGNN':
             raise NotImplementedError('the node-sharded trainer runs --train_which=TeacherGNN')
+        if int(getattr(self.args, 'correct_and_smooth', 0) or 0):
+            raise NotImplementedError('--correct_and_smooth=1 on the node-sharded trainer: the propagation steps would need the exchange of the state '
+                                      'rows between the shards at every step, which is not built; run it on one device')
         return self.train_teacherGNN()
 
 

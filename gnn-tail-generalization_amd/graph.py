@@ -6,6 +6,8 @@ and the hub plan, all built once on the GPU through the C ABI (include/coldbrew_
 The DGL-like query surface that GCNConv.forward touches is kept: in_degrees(),
 out_degrees(), number_of_edges(), number_of_nodes().
 """
+import math
+
 import torch
 
 from . import _lib
@@ -496,6 +498,37 @@ class CSRGraph:
                                               _lib.stream_ptr()), 'cb_spmm_csr_lp_f32')
         return out
 
+    def spmm_prop(self, h, row_scale, mix, c_mix, clamp=None, fix_rows=None, post_scale=None, out=None):
+        """out = post_scale * fix(clamp(row_scale * (A h) + c_mix * mix, lo, hi)): one propagation step of general_outcome_correlation with its
+        post-step in the aggregation's store (cb_spmm_csr_prop_f32).  clamp: (lo, hi) or None (identity); fix_rows: uint8 [N] or None — rows with a
+        non-zero byte are set to their mix row (fix_inputs).  A_norm = diag(R) A diag(S) is applied through the operands: h = S * result_t,
+        row_scale = alpha R, post_scale = S (ops.propagate).  clamp = (0, 1) without fix_rows is spmm_lp bit for bit."""
+        lib = _lib.load()
+        _lib.require_device(h, row_scale, mix, fix_rows, post_scale, out)
+        if self.n_cols != self.N or self.row_offset:
+            raise ValueError('spmm_prop: a propagation step needs the whole square graph on this device; this CSR is a row block of one '
+                             f'([{self.N}, {self.n_cols}]): the exchange of the state rows between blocks is missing')
+        if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != self.n_cols or mix.shape != (self.N, h.shape[1]) or mix.dtype != torch.float32:
+            raise ValueError('spmm_prop: float32 [n_cols, d] rows and a float32 [N, d] mix matrix expected')
+        if fix_rows is not None and (fix_rows.dtype != torch.uint8 or fix_rows.shape != (self.N,) or not fix_rows.is_contiguous()):
+            raise ValueError('spmm_prop: fix_rows is a contiguous uint8 [N] mask (non-zero = the row keeps its mix row)')
+        lo, hi = (-math.inf, math.inf) if clamp is None else (float(clamp[0]), float(clamp[1]))
+        h = h if h.stride(1) == 1 else h.contiguous()
+        mix = mix if mix.stride(1) == 1 else mix.contiguous()
+        d = h.shape[1]
+        if out is None:
+            out = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
+        plan = self._plan
+        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
+        ws = self._workspace(ws_bytes)
+        with torch.cuda.device(h.device):
+            _lib.check(lib.cb_spmm_csr_prop_f32(_lib.ptr(self.rowptr), _lib.ptr(self.col), self.N, self.E, _lib.ptr(h), h.stride(0) if h.shape[0] > 1 else d,
+                                                d, _lib.ptr(row_scale), _lib.ptr(mix), mix.stride(0) if self.N > 1 else d, float(c_mix), lo, hi,
+                                                _lib.ptr(fix_rows), _lib.ptr(post_scale), _lib.ptr(out), out.stride(0) if self.N > 1 else d,
+                                                self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr),
+                                                _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), 'cb_spmm_csr_prop_f32')
+        return out
+
     def edge_perm(self, transpose=False):
         """CSR position -> column of edge_index (int64 [E]) for the by-dst (transpose=False) or by-src orientation: the stable sort of
         the (row, col) keys, i.e. the order cb_csr_from_coo_i64 lays the edges out in (duplicates of a multigraph keep their input
@@ -746,6 +779,10 @@ class SegmentedCSRGraph:
 
     def algorithmic_bytes(self, d, elem=4, row_scale=True, bias=True, src_elem=None):
         return self.E * (d * (src_elem or elem) + 4) + self.N * (d * elem + 4) + (4 * self.N if row_scale else 0) + (d * elem if bias else 0)
+
+    def spmm_prop(self, *args, **kwargs):
+        raise ValueError('spmm_prop: a segmented graph (E >= 2^31) is not served: the propagation step is one launch over an int32-indexed CSR, '
+                         'and the per-segment launches with a shared state matrix are missing')
 
     def spmm(self, h, transpose=False, row_scale=None, bias=None, relu=False, out=None, acc_init=None):
         """As CSRGraph.spmm: one launch per row block into that block's rows of `out`."""

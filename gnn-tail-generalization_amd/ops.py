@@ -503,6 +503,174 @@ def label_propagation(graph, y0, deg_inv_sqrt, alpha, num_propagations):
     return h[:, :c].contiguous() if cp != c else h
 
 
+# ---------------------------------------------------------------------------------------------
+# Correct & Smooth (Label_propagation_model/outcome_correlation.py:95-213)
+# ---------------------------------------------------------------------------------------------
+ADJ_FORMS = ('DAD', 'DA', 'AD')
+CS_MODES = {'double_correlation_autoscale': 0, 'double_correlation_fixed': 1, 'only_outcome_correlation': 2}
+
+
+def padded_classes(c):
+    """Row width of the matrices a propagation gathers (label_propagation: rows of more than 16 classes are padded to 64-byte multiples)."""
+    return (c + 15) // 16 * 16 if c > 16 else c
+
+
+def adj_scales(deg_inv_sqrt, adj):
+    """(R, S) of A_norm = diag(R) A diag(S) for gen_normalized_adjs' three forms (:51-55); None stands for the all-ones vector."""
+    if adj not in ADJ_FORMS:
+        raise ValueError(f"normalised adjacency '{adj}': one of {ADJ_FORMS}")
+    dis = _c(deg_inv_sqrt.float())
+    if adj == 'DAD':
+        return dis, dis
+    dis2 = dis * dis
+    return (dis2, None) if adj == 'DA' else (None, dis2)
+
+
+def _prop_graph(graph):
+    if not hasattr(graph, 'spmm_prop'):
+        raise ValueError(f'{type(graph).__name__} has no spmm_prop: propagation runs on one whole CSRGraph (a node-sharded graph would need the '
+                         'exchange of the state rows between the shards at every step, which is missing)')
+    if not getattr(graph, 'symmetric', True):
+        raise ValueError('propagation needs a symmetric graph (to_undirected, outcome_correlation.py:41): the by-dst CSR then serves DAD, DA and AD alike')
+    return graph
+
+
+def rows_mask(rows, n, device):
+    """uint8 [n] mask of a row set given as an index tensor, a bool mask or already as such a mask (no host synchronisation)."""
+    if rows is None:
+        return None
+    rows = torch.as_tensor(rows, device=device)
+    if rows.dtype == torch.uint8 and rows.shape == (n,):
+        return _c(rows)
+    if rows.dtype == torch.bool:
+        return rows.to(torch.uint8).contiguous()
+    return torch.zeros(n, dtype=torch.uint8, device=device).index_fill_(0, rows.long().reshape(-1), 1)
+
+
+def _scaled_rows(y, s):
+    if s is None:
+        return y
+    return act_bwd(y, None, s, want_out=True, want_colsum=False)[0]
+
+
+def _propagate_padded(graph, y, h, R, S, alpha, T, clamp, alpha_term, fix):
+    """T steps from the state h = S * y over the padded mix matrix y; returns result_T (padded).  y is never written; h may be y itself."""
+    a_r = _c(R * float(alpha)) if R is not None else torch.full((y.shape[0],), float(alpha), dtype=torch.float32, device=y.device)
+    c_mix = 1.0 - float(alpha) if alpha_term else 1.0
+    bufs = [torch.empty_like(y), torch.empty_like(y) if T > 1 else None]
+    for t in range(T):
+        out = bufs[t & 1]
+        graph.spmm_prop(h, a_r, y, c_mix, clamp=clamp, fix_rows=fix, post_scale=None if t == T - 1 else S, out=out)
+        h = out
+    return h
+
+
+def propagate(graph, y, deg_inv_sqrt, alpha, num_propagations, adj='DAD', clamp=(0.0, 1.0), alpha_term=True, fixed_rows=None):
+    """general_outcome_correlation (:128-145) on the device: result <- post(alpha * A_norm result + (1 - alpha | 1) * y), `num_propagations` times from
+    result = y, with A_norm one of DAD / DA / AD (:51-55) and post = clamp(lo, hi), the identity (clamp=None) and / or fix_inputs (fixed_rows: index
+    tensor or mask of the rows that are reset to their rows of y after every step, :194-199).  Every step is ONE launch of cb_spmm_csr_prop_f32: the
+    state carried between steps is S * result_t (see adj_scales), so no normalised copy of the adjacency and no elementwise pass exists."""
+    _lib.require_device(y, deg_inv_sqrt)
+    graph = _prop_graph(graph)
+    y = _c(y.float())
+    T = int(num_propagations)
+    if T <= 0:
+        return y.clone()
+    R, S = adj_scales(deg_inv_sqrt, adj)
+    c = y.shape[1]
+    cp = padded_classes(c)
+    if cp != c:
+        y = torch.nn.functional.pad(y, (0, cp - c))
+    fix = rows_mask(fixed_rows, y.shape[0], y.device)
+    out = _propagate_padded(graph, y, _scaled_rows(y, S), R, S, alpha, T, None if clamp is None else (float(clamp[0]), float(clamp[1])), alpha_term, fix)
+    return out[:, :c].contiguous() if cp != c else out
+
+
+def cs_residual_init(model_out, labels, label_rows, state_scale=None, want_state=False):
+    """pre_residual_correlation (:95-110) as one row kernel: (E0 padded [N, Cp], state = state_scale * E0 or None, sum |E0| as a device scalar [1])."""
+    lib = _lib.load()
+    _lib.require_device(model_out, labels, label_rows, state_scale)
+    p = _c(model_out.float())
+    n, c = p.shape
+    cp = padded_classes(c)
+    e0 = torch.empty((n, cp), dtype=torch.float32, device=p.device)
+    state = torch.empty_like(e0) if (want_state or state_scale is not None) else None
+    abs_sum = torch.empty(1, dtype=torch.float32, device=p.device)
+    wsb = lib.cb_cs_workspace_bytes(n, cp)
+    ws = _ws(wsb, p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(lib.cb_cs_residual_init_f32(_lib.ptr(p), c, _lib.ptr(_c(labels.long().reshape(-1))), _lib.ptr(label_rows), n, c, cp, _lib.ptr(state_scale),
+                                               _lib.ptr(e0), _lib.ptr(state), _lib.ptr(abs_sum), _lib.ptr(ws), wsb, _lib.stream_ptr()),
+                   'cb_cs_residual_init_f32')
+    return e0, state, abs_sum
+
+
+def cs_correct_snap(mode, model_out, resid, labels, label_rows, abs_sum=None, n_label=0, scale=1.0, state_scale=None):
+    """The "correct" combine of `mode` (a key of CS_MODES or its number) and pre_outcome_correlation (:112-126) as one row kernel:
+    (res_result [N, C], y2 padded [N, Cp], state = state_scale * y2 or None).  `resid` is the padded result of the first propagation (None for
+    only_outcome_correlation); abs_sum the device scalar of cs_residual_init — read on the device, never on the host."""
+    lib = _lib.load()
+    mode = CS_MODES[mode] if isinstance(mode, str) else int(mode)
+    _lib.require_device(model_out, resid, labels, label_rows, abs_sum, state_scale)
+    p = _c(model_out.float())
+    n, c = p.shape
+    cp = padded_classes(c)
+    if resid is not None and (resid.dtype != torch.float32 or resid.shape[0] != n or resid.shape[1] < c or resid.stride(1) != 1):
+        raise ValueError('cs_correct_snap: resid is a float32 [N, >= C] matrix with contiguous rows')
+    res = torch.empty((n, c), dtype=torch.float32, device=p.device)
+    y2 = torch.empty((n, cp), dtype=torch.float32, device=p.device)
+    state = torch.empty_like(y2) if state_scale is not None else None
+    with torch.cuda.device(p.device):
+        _lib.check(lib.cb_cs_correct_snap_f32(mode, _lib.ptr(p), c, _lib.ptr(resid), resid.stride(0) if resid is not None else 0,
+                                              _lib.ptr(_c(labels.long().reshape(-1))), _lib.ptr(label_rows), n, c, cp, _lib.ptr(abs_sum), int(n_label),
+                                              float(scale), _lib.ptr(state_scale), _lib.ptr(res), c, _lib.ptr(y2), _lib.ptr(state), _lib.stream_ptr()),
+                   'cb_cs_correct_snap_f32')
+    return res, y2, state
+
+
+def correct_and_smooth(graph, model_out, labels, label_idx, fn, A1, alpha1, num_propagations1, A2, alpha2, num_propagations2, scale=1.0,
+                       deg_inv_sqrt=None):
+    """Correct & Smooth on the device -> (res_result, result), both [N, C].  fn names the reference function (:158-213):
+      double_correlation_autoscale   E0 = onehot - P on the label rows; resid = propagate(E0, A1, clamp(-1, 1)); res = P + autoscale * resid
+      double_correlation_fixed       resid = propagate(E0, A1, label rows fixed); res = P + scale * resid
+      only_outcome_correlation       res = P (A1 / alpha1 / num_propagations1 unused; the smoothing runs with A2 / alpha2 / num_propagations2)
+    then result = propagate(res with the label rows snapped to one-hot, A2, clamp(0, 1)).  label_idx: the label rows (residual_idx == label_idx in
+    every reference call; indices are taken as distinct).  2 row kernels + one aggregation launch per step on the graph's by-dst CSR (symmetric graph),
+    no host synchronisation between the first and the last launch.  deg_inv_sqrt defaults to the graph's in-degrees ^ -1/2 with inf -> 0 (:46-48)."""
+    if fn not in CS_MODES:
+        raise ValueError(f"correct_and_smooth: fn '{fn}' is not one of {sorted(CS_MODES)}")
+    graph = _prop_graph(graph)
+    _lib.require_device(model_out, labels, label_idx)
+    mode = CS_MODES[fn]
+    p = _c(model_out.float())
+    n = p.shape[0]
+    if deg_inv_sqrt is None:
+        deg_inv_sqrt = graph.in_degrees().to(torch.float32).pow(-0.5)
+        deg_inv_sqrt = torch.where(torch.isinf(deg_inv_sqrt), torch.zeros_like(deg_inv_sqrt), deg_inv_sqrt)
+    label_idx = torch.as_tensor(label_idx, device=p.device)
+    n_label = int(label_idx.sum().item()) if label_idx.dtype in (torch.bool, torch.uint8) else int(label_idx.numel())      # (a mask: counted before the first launch)
+    rows = rows_mask(label_idx, n, p.device)
+    R2, S2 = adj_scales(deg_inv_sqrt, A2)
+    resid = abs_sum = None
+    if mode != 2:
+        R1, S1 = adj_scales(deg_inv_sqrt, A1)
+        e0, h0, abs_sum = cs_residual_init(p, labels, rows, state_scale=S1)
+        T1 = int(num_propagations1)
+        if T1 <= 0:
+            resid = e0
+        elif mode == 0:
+            resid = _propagate_padded(graph, e0, h0 if h0 is not None else e0, R1, S1, alpha1, T1, (-1.0, 1.0), True, None)
+        else:
+            resid = _propagate_padded(graph, e0, h0 if h0 is not None else e0, R1, S1, alpha1, T1, None, True, rows)
+    res, y2, h2 = cs_correct_snap(mode, p, resid, labels, rows, abs_sum=abs_sum, n_label=n_label, scale=scale, state_scale=S2)
+    T2 = int(num_propagations2)
+    c = p.shape[1]
+    if T2 <= 0:
+        return res, y2[:, :c].contiguous()
+    out = _propagate_padded(graph, y2, h2 if h2 is not None else y2, R2, S2, alpha2, T2, (0.0, 1.0), True, None)
+    return res, (out[:, :c].contiguous() if out.shape[1] != c else out)
+
+
 def se_topk_replace(le_guess, teacher_se, k, return_selection=False):
     """`SEMLP.replacement` (MLP_model/__init__.py:143-156) for all rows of `le_guess` at once: softmax-weighted mix of the K
     teacher structural embeddings with the largest inner product.  No gradient (the reference detaches both sides)."""

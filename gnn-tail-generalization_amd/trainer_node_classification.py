@@ -5,7 +5,8 @@ eval_headtail__traintest_v2 :226-236, evaluate :672-681, cal_acc_rounded100 :683
 Same class/method names, same per-epoch record layout and return shapes; the forward/backward runs on the HIP path.
 --train_which=TeacherGNN, LP (pure label propagation), SEMLP (teacher -> best checkpoint -> collect_SE -> part 1: regression of the
 student onto the teacher's structural embeddings -> part 2: classification on [x | virtual neighbours | guess]) and StudentBaseMLP (the
-residual MLP on the features alone) are built; GraphMLP is not (MLP_model/__init__.py says why).
+residual MLP on the features alone) are built; GraphMLP is not (MLP_model/__init__.py says why).  --correct_and_smooth=1 (build extension) runs
+the reference's Correct & Smooth post-processing (Label_propagation_model) on the trained model's probabilities after any of them.
 """
 import contextlib
 import os
@@ -40,6 +41,12 @@ class trainer:
     """Loads data in __init__, trains in main() — as the reference's trainer does."""
 
     def main(self):
+        results = self._run_train_which()
+        if int(getattr(self.args, 'correct_and_smooth', 0) or 0):
+            self.correct_and_smooth()      # post-hoc: what main() returns is what it returns without the flag
+        return results
+
+    def _run_train_which(self):
         if self.args.do_deg_analyze:
             save_graph_analyze(self.args.N_nodes, self.data, self.args.use_special_split)
         if self.args.train_which in ['TeacherGNN']:
@@ -55,6 +62,56 @@ class trainer:
             return self.train_seMLP_part2()
         raise NotImplementedError(f'--train_which={self.args.train_which}: TeacherGNN, LP, SEMLP and StudentBaseMLP are built; GraphMLP needs a '
                                   'sparse adjacency power and an N_b x N_b neighbour-contrastive loss that have no kernel here')
+
+    def eval_probabilities(self):
+        """Eval-mode class probabilities of ALL nodes from the model this run trained: the student's part 2 (SEMLP / StudentBaseMLP) or the teacher."""
+        with torch.no_grad():
+            if self.args.train_which in ['SEMLP', 'StudentBaseMLP'] and getattr(self, 'seMLP', None) is not None:
+                self.seMLP.eval()
+                logits = self.seMLP.forward_part2(self.data.x, edge_index=self.data.edge_index, batch_idx=None)
+            elif getattr(self, 'teacherGNN', None) is not None:
+                self.teacherGNN.eval()
+                logits = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index).emb4classi
+            else:
+                raise ValueError(f'--train_which={self.args.train_which} leaves no trained model behind: pass model_out to correct_and_smooth()')
+            return F.softmax(logits.detach().float(), dim=1)
+
+    def correct_and_smooth(self, model_out=None):
+        """Correct & Smooth (Label_propagation_model.LPStep with args.lpStep: fn, A1 / alpha1 / num_propagations1, A2 / alpha2 / num_propagations2) applied
+        to `model_out` ([N, C] class probabilities; default: eval_probabilities()) on an undirected copy of data.edge_index — `data` is not modified.
+        Leaves the smoothed result in self.cs_out (the probabilities in self.cs_model_out), the accuracies (x100, rounded as run_pureLP's) in
+        self.bag['correct_and_smooth'], prints one line and writes wIns/Recs/<resdir>/cs_acc.npy = [train before, test before, train after, test after
+        (, head, tail(, isolated) test accuracy after: --want_headtail)].  Returns that array."""
+        from .data import Data
+        from .Label_propagation_model import LPStep
+        if model_out is None:
+            model_out = self.eval_probabilities()
+        model_out = model_out.detach().float().to(self.device)
+        data, labels = self.data, self.data.y.reshape(-1)
+        view = Data(x=data.x, y=data.y, edge_index=data.edge_index)      # process_adj rewrites edge_index of what it is given: the view's
+        masks = {'train': data.train_mask, 'valid': getattr(data, 'val_mask', None), 'test': data.test_mask}
+        step = LPStep(self.args, view, masks)
+        step.no_prep = 0
+        with torch.no_grad():
+            out = step(model_out, view)
+        self.lpStep, self.cs_model_out, self.cs_out = step, model_out, out
+        acc = [np.round(evaluate(m, labels, mask) * 100, 2) for m in (model_out, out) for mask in (data.train_mask, data.test_mask)]
+        rec = {'train_before': acc[0], 'test_before': acc[1], 'train_after': acc[2], 'test_after': acc[3], 'fn': step.fn_name}
+        if self.args.want_headtail:
+            names = ['large_deg_idx', 'small_deg_idx'] + (['zero_deg_idx'] if self.args.use_special_split else [])
+            for name, key in zip(names, ['head', 'tail', 'iso']):
+                idx = getattr(data, name)
+                idx = (idx if torch.is_tensor(idx) else torch.as_tensor(np.asarray(idx))).to(device=out.device, dtype=torch.long).reshape(-1)
+                _train, test = self.eval_headtail__traintest_v2(out[idx], labels[idx], idx, cal_acc_rounded100)
+                rec[key + '_after'] = test
+                acc.append(test)
+        _lib.device_status()
+        self.bag['correct_and_smooth'] = rec
+        arr = np.array(acc, dtype=np.float64)
+        wzRec(arr, 'cs_acc', want_save_npy=1, npy_dir=self.resdir)
+        print(f'Correct & Smooth ({step.fn_name}, {step.adj_names["A1"]}/{step.adj_names["A2"]}): train,test acc before = {acc[0]}, {acc[1]} -> after = {acc[2]}, {acc[3]}'
+              + (f', head_tail_iso after = {[float(v) for v in acc[4:]]}' if len(acc) > 4 else ''))
+        return arr
 
     def _new_student(self, teacher):
         self.seMLP = SEMLP(self.args, self.data, teacher).to(self.device)

@@ -648,6 +648,35 @@ int cb_spmm_csr_lp_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int
                        int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
                        const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
 
+/* One propagation step of general_outcome_correlation (Label_propagation_model/outcome_correlation.py:128-145) for every normalised adjacency and
+ * post-step of Correct & Smooth, next to cb_spmm_csr_lp_f32 (same kernels, same hub plan; lo = 0, hi = 1, fix_rows = NULL is that entry bit for bit):
+ *     out[v, :] = post_scale[v] * fix_v(clamp(row_scale[v] * sum_{u in row v} h[u, :] + c_mix * mix[v, :], lo, hi))      (post_scale NULL: 1)
+ * lo = -INFINITY and hi = +INFINITY: no clamp.  fix_rows (uint8 [N], one byte per row, or NULL): where the byte is non-zero the row is replaced by
+ * mix[v, :] (fix_inputs, :194-199, whose fixed values ARE the mix rows).  With A_norm = diag(R) A diag(S) — DAD: R = S = D^-1/2; DA: R = D^-1, S = 1;
+ * AD: R = 1, S = D^-1 (:51-55) — and the state s_t = S (.) result_t as h: row_scale = alpha R, c_mix = 1 - alpha (alpha_term) or 1, post_scale = S
+ * (NULL on the last step, which returns result itself).  The CSR is by destination; the graph is symmetric (to_undirected, :41). */
+int cb_spmm_csr_prop_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
+                         const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, float lo, float hi, const uint8_t* fix_rows,
+                         const float* post_scale, float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
+                         const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
+
+/* Row passes of Correct & Smooth (csrc/cb_cs.hip).  label_rows: uint8 [N], non-zero = label row (the layout of fix_rows above); labels: int64 [N];
+ * Cp >= C: the row width of the matrices the aggregation reads (padding columns are written as 0).  Workspace of the first: cb_cs_workspace_bytes.
+ *
+ * cb_cs_residual_init_f32 — pre_residual_correlation (:95-110): E0 [N, Cp] = onehot(labels) - P on the label rows, 0 elsewhere;
+ *   state [N, Cp] (may be NULL) = state_scale (.) E0 (state_scale NULL: 1); abs_sum[0] (device) = sum |E0| — two stages, fixed order, no atomics. */
+size_t cb_cs_workspace_bytes(int64_t N, int64_t Cp);
+int cb_cs_residual_init_f32(const float* P, int64_t ld_p, const int64_t* labels, const uint8_t* label_rows, int64_t N, int64_t C, int64_t Cp,
+                            const float* state_scale, float* E0, float* state, float* abs_sum, void* ws, size_t ws_bytes, void* stream);
+/* cb_cs_correct_snap_f32 — the "correct" combine and pre_outcome_correlation (:112-126) in one pass:
+ *   mode 0 (autoscale, :170-176): scale[v] = (abs_sum[0] / n_label) / sum_j |resid[v, j]|, inf -> 1, then > 1000 -> 1; res = P + scale * resid, NaN -> P
+ *   mode 1 (fixed, :200):         res = P + scale * resid                    mode 2 (only, :209): res = P (resid unused)
+ *   res_result [N, ld_res] = res; y2 [N, Cp] = res with the label rows set to onehot(labels); state [N, Cp] (may be NULL) = state_scale (.) y2.
+ * abs_sum is read on the device (what cb_cs_residual_init_f32 left there): no host synchronisation between the two. */
+int cb_cs_correct_snap_f32(int32_t mode, const float* P, int64_t ld_p, const float* resid, int64_t ld_r, const int64_t* labels,
+                           const uint8_t* label_rows, int64_t N, int64_t C, int64_t Cp, const float* abs_sum, int64_t n_label, float scale,
+                           const float* state_scale, float* res_result, int64_t ld_res, float* y2, float* state, void* stream);
+
 /* The same pack with the rows narrowed to bf16 (round-to-nearest-even) as they are written: the send buffer of the bf16 halo wire. */
 int cb_gather_rows_bf16_f32(const float* src, int64_t ld, const int64_t* idx, int64_t n_idx, int64_t d, uint16_t* out, void* stream);
 /* out[r, :] = pos[r] >= 0 ? src[pos[r], :] : fill for r < n_rows (contiguous [n, d] src and [n_rows, d] out, d % 4 == 0): a matrix over a
