@@ -19,6 +19,17 @@ _I32 = ctypes.c_int32
 _SZ = ctypes.c_size_t
 _P = ctypes.c_void_p
 
+
+class CsrView(ctypes.Structure):
+    """cb_csr_view of include/coldbrew_hip.h: one orientation's CSR, its hub plan and the workspace of the hub partial sums.  Built by
+    graph.CSRGraph._view, which also hangs the tensors behind the pointers on the instance (`_keep`) so that they live as long as it does."""
+    _fields_ = [('rowptr', _P), ('col', _P), ('col_flags', _I32), ('n_rows', _I64), ('n_edges', _I64),
+                ('hub_threshold', _I32), ('n_hubs', _I32), ('n_chunks', _I32), ('hub_rows', _P), ('hub_chunk_ptr', _P),
+                ('ws', _P), ('ws_bytes', _SZ)]
+
+
+_G = ctypes.POINTER(CsrView)
+
 # name -> (restype, argtypes); mirrors include/coldbrew_hip.h one to one
 SIGNATURES = {
     'cb_version': (ctypes.c_int, []),
@@ -36,10 +47,7 @@ SIGNATURES = {
     'cb_spmm_hub_fill_scratch_ints': (_I64, [_I64]),
     'cb_spmm_hub_fill': (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P]),
     'cb_spmm_workspace_bytes': (_SZ, [_I64, _I64]),
-    'cb_spmm_csr_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64,
-                                       _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_colscale_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64,
-                                                _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    'cb_spmm_csr_f32': (ctypes.c_int, [_G, _P, _I32, _I64, _I64, _P, _P, _P, ctypes.c_int, _P, _I64, _P, _I64, _P]),
     'cb_dropout_f32': (ctypes.c_int, [_P, _P, _I64, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P]),
     'cb_axpby_f32': (ctypes.c_int, [ctypes.c_float, _P, ctypes.c_float, _P, _P, _I64, _P]),
     'cb_colsum_workspace_bytes': (_SZ, [_I64, _I64]),
@@ -58,20 +66,11 @@ SIGNATURES = {
                                             ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _SZ, _P]),
     'cb_gemm_tn_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
     'cb_gemm_tn_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
-    'cb_spmm_csr_fused_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                             ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
-                                             _P, _SZ, _P]),
-    'cb_spmm_csr_fused_rows_f32': (ctypes.c_int, [_P, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                                  ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
-                                                  _P, _SZ, _P]),
+    'cb_spmm_csr_fused_f32': (ctypes.c_int, [_G, _P, _P, _I32, _I64, _I64, _P, _P, _P, _I64, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
+                                             _P, _I32, _P, _I64, _P, _I64, _P]),
     'cb_trunk_layer_bwd_f32': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _I64, _I64, ctypes.c_float, ctypes.c_uint64,
                                               _P, _I64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_uint64, ctypes.c_float, _P, _P, _P, _SZ, _P]),
     'cb_gemm_nn_bf16out_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, ctypes.c_int, _P, _SZ, _P]),
-    'cb_spmm_csr_bf16_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64,
-                                            _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_fused_bf16_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                                  ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P,
-                                                  _P, _P, _SZ, _P]),
     'cb_node_norm_fwd_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P]),
     'cb_node_norm_bwd_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, _P]),
     'cb_colstats_workspace_bytes': (_SZ, [_I64, _I64]),
@@ -81,16 +80,6 @@ SIGNATURES = {
     'cb_topk_replace_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
     'cb_topk_replace_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _P, _SZ, _P]),
     'cb_gather_rows_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
-    'cb_spmm_csr_acc_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P, _I64,
-                                           _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_fused_acc_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float,
-                                                 ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
-                                                 _I32, _I32, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_acc_bf16_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P, _I64,
-                                                _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_fused_acc_bf16_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float,
-                                                      ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
-                                                      _I32, _I32, _P, _P, _P, _SZ, _P]),
     'cb_gather_rows_bf16_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
     'cb_adam_norm_workspace_bytes': (ctypes.c_size_t, [_I32]),
     'cb_adam_multi_norm_f32': (ctypes.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -103,24 +92,14 @@ SIGNATURES = {
                                                ctypes.c_int, _P, _P, _P]),
     'cb_agg_gemm_image_bytes': (_SZ, [_I64, _I64]),
     'cb_agg_gemm_image_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_int, _P, _SZ, _P]),
-    'cb_spmm_gemm_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P,
-                                        _P, _SZ, _P, _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_fused_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ,
+    'cb_spmm_gemm_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P]),
+    'cb_spmm_gemm_fused_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
                                               _P, _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_fused_eval_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                                   ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ,
-                                                   _P, _P, _P, _I64, _P, _I64, _P]),
     'cb_agg_gemm_head_image_bytes': (_SZ, [_I64, _I64]),
     'cb_agg_gemm_head_image_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_int, _P, _SZ, _P]),
-    'cb_spmm_gemm_fused_head_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                                   ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ,
+    'cb_spmm_gemm_fused_head_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
                                                    _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_fused_head_eval_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float,
-                                                   ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ,
-                                                   _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_store_rows_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P,
-                                                   _P, _P, _P, _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P,
+    'cb_spmm_gemm_store_rows_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P,
                                                    _I64, _P, _I32, _P, _I64, _P, _I64, _P]),
     'cb_spmm_csr_weighted_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P]),
     'cb_spmm_edge_dot_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P]),
@@ -137,10 +116,8 @@ SIGNATURES = {
                                           ctypes.c_uint64, ctypes.c_uint64, _P, _I64, _P]),
     'cb_gemm_tn_gdrop_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64]),
     'cb_gemm_tn_gdrop_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _SZ, _P]),
-    'cb_spmm_csr_lp_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, _P, _P, _I64, _I32, _I32, _I32, _P, _P,
-                                          _P, _SZ, _P]),
-    'cb_spmm_csr_prop_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _I64,
-                                            _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    'cb_spmm_csr_lp_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, _P, _P, _I64, _P]),
+    'cb_spmm_csr_prop_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _I64, _P]),
     'cb_cs_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_cs_residual_init_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     'cb_cs_correct_snap_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, ctypes.c_float, _P, _P, _I64, _P, _P, _P]),
@@ -148,11 +125,10 @@ SIGNATURES = {
                                                     _P, _I64, _P, _P, _SZ, _P, _P, _P]),
     'cb_trunk_input_bwd_multi_cs_f32': (ctypes.c_int, [_P, ctypes.c_uint64, _I32, _P, _P, ctypes.c_float, _P, _P, _I64, _I64, ctypes.c_float,
                                                        _P, _I64, _P, _P, _SZ, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
-    'cb_spmm_csr_store_bwd_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
-                                                 _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    'cb_spmm_csr_store_bwd_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I64, _P, _I64, _P]),
     'cb_spmm_store_bwd_mix_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
-    'cb_spmm_csr_store_bwd_mix_f32': (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
-                                                     _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _SZ, _I32, _P, _P, _P, ctypes.c_float, _P, _P, _SZ, _P]),
+    'cb_spmm_csr_store_bwd_mix_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I64, _P, _I64,
+                                                     _I32, _P, _P, _P, ctypes.c_float, _P, _P, _SZ, _P]),
     'cb_gemm_tn_instage_supported': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64]),
     'cb_gemm_tn_instage_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_gemm_tn_instage_f32': (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, ctypes.c_uint64, _P, _I64,

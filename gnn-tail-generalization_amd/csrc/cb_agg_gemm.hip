@@ -422,9 +422,12 @@ static int ag_n_blocks(int n_tiles) {
 }
 
 template <bool FUSED, bool ACC>
-static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N, const float* h, int64_t ld_h, Epilogue ep, float* out,
-                           int64_t ld_out, int hub_T, int n_hubs, int n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr,
-                           float* partial, hipStream_t st, FusedEpi fe, GemmTail gt) {
+static int launch_agg_gemm(const cb_csr_view& g, const float* h, int64_t ld_h, Epilogue ep, float* out, int64_t ld_out, hipStream_t st, FusedEpi fe,
+                           GemmTail gt) {
+  const int32_t *rowptr = g.rowptr, *col = g.col, *hub_rows = g.hub_rows, *hub_chunk_ptr = g.hub_chunk_ptr;
+  const int64_t N = g.n_rows;
+  const int hub_T = g.hub_threshold, n_hubs = g.n_hubs, n_chunks = g.n_chunks;
+  float* partial = (float*)g.ws;
   const int d = kKD;
   const dim3 blk(256);
   int* err = device_error_word();
@@ -435,7 +438,7 @@ static int launch_agg_gemm(const int32_t* rowptr, const int32_t* col, int64_t N,
   if (n_hubs > 0) {      // hub rows first: the main kernel reads their finished rows back
     const int64_t ld_p = ag_partial_ld(d);
     const dim3 gridc((unsigned)((n_chunks + 3) / 4), 1);
-    if (ep.col_scale) {      // SR: the source-row factor, as cb_spmm_csr_colscale_f32's hub kernels apply it
+    if (ep.col_scale) {      // SR: the source-row factor, as cb_spmm_csr_f32's hub kernels apply it
       if (ep.col_flags)
         hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2, true>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
                            hub_chunk_ptr, partial, ld_p, ep);
@@ -512,131 +515,105 @@ extern "C" int cb_agg_gemm_image_f32(const float* W, int64_t ld, int64_t K, int6
   return CB_OK;
 }
 
-static int agg_gemm_common_checks(const char* who, int64_t N, int64_t E, int64_t d, const void* rowptr, const void* col, const void* h, int64_t ld_h,
-                                  int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const void* hub_rows, const void* hub_chunk_ptr, const void* ws,
-                                  size_t ws_bytes, const void* image, const float* g_addend, int64_t ld_add, const float* g_out, int64_t ld_gout,
-                                  const float* acc_init, int64_t ld_init) {
-  CB_CHECK_ARG(N >= 0 && E >= 0 && d == kKD, CB_E_INVALID, "%s: the fused dense part needs d == 256", who);
-  CB_CHECK_ARG(N < INT32_MAX - kTM && E < INT32_MAX, CB_E_RANGE, "%s: size exceeds the int32 contract", who);
-  if (N == 0) return CB_OK;
-  CB_CHECK_ARG(rowptr && h && image && g_out && (E == 0 || col), CB_E_INVALID, "%s: null pointer", who);
+// What every entry of this file asks beyond the graph view (check_csr_view): d == 256, room for the ragged last tile in the int32 row index, the
+// weight image and 16-byte aligned rows.  v = the checked view; an empty graph (n_rows == 0) passes and the entry returns.
+static int agg_gemm_common_checks(const char* who, const cb_csr_view* g, cb_csr_view& v, int64_t d, const void* h, int64_t ld_h, const void* image,
+                                  const float* g_addend, int64_t ld_add, const float* g_out, int64_t ld_gout, const float* acc_init, int64_t ld_init) {
+  CB_CHECK_ARG(d == kKD, CB_E_INVALID, "%s: the fused dense part needs d == 256", who);
+  const int rc = check_csr_view(who, g, d, v);
+  if (rc != CB_OK || v.n_rows == 0) return rc;
+  CB_CHECK_ARG(v.n_rows < INT32_MAX - kTM, CB_E_RANGE, "%s: size exceeds the int32 contract", who);
+  CB_CHECK_ARG(h && image && g_out, CB_E_INVALID, "%s: null pointer", who);
   CB_CHECK_ARG(ag_al16(h) && ld_h % 4 == 0 && ld_h >= d && ag_al16(image) && ag_al16(g_out) && ld_gout % 4 == 0 && ld_gout >= kND &&
                    (!g_addend || (ag_al16(g_addend) && ld_add % 4 == 0 && ld_add >= kND)) &&
                    (!acc_init || (ag_al16(acc_init) && ld_init % 4 == 0 && ld_init >= d)),
                CB_E_INVALID, "%s: 16-byte aligned rows of at least 256 floats required", who);
-  CB_CHECK_ARG(hub_T > 0 && n_hubs >= 0 && n_chunks >= 0, CB_E_INVALID, "%s: bad hub plan", who);
-  CB_CHECK_ARG(n_hubs == 0 || (hub_rows && hub_chunk_ptr && ws && ws_bytes >= (size_t)n_chunks * ag_partial_ld(d) * sizeof(float)), CB_E_WORKSPACE,
-               "%s: hub plan given but workspace missing/too small", who);
   return CB_OK;
 }
 
-// Plain aggregation (out = act(row_scale * (acc_init + sum) + bias), as cb_spmm_csr_f32 / cb_spmm_csr_acc_f32) + g_out = g_rowscale *
-// (out @ B) + g_addend, B = the 256 x 256 matrix whose fragment image cb_agg_gemm_image_f32 wrote.  acc_init (may be NULL): the partial
-// sums of the earlier passes of a node-sharded aggregation ([N, ld_init]); `out` may alias it (a row's partial sums are read before the
-// row is stored, by the same wavefront).
-extern "C" int cb_spmm_gemm_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                                int64_t d, const float* row_scale, const float* bias, int relu, const float* acc_init, int64_t ld_init, float* out,
-                                int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
-                                const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image, const float* g_rowscale,
+// Plain aggregation (out = act(row_scale * (acc_init + sum) + bias), as cb_spmm_csr_f32) + g_out = g_rowscale * (out @ B) + g_addend, B = the
+// 256 x 256 matrix whose fragment image cb_agg_gemm_image_f32 wrote.  acc_init (may be NULL): the partial sums of the earlier passes of a
+// node-sharded aggregation ([N, ld_init]); `out` may alias it (a row's partial sums are read before the row is stored, by the same wavefront).
+extern "C" int cb_spmm_gemm_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, int relu,
+                                const float* acc_init, int64_t ld_init, float* out, int64_t ld_out, const void* image, const float* g_rowscale,
                                 const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream) {
-  const int rc = agg_gemm_common_checks("cb_spmm_gemm_f32", N, E, d, rowptr, col, h, ld_h, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws,
-                                        ws_bytes, image, g_addend, ld_add, g_out, ld_gout, acc_init, ld_init);
-  if (rc != CB_OK || N == 0) return rc;
+  cb_csr_view v;
+  const int rc = agg_gemm_common_checks("cb_spmm_gemm_f32", g, v, d, h, ld_h, image, g_addend, ld_add, g_out, ld_gout, acc_init, ld_init);
+  if (rc != CB_OK || v.n_rows == 0) return rc;
   CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d, CB_E_INVALID, "cb_spmm_gemm_f32: 16-byte aligned output rows required");
-  if (n_hubs == 0) hub_T = INT32_MAX;
-  Epilogue ep{row_scale, bias, relu, acc_init, ld_init, col_flags};
+  Epilogue ep{row_scale, bias, relu, acc_init, ld_init, v.col_flags};
   GemmTail gt{(const uint4*)image, g_rowscale, g_addend, ld_add, g_out, ld_gout};
-  if (acc_init)
-    return launch_agg_gemm<false, true>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
-                                        (hipStream_t)stream, FusedEpi{}, gt);
-  return launch_agg_gemm<false, false>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
-                                       (hipStream_t)stream, FusedEpi{}, gt);
+  if (acc_init) return launch_agg_gemm<false, true>(v, h, ld_h, ep, out, ld_out, (hipStream_t)stream, FusedEpi{}, gt);
+  return launch_agg_gemm<false, false>(v, h, ld_h, ep, out, ld_out, (hipStream_t)stream, FusedEpi{}, gt);
 }
 
 // The sum-first layer of the rows-only forward (trunk.py _layer_on_rows) in one kernel: out = H = sum_u col_scale[u] * h[u] over each row's edges
-// (cb_spmm_csr_colscale_f32, stored: the backward's source-side level reads it) and, from the dense tail, the trunk's store on the node rows row_ids
+// (cb_spmm_csr_f32 with col_scale, stored: the backward's source-side level reads it) and, from the dense tail, the trunk's store on the node rows row_ids
 // of H's rows — g_out = dropout(c_act * relu(g_rowscale * (H @ B) + bias) + c_mix * mix_src[mix_index[m] | row_ids[m]]), out_act = the ReLU output,
 // relu_bits[row_ids[m]] = its mask words (cb_gemm_nn_store_rows_f32: the same values bit for bit).
-extern "C" int cb_spmm_gemm_store_rows_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                                           int64_t d, const float* col_scale, float* out, int64_t ld_out, int32_t hub_T, int32_t n_hubs, int32_t n_chunks,
-                                           const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
-                                           const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src, int64_t ld_mix,
-                                           const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev,
-                                           int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* g_out,
-                                           int64_t ld_gout, void* stream) {
-  const int rc = agg_gemm_common_checks("cb_spmm_gemm_store_rows_f32", N, E, d, rowptr, col, h, ld_h, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
-                                        ws, ws_bytes, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
-  if (rc != CB_OK || N == 0) return rc;
+extern "C" int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* col_scale, float* out, int64_t ld_out,
+                                           const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src,
+                                           int64_t ld_mix, const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed,
+                                           const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act,
+                                           int64_t ld_act, float* g_out, int64_t ld_gout, void* stream) {
+  cb_csr_view v;
+  const int rc = agg_gemm_common_checks("cb_spmm_gemm_store_rows_f32", g, v, d, h, ld_h, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
+  if (rc != CB_OK || v.n_rows == 0) return rc;
   CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids && (!mix_src || (ag_al16(mix_src) && ld_mix % 4 == 0 && ld_mix >= kND)) &&
                    (!out_act || (ag_al16(out_act) && ld_act % 4 == 0 && ld_act >= kND)) && (!relu_bits || ag_al16(relu_bits)),
                CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: null pointer or misaligned rows");
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: dropout p / row offset out of range");
-  if (n_hubs == 0) hub_T = INT32_MAX;
-  Epilogue ep{nullptr, nullptr, 0, nullptr, 0, col_flags};
+  Epilogue ep{nullptr, nullptr, 0, nullptr, 0, v.col_flags};
   ep.col_scale = col_scale;
   GemmTail gt{(const uint4*)image, g_rowscale, nullptr, 0, g_out, ld_gout};
   gt.c_act = c_act; gt.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u; gt.keep_scale = 1.f / (1.f - drop_p);
   gt.seed = seed; gt.seed_dev = seed_dev; gt.row0 = row0; gt.bias = bias;
   gt.row_ids = row_ids; gt.mix_src = mix_src; gt.ld_mix = ld_mix; gt.mix_index = mix_index; gt.c_mix = c_mix;
   gt.bits_out = (unsigned long long*)relu_bits; gt.bits_relu_only = bits_relu_only; gt.out_act = out_act; gt.ld_act = ld_act;
-  return launch_agg_gemm<false, false>(rowptr, col, N, h, ld_h, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
-                                       (hipStream_t)stream, FusedEpi{}, gt);
+  return launch_agg_gemm<false, false>(v, h, ld_h, ep, out, ld_out, (hipStream_t)stream, FusedEpi{}, gt);
 }
 
-// Fused trunk store (cb_spmm_csr_fused_f32 / cb_spmm_csr_fused_acc_f32: ReLU / mix / dropout, mask words, out_next) + g_out = g_rowscale *
-// (out_next @ B) + g_addend.
-static int spmm_gemm_fused_impl(int skip_next, const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                                int64_t E, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias,
-                                const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act,
-                                float* out_next, int64_t ld_next, int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                                size_t ws_bytes, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add,
+// Fused trunk store (cb_spmm_csr_fused_f32: ReLU / mix / dropout, mask words, out_next) + g_out = g_rowscale * (out_next @ B) + g_addend.
+// skip_next: a forward that no backward follows (evaluation / metrics passes) — the stored activations X_{l+1} have no reader, the next layer's Z
+// leaves this kernel, so the rows the persistent kernel finishes stay on chip (out_next: still the hub rows' way into the tile, contents otherwise
+// undefined; may be NULL when the plan has no hub rows).  10 GB less written per launch at the headline size.
+// n_out > 0: the narrow tail — g_out = logits [N, ld_gout >= n_out]; the common checks see a stand-in leading dimension.
+static int spmm_gemm_fused_impl(const char* who, const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
+                                const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
+                                const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
+                                int64_t ld_next, int32_t skip_next, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add,
                                 float* g_out, int64_t ld_gout, void* stream, const float* head_bias = nullptr, int n_out = 0) {
-  // (n_out > 0: the narrow tail — g_out = logits [N, ld_gout >= n_out]; the common checks see a stand-in leading dimension)
-  const int rc = agg_gemm_common_checks("cb_spmm_gemm_fused_f32", N, E, d, rowptr, col, h, ld_h, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr,
-                                        ws, ws_bytes, image, g_addend, ld_add, g_out, n_out > 0 ? kND : ld_gout, acc_init, ld_init);
-  if (rc != CB_OK || N == 0) return rc;
-  // (the evaluation form writes out_next for hub rows only: without a hub plan it may be NULL)
-  CB_CHECK_ARG((out_next || (skip_next && n_hubs == 0)) && ag_al16(out_next) && ld_next % 4 == 0 && ld_next >= d &&
+  cb_csr_view v;
+  const int rc = agg_gemm_common_checks(who, g, v, d, h, ld_h, image, g_addend, ld_add, g_out, n_out > 0 ? kND : ld_gout, acc_init, ld_init);
+  if (rc != CB_OK || v.n_rows == 0) return rc;
+  CB_CHECK_ARG((out_next || (skip_next && v.n_hubs == 0)) && ag_al16(out_next) && ld_next % 4 == 0 && ld_next >= d &&
                    (!mix_src || (ag_al16(mix_src) && ld_mix % 4 == 0)) && (!out_act || (ag_al16(out_act) && ld_act % 4 == 0 && ld_act >= d)),
-               CB_E_INVALID, "cb_spmm_gemm_fused_f32: 16-byte aligned rows required");
-  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "cb_spmm_gemm_fused_f32: dropout p out of range");
-  if (n_hubs == 0) hub_T = INT32_MAX;
-  Epilogue ep{row_scale, bias, 1, acc_init, ld_init, col_flags};
+               CB_E_INVALID, "%s: 16-byte aligned rows required", who);
+  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "%s: dropout p out of range", who);
+  Epilogue ep{row_scale, bias, 1, acc_init, ld_init, v.col_flags};
   FusedEpi fe{};
   fe.mix_src = mix_src; fe.ld_mix = ld_mix; fe.c_act = c_act; fe.c_mix = c_mix;
   fe.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
   fe.keep_scale = 1.f / (1.f - drop_p);
   fe.seed = seed; fe.seed_dev = seed_dev; fe.row0 = row0; fe.bits = (unsigned long long*)relu_bits; fe.bits_relu_only = bits_relu_only;
   fe.out_act = out_act; fe.ld_act = ld_act; fe.out_next = out_next; fe.ld_next = ld_next; fe.d = (int)d;
-  fe.skip_next = skip_next;
+  fe.skip_next = skip_next != 0;
   GemmTail gt{(const uint4*)image, g_rowscale, g_addend, ld_add, g_out, ld_gout};
   gt.bias = head_bias; gt.n_out = n_out;
-  if (acc_init)
-    return launch_agg_gemm<true, true>(rowptr, col, N, h, ld_h, ep, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
-                                       (hipStream_t)stream, fe, gt);
-  return launch_agg_gemm<true, false>(rowptr, col, N, h, ld_h, ep, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, (float*)ws,
-                                      (hipStream_t)stream, fe, gt);
+  if (acc_init) return launch_agg_gemm<true, true>(v, h, ld_h, ep, out_next, ld_next, (hipStream_t)stream, fe, gt);
+  return launch_agg_gemm<true, false>(v, h, ld_h, ep, out_next, ld_next, (hipStream_t)stream, fe, gt);
 }
 
-#define CB_SGF_PARAMS                                                                                                                              \
-  const float *acc_init, int64_t ld_init, const int32_t *rowptr, const int32_t *col, int32_t col_flags, int64_t N, int64_t E, const float *h,      \
-      int64_t ld_h, int64_t d, const float *row_scale, const float *bias, const float *mix_src, int64_t ld_mix, float c_act, float c_mix,          \
-      float drop_p, uint64_t seed, const uint64_t *seed_dev, int64_t row0, uint64_t *relu_bits, int32_t bits_relu_only, float *out_act,          \
-      int64_t ld_act, float *out_next, int64_t ld_next, int32_t hub_T,                                                                            \
-      int32_t n_hubs, int32_t n_chunks, const int32_t *hub_rows, const int32_t *hub_chunk_ptr, void *ws, size_t ws_bytes, const void *image,       \
-      const float *g_rowscale, const float *g_addend, int64_t ld_add, float *g_out, int64_t ld_gout, void *stream
-#define CB_SGF_ARGS                                                                                                                                \
-  acc_init, ld_init, rowptr, col, col_flags, N, E, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0,      \
-      relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws, ws_bytes, image, g_rowscale, g_addend, ld_add, g_out,    \
-      ld_gout, stream
-extern "C" int cb_spmm_gemm_fused_f32(CB_SGF_PARAMS) { return spmm_gemm_fused_impl(0, CB_SGF_ARGS); }
-// The same for a forward that no backward follows (evaluation / metrics passes): the stored activations X_{l+1} have no reader — the next
-// layer's Z leaves this kernel —, so the rows the persistent kernel finishes stay on chip (out_next: still the hub rows' way into the
-// tile, contents otherwise undefined; may be NULL when the plan has no hub rows).  10 GB less written per launch at the headline size.
-extern "C" int cb_spmm_gemm_fused_eval_f32(CB_SGF_PARAMS) { return spmm_gemm_fused_impl(1, CB_SGF_ARGS); }
-#undef CB_SGF_PARAMS
-#undef CB_SGF_ARGS
+extern "C" int cb_spmm_gemm_fused_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
+                                      const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
+                                      const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
+                                      int64_t ld_next, int32_t skip_next,
+                                      const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout,
+                                      void* stream) {
+  return spmm_gemm_fused_impl("cb_spmm_gemm_fused_f32", g, acc_init, ld_init, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed,
+                              seed_dev, row0, relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, skip_next, image, g_rowscale, g_addend, ld_add,
+                              g_out, ld_gout, stream);
+}
 
 // ---- the output Linear as the tail of the LAST layer's aggregation (round 5; GCN.py:133-138: Linear(dropout(X_L)) on the rows the store just made) ----
 extern "C" size_t cb_agg_gemm_head_image_bytes(int64_t K, int64_t C) {
@@ -656,31 +633,19 @@ extern "C" int cb_agg_gemm_head_image_f32(const float* W, int64_t ld, int64_t K,
   return CB_OK;
 }
 
-#define CB_SGH_PARAMS                                                                                                                              \
-  const float *acc_init, int64_t ld_init, const int32_t *rowptr, const int32_t *col, int32_t col_flags, int64_t N, int64_t E, const float *h,      \
-      int64_t ld_h, int64_t d, const float *row_scale, const float *bias, const float *mix_src, int64_t ld_mix, float c_act, float c_mix,          \
-      float drop_p, uint64_t seed, const uint64_t *seed_dev, int64_t row0, uint64_t *relu_bits, int32_t bits_relu_only, float *out_act,          \
-      int64_t ld_act, float *out_next, int64_t ld_next, int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t *hub_rows,                \
-      const int32_t *hub_chunk_ptr, void *ws, size_t ws_bytes, const void *head_image, const float *head_bias, int64_t C, float *logits,          \
-      int64_t ld_logits, void *stream
-static int spmm_gemm_head_impl(int skip_next, CB_SGH_PARAMS) {
-  CB_CHECK_ARG(C >= 1 && C <= 32 * kNTn && (N == 0 || (logits && ld_logits >= C)), CB_E_INVALID, "cb_spmm_gemm_fused_head_f32: 1 <= C <= 64 logits per row expected");
-  // (the common checks want a 256-wide 16-byte aligned tail output: the narrow tail has its own rule — any ld >= C, float4 stores where ld % 4 == 0)
-  CB_CHECK_ARG(N == 0 || ((uintptr_t)logits % 16) == 0, CB_E_INVALID, "cb_spmm_gemm_fused_head_f32: logits must be 16-byte aligned");
-  return spmm_gemm_fused_impl(skip_next, acc_init, ld_init, rowptr, col, col_flags, N, E, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed,
-                              seed_dev, row0, relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws,
-                              ws_bytes, head_image, nullptr, nullptr, 0, logits, ld_logits, stream, head_bias, (int)C);
-}
 // Fused trunk store of the LAST layer (as cb_spmm_gemm_fused_f32) + logits = out_next @ B + head_bias, B = the 256 x C matrix behind head_image.
-extern "C" int cb_spmm_gemm_fused_head_f32(CB_SGH_PARAMS) {
-  return spmm_gemm_head_impl(0, acc_init, ld_init, rowptr, col, col_flags, N, E, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0,
-                             relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws, ws_bytes, head_image,
-                             head_bias, C, logits, ld_logits, stream);
+// skip_next: the last layer's activations are not written at all (hub rows excepted), only the logits leave.
+extern "C" int cb_spmm_gemm_fused_head_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
+                                           const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
+                                           const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
+                                           int64_t ld_next, int32_t skip_next, const void* head_image, const float* head_bias, int64_t C, float* logits,
+                                           int64_t ld_logits, void* stream) {
+  const char* who = "cb_spmm_gemm_fused_head_f32";
+  const bool empty = g && g->n_rows == 0;
+  CB_CHECK_ARG(C >= 1 && C <= 32 * kNTn && (empty || (logits && ld_logits >= C)), CB_E_INVALID, "%s: 1 <= C <= 64 logits per row expected", who);
+  // (the common checks want a 256-wide 16-byte aligned tail output: the narrow tail has its own rule — any ld >= C, float4 stores where ld % 4 == 0)
+  CB_CHECK_ARG(empty || ((uintptr_t)logits % 16) == 0, CB_E_INVALID, "%s: logits must be 16-byte aligned", who);
+  return spmm_gemm_fused_impl(who, g, acc_init, ld_init, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0, relu_bits,
+                              bits_relu_only, out_act, ld_act, out_next, ld_next, skip_next, head_image, nullptr, nullptr, 0, logits, ld_logits, stream,
+                              head_bias, (int)C);
 }
-// The same for a forward that no backward follows: the last layer's activations are not written at all (hub rows excepted), only the logits leave.
-extern "C" int cb_spmm_gemm_fused_head_eval_f32(CB_SGH_PARAMS) {
-  return spmm_gemm_head_impl(1, acc_init, ld_init, rowptr, col, col_flags, N, E, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0,
-                             relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, ws, ws_bytes, head_image,
-                             head_bias, C, logits, ld_logits, stream);
-}
-#undef CB_SGH_PARAMS

@@ -47,7 +47,7 @@ const char* device_error_text() {
 }
 }  // namespace cb
 
-extern "C" int cb_version(void) { return 4; }
+extern "C" int cb_version(void) { return 5; }
 extern "C" const char* cb_last_error(void) { return cb::g_err; }
 
 // CB_OK, or CB_E_DEVICE (message through cb_last_error()) if a kernel launched by this process recorded a device-side error since the

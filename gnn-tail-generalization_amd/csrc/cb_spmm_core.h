@@ -1,6 +1,6 @@
 // Device side of the CSR sum-aggregation (design notes: cb_spmm.hip): vector helpers, the epilogues, the edge-stream walk of a
-// wavefront's row block (stream_rows), the row / hub kernels.  Shared by cb_spmm.hip (the aggregation entry points) and
-// cb_agg_gemm.hip (aggregation + next dense transform in one kernel).
+// wavefront's row block (stream_rows), the row / hub kernels — and, at the end, the one host-side check of a cb_csr_view.  Shared by
+// cb_spmm.hip (the aggregation entry points) and cb_agg_gemm.hip (aggregation + next dense transform in one kernel).
 #pragma once
 #include "cb_common.h"
 #include "cb_philox.h"
@@ -748,6 +748,25 @@ __global__ void __launch_bounds__(256) k_spmm_hub_finish(int d, int n_hubs, cons
     float rv[VEC];
     write_row<VEC>(out + (int64_t)row * ld_out + c0, acc, s, bvec, ep.relu, rv);
   }
+}
+
+// The graph side of every aggregation entry (include/coldbrew_hip.h, cb_csr_view), checked once for a call on rows of d elements: sizes, the
+// int32 index contract, null pointers, the hub plan and the workspace for its partial sums.  v = the view the launches take: a copy with
+// hub_threshold = INT32_MAX when there are no hub rows (no plan given: every row is reduced whole by one wavefront).  An empty call
+// (n_rows == 0 or d == 0) passes without a look at the pointers: the entry returns before it launches anything.
+static inline int check_csr_view(const char* who, const cb_csr_view* g, int64_t d, cb_csr_view& v) {
+  CB_CHECK_ARG(g != nullptr, CB_E_INVALID, "%s: the graph view is null", who);
+  v = *g;
+  CB_CHECK_ARG(v.n_rows >= 0 && v.n_edges >= 0 && d >= 0, CB_E_INVALID, "%s: negative size", who);
+  CB_CHECK_ARG(v.n_rows < INT32_MAX && v.n_edges < INT32_MAX && d < (1 << 20), CB_E_RANGE, "%s: size exceeds the int32 contract", who);
+  if (v.n_rows == 0 || d == 0) return CB_OK;
+  CB_CHECK_ARG(v.rowptr && (v.n_edges == 0 || v.col), CB_E_INVALID, "%s: null pointer in the graph view", who);
+  CB_CHECK_ARG(v.hub_threshold > 0 && v.n_hubs >= 0 && v.n_chunks >= 0, CB_E_INVALID, "%s: bad hub plan", who);
+  const size_t need = cb_spmm_workspace_bytes(v.n_chunks, d);
+  CB_CHECK_ARG(v.n_hubs == 0 || (v.hub_rows && v.hub_chunk_ptr && v.ws && v.ws_bytes >= need), CB_E_WORKSPACE,
+               "%s: hub plan given but workspace missing/too small (%zu < %zu)", who, v.ws_bytes, need);
+  if (v.n_hubs == 0) v.hub_threshold = INT32_MAX;
+  return CB_OK;
 }
 
 }  // namespace cb

@@ -265,20 +265,19 @@ __global__ void __launch_bounds__(256) k_small_hub_finish(int d, int n_hubs, con
 }
 
 template <int G, int VEC>
-int launch_small_t(const int32_t* rowptr, const int32_t* col, int64_t N, const float* h, int64_t ld_h, int64_t d, SmallEpi ep, float* out,
-                   int64_t ld_out, int hub_T, int n_hubs, int n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr,
-                   float* partial, int64_t ld_p, hipStream_t st) {
+int launch_small_t(const cb_csr_view& g, const float* h, int64_t ld_h, int64_t d, SmallEpi ep, float* out, int64_t ld_out, int64_t ld_p, hipStream_t st) {
   constexpr int RPW = 32, U = 4, WPB = 4;
-  const int64_t n_waves = (N + RPW - 1) / RPW;
-  hipLaunchKernelGGL((k_spmm_small<G, VEC, RPW, U>), dim3((unsigned)((n_waves + WPB - 1) / WPB)), dim3(kWave * WPB), 0, st, rowptr, col, h,
-                     ld_h, out, ld_out, (int)N, (int)d, ep, hub_T);
+  float* partial = (float*)g.ws;
+  const int64_t n_waves = (g.n_rows + RPW - 1) / RPW;
+  hipLaunchKernelGGL((k_spmm_small<G, VEC, RPW, U>), dim3((unsigned)((n_waves + WPB - 1) / WPB)), dim3(kWave * WPB), 0, st, g.rowptr, g.col, h,
+                     ld_h, out, ld_out, (int)g.n_rows, (int)d, ep, g.hub_threshold);
   CB_LAUNCH_CHECK();
-  if (n_hubs > 0) {
-    hipLaunchKernelGGL((k_small_hub_chunks<G, VEC, U>), dim3((unsigned)((n_chunks + WPB - 1) / WPB)), dim3(kWave * WPB), 0, st, rowptr,
-                       col, h, ld_h, (int)d, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, partial, ld_p);
+  if (g.n_hubs > 0) {
+    hipLaunchKernelGGL((k_small_hub_chunks<G, VEC, U>), dim3((unsigned)((g.n_chunks + WPB - 1) / WPB)), dim3(kWave * WPB), 0, st, g.rowptr,
+                       g.col, h, ld_h, (int)d, g.hub_threshold, g.n_hubs, g.n_chunks, g.hub_rows, g.hub_chunk_ptr, partial, ld_p);
     CB_LAUNCH_CHECK();
-    const int64_t work = (int64_t)n_hubs * d;
-    hipLaunchKernelGGL(k_small_hub_finish, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, (int)d, n_hubs, hub_rows, hub_chunk_ptr,
+    const int64_t work = (int64_t)g.n_hubs * d;
+    hipLaunchKernelGGL(k_small_hub_finish, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, (int)d, g.n_hubs, g.hub_rows, g.hub_chunk_ptr,
                        partial, ld_p, out, ld_out, ep);
     CB_LAUNCH_CHECK();
   }
@@ -293,11 +292,10 @@ int launch_small_t(const int32_t* rowptr, const int32_t* col, int64_t N, const f
 // 4.32 ms = 0.60 of the HBM roofline on the S 8(d) bytes; d = 64: 5.67 vs 4.32 ms), so wider rows stay on k_spmm_rows.
 bool spmm_small_eligible(int64_t d, bool /*al16*/) { return d >= 1 && d <= 16; }
 
-int launch_spmm_small(const int32_t* rowptr, const int32_t* col, int64_t N, const float* h, int64_t ld_h, int64_t d, const float* row_scale,
-                      const float* bias, int relu, float* out, int64_t ld_out, int hub_T, int n_hubs, int n_chunks,
-                      const int32_t* hub_rows, const int32_t* hub_chunk_ptr, float* partial, int64_t ld_p, bool al16, hipStream_t st) {
+int launch_spmm_small(const cb_csr_view& g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, int relu, float* out,
+                      int64_t ld_out, int64_t ld_p, bool al16, hipStream_t st) {
   SmallEpi ep{row_scale, bias, relu};
-#define CB_SMALL_ARGS rowptr, col, N, h, ld_h, d, ep, out, ld_out, hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, partial, ld_p, st
+#define CB_SMALL_ARGS g, h, ld_h, d, ep, out, ld_out, ld_p, st
   if (al16 && d > 4) return launch_small_t<4, 4>(CB_SMALL_ARGS);   // float4 lanes: 16-byte aligned rows, d in {8, 12, 16}
   if (d <= 4) return launch_small_t<4, 1>(CB_SMALL_ARGS);
   if (d <= 8) return launch_small_t<8, 1>(CB_SMALL_ARGS);

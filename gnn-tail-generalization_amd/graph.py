@@ -218,11 +218,7 @@ class CSRGraph:
         d = h.shape[1]
         g = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
         gr = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
-        plan = self._plan
-        col_k = self.flagged_cols(False, d * 4)
-        flags = int(col_k is not None and h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
-        wsb = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(wsb)
+        view = self._view(d, use_flags=h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
         prof = self.profile
         if prof is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -233,13 +229,12 @@ class CSRGraph:
                 raise ValueError('spmm_store_bwd(mix=...): at most two compact operands with position maps')
             k = len(ops_)
             colsum = torch.empty(d, dtype=torch.float32, device=h.device) if want_cs else None
-            ws2b = lib.cb_spmm_store_bwd_mix_workspace_bytes(self.N, plan.n_hubs, d) if want_cs else 0
+            ws2b = lib.cb_spmm_store_bwd_mix_workspace_bytes(self.N, self._plan.n_hubs, d) if want_cs else 0
             ws2 = torch.empty(max(ws2b, 16), dtype=torch.uint8, device=h.device) if want_cs else None
             with torch.cuda.device(h.device):
                 _lib.check(lib.cb_spmm_csr_store_bwd_mix_f32(
-                    _lib.ptr(self.rowptr), _lib.ptr(col_k if flags else self.col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d, _lib.ptr(row_scale), _lib.ptr(bits),
-                    _lib.ptr(bwd_rowscale), float(c_act), float(p), ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(g), d, _lib.ptr(gr), d, self.hub_threshold,
-                    plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), wsb, k,
+                    view, _lib.ptr(h), h.stride(0), d, _lib.ptr(row_scale), _lib.ptr(bits), _lib.ptr(bwd_rowscale), float(c_act), float(p), ctypes.c_uint64(seed),
+                    ops.seed_dev_ptr(), int(row0), _lib.ptr(g), d, _lib.ptr(gr), d, k,
                     (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in ops_]), (ctypes.c_void_p * max(k, 1))(*[q.data_ptr() for q in pos_]),
                     (ctypes.c_uint64 * max(k, 1))(*[int(s_) for s_ in seeds_]), float(c_mix), _lib.ptr(colsum), _lib.ptr(ws2), ws2b, _lib.stream_ptr()),
                     'cb_spmm_csr_store_bwd_mix_f32')
@@ -249,10 +244,8 @@ class CSRGraph:
                 prof.append(prof_rec(ev0, ev1, self, 'store_bwd', self.algorithmic_bytes(d, row_scale=row_scale is not None, bias=False), self.N * d * 4 + self.N * d // 8 + extra))
             return g, gr, colsum
         with torch.cuda.device(h.device):
-            _lib.check(lib.cb_spmm_csr_store_bwd_f32(_lib.ptr(self.rowptr), _lib.ptr(col_k if flags else self.col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
-                                                     _lib.ptr(row_scale), _lib.ptr(bits), _lib.ptr(bwd_rowscale), float(c_act), float(p), ctypes.c_uint64(seed),
-                                                     ops.seed_dev_ptr(), int(row0), _lib.ptr(g), d, _lib.ptr(gr), d, self.hub_threshold, plan.n_hubs, plan.n_chunks,
-                                                     _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), wsb, _lib.stream_ptr()),
+            _lib.check(lib.cb_spmm_csr_store_bwd_f32(view, _lib.ptr(h), h.stride(0), d, _lib.ptr(row_scale), _lib.ptr(bits), _lib.ptr(bwd_rowscale), float(c_act),
+                                                     float(p), ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(g), d, _lib.ptr(gr), d, _lib.stream_ptr()),
                        'cb_spmm_csr_store_bwd_f32')
         if prof is not None:
             ev1.record()
@@ -409,12 +402,28 @@ class CSRGraph:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def _view(self, d, transpose=False, use_flags=False, elem=4):
+        """The cb_csr_view (include/coldbrew_hip.h) of one aggregation call over rows of d elements: rowptr, column ids and hub plan of ONE
+        orientation, and the workspace of the hub partial sums sized for THIS d.  use_flags: the caller's own rule allows flagged column ids
+        for this launch (source rows of d * elem bytes) — they are used where the graph holds them.  The struct keeps the tensors it points
+        into alive (`_keep`); nothing retains it beyond the call."""
+        rowptr, col, plan = (self.rowptr_t, self.col_t, self._plan_t) if transpose else (self.rowptr, self.col, self._plan)
+        col_k = self.flagged_cols(transpose, d * elem) if use_flags else None
+        if col_k is not None:
+            col = col_k
+        ws_bytes = _lib.load().cb_spmm_workspace_bytes(plan.n_chunks, d)
+        ws = self._workspace(ws_bytes)
+        v = _lib.CsrView(rowptr.data_ptr(), col.data_ptr(), int(col_k is not None), self.N, self.E, self.hub_threshold, plan.n_hubs, plan.n_chunks,
+                         plan.hub_rows.data_ptr(), plan.hub_chunk_ptr.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes)
+        v._keep = (rowptr, col, plan, ws)
+        return v
+
     # -- the aggregation ----------------------------------------------------------------
     def spmm(self, h, transpose=False, row_scale=None, bias=None, relu=False, out=None, acc_init=None, col_scale=None):
         """out[v] = act(row_scale[v] * (acc_init[v] + sum_{u in row v} h[u]) + bias); by-dst CSR unless transpose.
         acc_init (optional, fp32 [N, d]): partial sums of an earlier pass over other columns (node-sharded path).
         col_scale (optional, fp32 [n_cols]; fp32 rows with d % 256 == 0, no bias / ReLU / acc_init): sum_u col_scale[u] * h[u]
-        (cb_spmm_csr_colscale_f32)."""
+        (cb_spmm_csr_f32's col_scale)."""
         lib = _lib.load()
         _lib.require_device(h, row_scale, bias, out, acc_init, col_scale)
         if col_scale is not None and (h.dtype != torch.float32 or h.shape[1] % 256 or bias is not None or relu or acc_init is not None
@@ -432,43 +441,21 @@ class CSRGraph:
         d = h.shape[1]
         if out is None:
             out = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
-        rowptr, col, plan = (self.rowptr_t, self.col_t, self._plan_t) if transpose else (self.rowptr, self.col, self._plan)
-        col_k = self.flagged_cols(transpose, d * h.element_size()) if d % 256 == 0 else None
-        flags = int(col_k is not None and d % 256 == 0 and h.data_ptr() % 16 == 0
-                    and out.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0 and out.stride(0) % 4 == 0)
-        if flags:
-            col = col_k
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
+        if acc_init is not None and (acc_init.dtype != torch.float32 or acc_init.shape != (self.N, d) or acc_init.stride(1) != 1):
+            raise ValueError('acc_init must be a float32 [N, d] matrix with contiguous rows')
+        view = self._view(d, transpose, use_flags=(d % 256 == 0 and h.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+                                                    and h.stride(0) % 4 == 0 and out.stride(0) % 4 == 0), elem=h.element_size())
         ld_h = h.stride(0) if h.shape[0] > 1 else d
         ld_o = out.stride(0) if out.shape[0] > 1 else d
+        ld_i = 0 if acc_init is None else acc_init.stride(0) if self.N > 1 else d
         prof = self.profile
         if prof is not None:   # HIP events on the stream the kernels are launched on
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        fn = lib.cb_spmm_csr_bf16_f32 if bf16 else lib.cb_spmm_csr_f32
         with torch.cuda.device(h.device):
-            if acc_init is not None:
-                if acc_init.dtype != torch.float32 or acc_init.shape != (self.N, d) or acc_init.stride(1) != 1:
-                    raise ValueError('acc_init must be a float32 [N, d] matrix with contiguous rows')
-                _lib.check((lib.cb_spmm_csr_acc_bf16_f32 if bf16 else lib.cb_spmm_csr_acc_f32)(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), ld_h, d,
-                                                   _lib.ptr(row_scale), _lib.ptr(bias), int(bool(relu)), _lib.ptr(acc_init),
-                                                   acc_init.stride(0) if self.N > 1 else d, _lib.ptr(out), ld_o,
-                                                   self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows),
-                                                   _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
-                           'cb_spmm_csr_acc_f32')
-            elif col_scale is not None:
-                _lib.check(lib.cb_spmm_csr_colscale_f32(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), ld_h, d,
-                                                        _lib.ptr(col_scale.contiguous()), _lib.ptr(row_scale), _lib.ptr(out), ld_o,
-                                                        self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows),
-                                                        _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
-                           'cb_spmm_csr_colscale_f32')
-            else:
-                _lib.check(fn(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), ld_h, d,
-                              _lib.ptr(row_scale), _lib.ptr(bias), int(bool(relu)), _lib.ptr(out), ld_o,
-                              self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows),
-                              _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
-                           'cb_spmm_csr')
+            _lib.check(lib.cb_spmm_csr_f32(view, _lib.ptr(h), int(bf16), ld_h, d, _lib.ptr(None if col_scale is None else col_scale.contiguous()),
+                                           _lib.ptr(row_scale), _lib.ptr(bias), int(bool(relu)), _lib.ptr(acc_init), ld_i, _lib.ptr(out), ld_o,
+                                           _lib.stream_ptr()), 'cb_spmm_csr_f32')
         if prof is not None:
             ev1.record()
             prof.append(prof_rec(ev0, ev1, self, 'colscale' if col_scale is not None else 'plain',
@@ -487,15 +474,10 @@ class CSRGraph:
         d = h.shape[1]
         if out is None:
             out = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
-        plan = self._plan
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
         with torch.cuda.device(h.device):
-            _lib.check(lib.cb_spmm_csr_lp_f32(_lib.ptr(self.rowptr), _lib.ptr(self.col), self.N, self.E, _lib.ptr(h), h.stride(0) if h.shape[0] > 1 else d,
-                                              d, _lib.ptr(row_scale), _lib.ptr(mix), mix.stride(0) if self.N > 1 else d, float(c_mix),
-                                              _lib.ptr(post_scale), _lib.ptr(out), out.stride(0) if self.N > 1 else d, self.hub_threshold, plan.n_hubs,
-                                              plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes,
-                                              _lib.stream_ptr()), 'cb_spmm_csr_lp_f32')
+            _lib.check(lib.cb_spmm_csr_lp_f32(self._view(d), _lib.ptr(h), h.stride(0) if h.shape[0] > 1 else d, d, _lib.ptr(row_scale), _lib.ptr(mix),
+                                              mix.stride(0) if self.N > 1 else d, float(c_mix), _lib.ptr(post_scale), _lib.ptr(out),
+                                              out.stride(0) if self.N > 1 else d, _lib.stream_ptr()), 'cb_spmm_csr_lp_f32')
         return out
 
     def spmm_prop(self, h, row_scale, mix, c_mix, clamp=None, fix_rows=None, post_scale=None, out=None):
@@ -518,15 +500,10 @@ class CSRGraph:
         d = h.shape[1]
         if out is None:
             out = torch.empty((self.N, d), dtype=torch.float32, device=h.device)
-        plan = self._plan
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
         with torch.cuda.device(h.device):
-            _lib.check(lib.cb_spmm_csr_prop_f32(_lib.ptr(self.rowptr), _lib.ptr(self.col), self.N, self.E, _lib.ptr(h), h.stride(0) if h.shape[0] > 1 else d,
-                                                d, _lib.ptr(row_scale), _lib.ptr(mix), mix.stride(0) if self.N > 1 else d, float(c_mix), lo, hi,
-                                                _lib.ptr(fix_rows), _lib.ptr(post_scale), _lib.ptr(out), out.stride(0) if self.N > 1 else d,
-                                                self.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr),
-                                                _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), 'cb_spmm_csr_prop_f32')
+            _lib.check(lib.cb_spmm_csr_prop_f32(self._view(d), _lib.ptr(h), h.stride(0) if h.shape[0] > 1 else d, d, _lib.ptr(row_scale), _lib.ptr(mix),
+                                                mix.stride(0) if self.N > 1 else d, float(c_mix), lo, hi, _lib.ptr(fix_rows), _lib.ptr(post_scale),
+                                                _lib.ptr(out), out.stride(0) if self.N > 1 else d, _lib.stream_ptr()), 'cb_spmm_csr_prop_f32')
         return out
 
     def edge_perm(self, transpose=False):
@@ -593,13 +570,7 @@ class CSRGraph:
             raise ValueError('this graph holds the forward orientation only')
         out = self._acc_out(acc_init, d, h.device)
         g_out = torch.empty((self.N, 256), dtype=torch.float32, device=h.device)
-        rowptr, col, plan = (self.rowptr_t, self.col_t, self._plan_t) if transpose else (self.rowptr, self.col, self._plan)
-        col_k = self.flagged_cols(transpose, d * 4)
-        flags = int(col_k is not None and h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
-        if flags:
-            col = col_k
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
+        view = self._view(d, transpose, use_flags=h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
         prof = self.profile
         if prof is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -607,11 +578,8 @@ class CSRGraph:
         if g_addend is not None and g_addend.stride(1) != 1:
             g_addend = g_addend.contiguous()
         with torch.cuda.device(h.device):
-            _lib.check(lib.cb_spmm_gemm_f32(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
-                                            _lib.ptr(row_scale), _lib.ptr(bias), int(bool(relu)), _lib.ptr(acc_init),
-                                            acc_init.stride(0) if acc_init is not None else 0, _lib.ptr(out), d, self.hub_threshold,
-                                            plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws),
-                                            ws_bytes, _lib.ptr(image), _lib.ptr(g_rowscale), _lib.ptr(g_addend),
+            _lib.check(lib.cb_spmm_gemm_f32(view, _lib.ptr(h), h.stride(0), d, _lib.ptr(row_scale), _lib.ptr(bias), int(bool(relu)), _lib.ptr(acc_init),
+                                            acc_init.stride(0) if acc_init is not None else 0, _lib.ptr(out), d, _lib.ptr(image), _lib.ptr(g_rowscale), _lib.ptr(g_addend),
                                             g_addend.stride(0) if g_addend is not None else 0, _lib.ptr(g_out), 256, _lib.stream_ptr()),
                        'cb_spmm_gemm_f32')
         if prof is not None:
@@ -646,19 +614,13 @@ class CSRGraph:
         out = torch.empty((self.N, d), dtype=torch.float32, device=dev)
         g_out = torch.empty((self.N, 256), dtype=torch.float32, device=dev)
         act = torch.empty_like(g_out) if want_act else None
-        col_k = self.flagged_cols(False, d * 4)
-        flags = int(col_k is not None and h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
-        rowptr, col, plan = self.rowptr, col_k if flags else self.col, self._plan
-        ws_bytes = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-        ws = self._workspace(ws_bytes)
+        view = self._view(d, use_flags=h.data_ptr() % 16 == 0 and h.stride(0) % 4 == 0)
         prof = self.profile
         if prof is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         with torch.cuda.device(dev):
-            _lib.check(lib.cb_spmm_gemm_store_rows_f32(_lib.ptr(rowptr), _lib.ptr(col), flags, self.N, self.E, _lib.ptr(h), h.stride(0), d,
-                                                       _lib.ptr(col_scale.contiguous()), _lib.ptr(out), d, self.hub_threshold, plan.n_hubs, plan.n_chunks,
-                                                       _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), ws_bytes, _lib.ptr(image),
+            _lib.check(lib.cb_spmm_gemm_store_rows_f32(view, _lib.ptr(h), h.stride(0), d, _lib.ptr(col_scale.contiguous()), _lib.ptr(out), d, _lib.ptr(image),
                                                        _lib.ptr(rowscale), _lib.ptr(bias), _lib.ptr(row_ids), _lib.ptr(mix),
                                                        mix.stride(0) if mix is not None else 0, _lib.ptr(mix_index), float(c_act), float(c_mix), float(p),
                                                        ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(bits), int(bool(relu_only)),

@@ -58,7 +58,7 @@ def _fused_spmm(graph, z, bias, x0, c_act, c_mix, p, seed, want_act=False, produ
     the exchange runs as the sliced pipeline of dist.ShardedGraph (produce(k, r0, r1), if given, fills rows [r0, r1) of z — the
     row-chunked layer GEMM — right before slice k is packed and sent); the interior-column pass (plain kernel, raw sums) and
     the halo passes of the earlier slices run while the later slices travel, the fused store is the last slice's pass
-    (cb_spmm_csr_fused_acc_f32 / _bf16_f32 when the halo rows crossed the links as bf16)."""
+    (cb_spmm_csr_fused_f32 with acc_init; over bf16 rows when the halo rows crossed the links as bf16)."""
     lib = _lib.load()
     sh = graph if hasattr(graph, 'part') else None
     if sh is not None and sh.overlap and z.dtype == torch.float32:
@@ -77,41 +77,32 @@ def _fused_gemm_launch(graph, z, bias, x0, c_act, c_mix, p, seed, image, g_rowsc
     """(bits, out_next, z_next[, act]) of cb_spmm_gemm_fused_f32: the fused trunk store of layer l and Z_{l+1} = g_rowscale * (out_next @ W_{l+1})
     + g_addend from one kernel (d = 256, fp32 rows).  g: the CSR to run on (default: the graph itself; node-sharded: the last halo slice,
     z = its receive buffer) with acc = the running sums of the earlier passes.  want_bits=False (a forward that no backward follows):
-    cb_spmm_gemm_fused_eval_f32 — no mask words, and out_next is not written either (it has no reader: returned as None).  want_act: a
+    the entry's skip_next — no mask words, and out_next is not written either (it has no reader: returned as None).  want_act: a
     fourth result, the ReLU output A_l itself (the next 'Residual' layer's mix source); relu_only: mask words of A_l > 0 alone.
     head = (b_out, C) (the LAST layer; image = graph.head_image(w_out)): the tail is the output Linear — the third result is the logits [N, C]
     (cb_spmm_gemm_fused_head_f32, GCN.py:133-138), g_rowscale / g_addend are ignored."""
     lib = _lib.load()
     g = graph if g is None else g
-    if head is not None:
-        fn = lib.cb_spmm_gemm_fused_head_f32 if want_bits else lib.cb_spmm_gemm_fused_head_eval_f32
-    else:
-        fn = lib.cb_spmm_gemm_fused_f32 if want_bits else lib.cb_spmm_gemm_fused_eval_f32
+    fn = lib.cb_spmm_gemm_fused_head_f32 if head is not None else lib.cb_spmm_gemm_fused_f32
     n, d = g.N, z.shape[1]
     dev = z.device
     bits = torch.empty((n, d // 256, 4), dtype=torch.int64, device=dev) if want_bits else None
-    plan = g._plan
     # (the evaluation form keeps the finished rows on chip: X_{l+1} goes to memory only as the hub rows' way into the tile)
-    out_next = torch.empty((n, d), dtype=torch.float32, device=dev) if (want_bits or plan.n_hubs > 0) else None
+    out_next = torch.empty((n, d), dtype=torch.float32, device=dev) if (want_bits or g._plan.n_hubs > 0) else None
     z_next = _exchanged(graph, n) if head is None else torch.empty((n, int(head[1])), dtype=torch.float32, device=dev)     # (Z_{l+1}: the next aggregation exchanges it | the logits)
     act = torch.empty((n, d), dtype=torch.float32, device=dev) if want_act else None
-    wsb = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-    ws = g._workspace(wsb)
     prof = getattr(graph, 'profile', None)
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    col_k = g.flagged_cols(False, d * 4)
     if g_addend is not None and g_addend.stride(1) != 1:
         g_addend = g_addend.contiguous()
     with torch.cuda.device(dev):
-        _lib.check(fn(_lib.ptr(acc), acc.stride(0) if acc is not None else 0, _lib.ptr(g.rowptr),
-                      _lib.ptr(col_k if col_k is not None else g.col), int(col_k is not None), n, g.E,
+        _lib.check(fn(g._view(d, use_flags=True), _lib.ptr(acc), acc.stride(0) if acc is not None else 0,
                       _lib.ptr(z), z.stride(0), d, _lib.ptr(graph.norm_in), _lib.ptr(bias), _lib.ptr(x0),
                       x0.stride(0) if x0 is not None else 0, float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed),
                       ops.seed_dev_ptr(), int(getattr(graph, 'row_offset', 0)), _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(act), d,
-                      _lib.ptr(out_next), d, g.hub_threshold, plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr),
-                      _lib.ptr(ws), wsb, _lib.ptr(image),
+                      _lib.ptr(out_next), d, int(not want_bits), _lib.ptr(image),
                       *((_lib.ptr(head[0]), int(head[1])) if head is not None
                         else (_lib.ptr(g_rowscale), _lib.ptr(g_addend), g_addend.stride(0) if g_addend is not None else 0)),
                       _lib.ptr(z_next), z_next.stride(0), _lib.stream_ptr()),
@@ -170,37 +161,24 @@ def agg_gemm_eligible(graph, hidden, agg_bf16):
 def _fused_launch(lib, graph, g, z, acc, bias, x0, c_act, c_mix, p, seed, want_act, want_bits=True, relu_only=False, row_ids=None, row_scale=None):
     """One fused-store launch over CSR g (the whole graph, a rank's single-pass block, or the last halo slice on top of acc).
     want_bits=False (forward without a backward: eval / metrics forwards): the backward's mask words are not written.
-    row_ids (int32 [g.N], with row_scale = norm_in on those rows): g's rows are a subset of the node rows (cb_spmm_csr_fused_rows_f32) — out_next is
+    row_ids (int32 [g.N], with row_scale = norm_in on those rows): g's rows are a subset of the node rows (the entry's row_ids) — out_next is
     compact, x0 / the mask words / the dropout mask are taken at the node row (the mask words of the other rows are not written)."""
     n, d = g.N, z.shape[1]
     dev = z.device
     bits = torch.empty((n if row_ids is None else graph.N, d // 256, 4), dtype=torch.int64, device=dev) if want_bits else None
     out_next = torch.empty((n, d), dtype=torch.float32, device=dev)
     act = torch.empty((n, d), dtype=torch.float32, device=dev) if want_act else None
-    plan = g._plan
-    wsb = lib.cb_spmm_workspace_bytes(plan.n_chunks, d)
-    ws = g._workspace(wsb)
     prof = getattr(graph, 'profile', None)
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
     bf16 = z.dtype == torch.bfloat16
-    col_k = g.flagged_cols(False, d * z.element_size()) if hasattr(g, 'flagged_cols') else None
-    head = (_lib.ptr(g.rowptr), _lib.ptr(col_k if col_k is not None else g.col), int(col_k is not None))
-    args = head + (n, g.E, _lib.ptr(z), z.stride(0), d, _lib.ptr(graph.norm_in if row_scale is None else row_scale), _lib.ptr(bias),
-            _lib.ptr(x0), x0.stride(0) if x0 is not None else 0, float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed),
-            ops.seed_dev_ptr(), int(getattr(graph, 'row_offset', 0)), _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(act), d, _lib.ptr(out_next), d,
-            g.hub_threshold,
-            plan.n_hubs, plan.n_chunks, _lib.ptr(plan.hub_rows), _lib.ptr(plan.hub_chunk_ptr), _lib.ptr(ws), wsb, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if row_ids is not None:
-            _lib.check(lib.cb_spmm_csr_fused_rows_f32(_lib.ptr(row_ids), *args), 'cb_spmm_csr_fused_rows_f32')
-        elif acc is not None:
-            fn = lib.cb_spmm_csr_fused_acc_bf16_f32 if bf16 else lib.cb_spmm_csr_fused_acc_f32
-            _lib.check(fn(_lib.ptr(acc), d, *args), 'cb_spmm_csr_fused_acc_f32')
-        else:
-            fn = lib.cb_spmm_csr_fused_bf16_f32 if bf16 else lib.cb_spmm_csr_fused_f32
-            _lib.check(fn(*args), 'cb_spmm_csr_fused_f32')
+        _lib.check(lib.cb_spmm_csr_fused_f32(g._view(d, use_flags=True, elem=z.element_size()), _lib.ptr(row_ids), _lib.ptr(z), int(bf16), z.stride(0), d,
+                                             _lib.ptr(graph.norm_in if row_scale is None else row_scale), _lib.ptr(bias), _lib.ptr(acc), d if acc is not None else 0,
+                                             _lib.ptr(x0), x0.stride(0) if x0 is not None else 0, float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed),
+                                             ops.seed_dev_ptr(), int(getattr(graph, 'row_offset', 0)), _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(act), d,
+                                             _lib.ptr(out_next), d, _lib.stream_ptr()), 'cb_spmm_csr_fused_f32')
     if prof is not None:
         ev1.record()
         # SURVEY §8(d) bytes of the aggregation; the fused store's own streams (mixed-in row read + mask bits) are kept apart

@@ -109,40 +109,54 @@ int cb_spmm_hub_fill(const int32_t* rowptr, int64_t N, int32_t hub_threshold, in
                      int32_t* hub_rows, int32_t* hub_chunk_ptr, int32_t* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The graph side of every aggregation call: one orientation's CSR, its hub plan and the workspace for the hub partial sums.
+ * A HOST struct, passed by pointer and read during the call only (nothing retains it); the pointers inside are device pointers.
+ * rowptr [n_rows + 1] / col [n_edges]: row v lists the rows that are summed into output row v.
+ * hub_threshold / n_hubs / n_chunks / hub_rows / hub_chunk_ptr: the plan of cb_spmm_hub_count / cb_spmm_hub_fill above, made with this
+ * rowptr and this hub_threshold.  With n_hubs == 0 (no plan) every row is reduced whole by one wavefront — correct for any graph, slow
+ * for power-law hubs — and hub_rows / hub_chunk_ptr / ws may be NULL.
+ * ws holds the hub partial sums: ws_bytes >= cb_spmm_workspace_bytes(n_chunks, d) for the d of the call.
+ * col_flags = 0: `col` holds plain column ids.  col_flags = 1 (d % 256 == 0, fp32 rows 16-byte / bf16 rows 8-byte aligned only): bit 31 of
+ * every id marks a HOT source row (one of the most-referenced rows, chosen at graph build so that together they fit the 256 MiB
+ * Infinity Cache); hot rows are gathered with the default cache policy, all others with the streaming (nt) policy, which
+ * keeps the re-used rows resident instead of letting 1e8 single-use 1 KiB rows evict them (-11 % per launch on the
+ * 10M-node power-law graph, profiles/r02_spmm_gather_policy.md).  Results do not depend on the flags.  cb_spmm_csr_lp_f32 and
+ * cb_spmm_csr_prop_f32 (narrow rows) take plain ids only.
+ * ---------------------------------------------------------------------------------- */
+typedef struct cb_csr_view {
+  const int32_t* rowptr; const int32_t* col; int32_t col_flags;
+  int64_t n_rows, n_edges;
+  int32_t hub_threshold, n_hubs, n_chunks;
+  const int32_t* hub_rows; const int32_t* hub_chunk_ptr;
+  void* ws; size_t ws_bytes;
+} cb_csr_view;
+size_t cb_spmm_workspace_bytes(int64_t n_chunks, int64_t d);
+
+/* ------------------------------------------------------------------------------------
  * Sum aggregation — replaces `graph.update_all(fn.copy_src('h','m'), fn.sum('m','h'))`
  * (GCN.py:198,238: DGL gspmm copy_lhs/sum) with the post-scale, bias (GCN.py:242-253) and
  * the ReLU that follows it in TricksComb.forward (GCN.py:127-128) fused as an epilogue:
  *
- *     out[v, :] = act( row_scale[v] * sum_{j in [rowptr[v], rowptr[v+1])} h[col[j], :] + bias[:] )
+ *     out[v, :] = act( row_scale[v] * (acc_init[v, :] + sum_{j in [rowptr[v], rowptr[v+1])} col_scale[col[j]] * h[col[j], :]) + bias[:] )
  *
- * row_scale / bias may be NULL (factor 1 / no bias); relu = 0/1.  Called with the by-dst
- * CSR for the forward and with the by-src CSR (no epilogue) for the backward
- * (autograd of gspmm = SpMM on the reverse graph).
- * `ws` holds the hub partial sums: cb_spmm_workspace_bytes(n_chunks, d).  With n_hubs == 0 (no plan) every
- * row is reduced whole by one wavefront — correct for any graph, slow for power-law hubs.
+ * row_scale / bias / col_scale / acc_init may be NULL (factor 1 / no bias / factor 1 / sums start from 0); relu = 0/1.  Called with the
+ * by-dst CSR for the forward and with the by-src CSR (no epilogue) for the backward (autograd of gspmm = SpMM on the reverse graph).
  * Deterministic: every row is reduced in CSR order by one wavefront, hub rows in chunk order.
- * col_flags = 0: `col` holds plain column ids.  col_flags = 1 (fp32 rows, d % 256 == 0, 16-byte aligned only): bit 31 of every
- * id marks a HOT source row (one of the most-referenced rows, chosen at graph build so that together they fit the 256 MiB
- * Infinity Cache); hot rows are gathered with the default cache policy, all others with the streaming (nt) policy, which
- * keeps the re-used rows resident instead of letting 1e8 single-use 1 KiB rows evict them (-11 % per launch on the
- * 10M-node power-law graph, profiles/r02_spmm_gather_policy.md).  Results do not depend on the flags.
+ * h_bf16 != 0: h holds bf16-stored rows (uint16_t, round-to-nearest-even; ld_h in bf16 elements, 8-byte aligned for the vector paths) —
+ * the gathered rows (Z in the forward, b*dY' in the backward; the halo rows of the bf16 wire, COLDBREW_HALO_WIRE=bf16) take half the
+ * traffic, accumulation and outputs stay fp32 (build extension = BASELINE config 2; the reference is fp32-only).
+ * col_scale ([number of columns]; fp32 rows, d % 256 == 0, 16-byte aligned, no acc_init / bias / ReLU): a factor per SOURCE row, applied
+ * as the row is gathered.  New: the row-sparse backward takes A (a * X_l) on the loss rows with it, i.e. the weight gradient
+ * X_l^T (a * A^T dY) of GCN.py:213,238 contracted over the loss rows as ((A (a * X_l))[S_0])^T dY[S_0] — without a scaled copy of X_l.
+ * acc_init ([n_rows, ld_init] fp32, read once, may alias out): the node-sharded aggregation in passes (new; the reference is
+ * single-device).  A rank's row block of the CSR is split by column owner: the interior-column pass (no epilogue) runs
+ * while the halo rows travel over xGMI; the halo-column pass starts from those raw sums and applies the epilogue once.  A raw in-place
+ * pass — acc_init == out, no row scale / bias / ReLU: the intermediate halo slices — neither reads nor writes rows that have no edge
+ * in this CSR.
  * ---------------------------------------------------------------------------------- */
-size_t cb_spmm_workspace_bytes(int64_t n_chunks, int64_t d);
-int cb_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E,
-                    const float* h, int64_t ld_h, int64_t d,
-                    const float* row_scale, const float* bias, int relu,
-                    float* out, int64_t ld_out,
-                    int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                    const int32_t* hub_rows, const int32_t* hub_chunk_ptr,
-                    void* ws, size_t ws_bytes, void* stream);
-/* out[v, :] = row_scale[v] * sum_{u in row v} col_scale[u] * h[u, :] — a factor per SOURCE row, applied as the row is gathered
- * (fp32 rows, d % 256 == 0, 16-byte aligned; col_scale: [number of columns]).  New: the row-sparse backward takes A (a * X_l) on the
- * loss rows with it, i.e. the weight gradient X_l^T (a * A^T dY) of GCN.py:213,238 contracted over the loss rows as
- * ((A (a * X_l))[S_0])^T dY[S_0] — without a scaled copy of X_l (trunk.py). */
-int cb_spmm_csr_colscale_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E,
-                             const float* h, int64_t ld_h, int64_t d, const float* col_scale, const float* row_scale,
-                             float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                             const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
+int cb_spmm_csr_f32(const cb_csr_view* g, const void* h, int32_t h_bf16, int64_t ld_h, int64_t d, const float* col_scale,
+                    const float* row_scale, const float* bias, int relu, const float* acc_init, int64_t ld_init,
+                    float* out, int64_t ld_out, void* stream);
 
 
 /* ------------------------------------------------------------------------------------
@@ -260,13 +274,16 @@ int cb_gemm_tn_f32(const float* A, int64_t lda, const float* G, int64_t ldg, con
  * alone (the 'Residual' connection, res_tricks.py:7-14: layer l+1's mix sends a second gradient through this ReLU under ANOTHER dropout mask —
  * the backward kernels regenerate the keep masks anyway); out_act (nullable) the activation itself (the mix source of the next 'Residual' layer).  d must be a multiple of 256; rows 16-byte aligned.  row0 = global index
  * of local row 0 (dropout mask of the unsharded tensor).  mix_src NULL: no mix; drop_p 0: no dropout.
+ * h_bf16 / acc_init ([n_rows, ld_init], 16-byte aligned rows; NULL: none) as in cb_spmm_csr_f32: bf16-stored source rows, and the fused store as
+ * the LAST pass of a node-sharded aggregation on top of the running sums.
+ * row_ids (int32 [n_rows], ascending; NULL: none; fp32 rows, no acc_init): the CSR's rows are a SUBSET of the node rows — row r of rowptr / row_scale /
+ * out_act / out_next is node row row_ids[r]; mix_src, relu_bits ([all node rows][d/256][4]) and the dropout mask are taken at the node row.  The
+ * rows-only training forward (trunk.py): a GCNConv + store (GCN.py:205-256,127-133) evaluated only on the rows the layers above read.
  * ---------------------------------------------------------------------------------- */
-int cb_spmm_csr_fused_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                          int64_t d,
-                          const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act,
-                          float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits,
-                          int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next, int32_t hub_threshold, int32_t n_hubs,
-                          int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes,
+int cb_spmm_csr_fused_f32(const cb_csr_view* g, const int32_t* row_ids, const void* h, int32_t h_bf16, int64_t ld_h, int64_t d,
+                          const float* row_scale, const float* bias, const float* acc_init, int64_t ld_init, const float* mix_src,
+                          int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
+                          uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
                           void* stream);
 
 /* Backward of that epilogue in one pass over contiguous [rows, d]:
@@ -334,11 +351,9 @@ int cb_trunk_input_bwd_multi_cs_f32(const float* g, uint64_t seed, int32_t n_mix
  *   out_gr = bwd_rowscale[v] * c_act * dropout_bwd_seed(g) where relu_bits (READ: the forward store's mask words) has the element's bit, else 0
  * = cb_spmm_csr_f32 followed by cb_trunk_layer_bwd_f32 (gx0 = NULL, no second gradient) without that pass's read of g; values bit-identical.  The
  * pass's column sums (the bias gradient) come from cb_trunk_input_bwd_multi_cs_f32.  d % 256 == 0, fp32 rows, 16-byte aligned. */
-int cb_spmm_csr_store_bwd_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                              int64_t d, const float* row_scale, const uint64_t* relu_bits, const float* bwd_rowscale, float c_act, float drop_p,
-                              uint64_t seed, const uint64_t* seed_dev, int64_t row0, float* out_g, int64_t ld_g, float* out_gr, int64_t ld_gr,
-                              int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                              size_t ws_bytes, void* stream);
+int cb_spmm_csr_store_bwd_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const uint64_t* relu_bits,
+                              const float* bwd_rowscale, float c_act, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
+                              float* out_g, int64_t ld_g, float* out_gr, int64_t ld_gr, void* stream);
 /* The same on ALL node rows, with the mix gradients FOLDED (round 6): the first output is not the raw g but everything this store and the layers above
  * send to X0 through their residual mixes (InitialConnection, res_tricks.py:19-23: X = (1 - alpha) X_l + alpha X_0, each under its own store's dropout
  * GCN.py:110,133):
@@ -347,33 +362,17 @@ int cb_spmm_csr_store_bwd_f32(const int32_t* rowptr, const int32_t* col, int32_t
  * column sums of out_gr / bwd_rowscale: the bias gradient (GCN.py:253) of the store whose backward this is; ws2 = cb_spmm_store_bwd_mix_workspace_bytes.
  * The input stage then reads ONE [N, d] matrix beside dL/d dropout(X0): cb_gemm_tn_instage_f32. */
 size_t cb_spmm_store_bwd_mix_workspace_bytes(int64_t N, int64_t n_hubs, int64_t d);
-int cb_spmm_csr_store_bwd_mix_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                                  int64_t d, const float* row_scale, const uint64_t* relu_bits, const float* bwd_rowscale, float c_act, float drop_p,
-                                  uint64_t seed, const uint64_t* seed_dev, int64_t row0, float* out_m, int64_t ld_m, float* out_gr, int64_t ld_gr,
-                                  int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                                  size_t ws_bytes, int32_t n_mix, const float* const* mix_g, const int32_t* const* mix_pos, const uint64_t* mix_seeds,
-                                  float c_mix, float* colsum, void* ws2, size_t ws2_bytes, void* stream);
+int cb_spmm_csr_store_bwd_mix_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const uint64_t* relu_bits,
+                                  const float* bwd_rowscale, float c_act, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
+                                  float* out_m, int64_t ld_m, float* out_gr, int64_t ld_gr, int32_t n_mix, const float* const* mix_g,
+                                  const int32_t* const* mix_pos, const uint64_t* mix_seeds, float c_mix, float* colsum, void* ws2, size_t ws2_bytes,
+                                  void* stream);
 
-/* ------------------------------------------------------------------------------------
- * bf16-storage variant of the aggregation (build extension = BASELINE config 2; the reference is fp32-only):
- * the rows that are gathered (Z in the forward, b*dY' in the backward) are stored as bf16 (round-to-nearest-
- * even), accumulation, outputs and everything else stay fp32.  Halves the dominant gather traffic.
- * Same semantics and arguments as cb_gemm_nn_f32 / cb_spmm_csr_f32 / cb_spmm_csr_fused_f32 otherwise
- * (ld in elements of the respective type; bf16 rows must be 8-byte aligned for the vector paths).
- * ---------------------------------------------------------------------------------- */
+/* bf16-storage variant of the dense transform in front of the aggregation (build extension = BASELINE config 2; the reference is fp32-only):
+ * C is stored as bf16 (round-to-nearest-even) for cb_spmm_csr_f32 / cb_spmm_csr_fused_f32 with h_bf16; everything else as cb_gemm_nn_f32. */
 int cb_gemm_nn_bf16out_f32(const float* A, int64_t lda, const float* B, int64_t ldb, uint16_t* C, int64_t ldc, int64_t M, int64_t N,
                            int64_t K, const float* rowscale, const float* addend, int64_t ld_add, const float* bias, int relu,
                            void* ws, size_t ws_bytes, void* stream);
-int cb_spmm_csr_bf16_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const uint16_t* h, int64_t ld_h, int64_t d,
-                         const float* row_scale, const float* bias, int relu, float* out, int64_t ld_out, int32_t hub_threshold,
-                         int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                         size_t ws_bytes, void* stream);
-int cb_spmm_csr_fused_bf16_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const uint16_t* h, int64_t ld_h,
-                               int64_t d, const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix,
-                               float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                               uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                               int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
-                               const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Normalisation tricks (GNN_model/norm_tricks.py) as fused reductions; all matrices contiguous [rows, d].
@@ -413,54 +412,6 @@ int cb_col_bwd_combine_f32(const float* g, const float* xh, const float* xs, con
 size_t cb_topk_replace_workspace_bytes(int64_t B, int64_t N, int64_t K);
 int cb_topk_replace_f32(const float* q, int64_t ldq, const float* t, int64_t ldt, int64_t B, int64_t N, int64_t D, int32_t K,
                         float* out, int32_t* out_idx, float* out_w, void* ws, size_t ws_bytes, void* stream);
-
-/* cb_spmm_csr_fused_f32 over a CSR whose rows are a SUBSET of the node rows: row r of rowptr / row_scale / out_act / out_next is node row row_ids[r]
- * (ascending ids); mix_src, relu_bits ([all node rows][d/256][4]) and the dropout mask are taken at the node row.  The rows-only training forward
- * (trunk.py): a GCNConv + store (GCN.py:205-256,127-133) evaluated only on the rows the layers above read. */
-int cb_spmm_csr_fused_rows_f32(const int32_t* row_ids, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E,
-                               const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, const float* mix_src,
-                               int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                               uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                               int32_t hub_T, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                               size_t ws_bytes, void* stream);
-
-/* ------------------------------------------------------------------------------------
- * Node-sharded aggregation in two passes (new; the reference is single-device).  A rank's row block of
- * the CSR is split by column owner: the interior-column pass (plain cb_spmm_csr_f32, no epilogue) runs while the halo
- * rows travel over xGMI; the halo-column pass starts from those raw sums and applies the epilogue once:
- *     out[v, :] = act( row_scale[v] * (acc_init[v, :] + sum_{j in row v of THIS csr} h[col[j], :]) + bias[:] )
- * Same arguments as cb_spmm_csr_f32 / cb_spmm_csr_fused_f32 plus acc_init [N, ld_init] (fp32, read once; the plain
- * variant allows acc_init == out; a raw in-place pass — acc_init == out, no row scale / bias / ReLU: the intermediate halo slices —
- * neither reads nor writes rows that have no edge in this CSR).  Replaces the same reference lines as those two
- * (GCN.py:198,238-253,127-133).
- * ---------------------------------------------------------------------------------- */
-int cb_spmm_csr_acc_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
-                        const float* row_scale, const float* bias, int relu, const float* acc_init, int64_t ld_init, float* out,
-                        int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
-                        const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
-int cb_spmm_csr_fused_acc_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                              int64_t E,
-                              const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias,
-                              const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                              const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act,
-                              float* out_next, int64_t ld_next, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                              const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
-
-/* The halo-column pass over bf16-stored halo rows: with the bf16 wire (COLDBREW_HALO_WIRE=bf16, opt-in, outside the 1e-4
- * parity) the rows leave cb_gather_rows_bf16_f32 narrowed (round-to-nearest-even), cross the links at 2 bytes per element and
- * are read by these passes exactly as they arrived (widened in registers; accumulation and outputs fp32) — no conversion pass
- * on either side.  Arguments as the fp32 forms, h = uint16_t rows (8-byte aligned for the vector paths). */
-int cb_spmm_csr_acc_bf16_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const uint16_t* h, int64_t ld_h,
-                             int64_t d, const float* row_scale, const float* bias, int relu, const float* acc_init, int64_t ld_init,
-                             float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
-                             const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
-int cb_spmm_csr_fused_acc_bf16_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags,
-                                   int64_t N, int64_t E, const uint16_t* h, int64_t ld_h, int64_t d, const float* row_scale,
-                                   const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p,
-                                   uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act,
-                                   int64_t ld_act, float* out_next, int64_t ld_next, int32_t hub_threshold, int32_t n_hubs,
-                                   int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes,
-                                   void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Device-side graph analysis in front of the path (per-edge Python dict / list loops in the reference).
@@ -504,56 +455,36 @@ int cb_gather_rows_f32(const float* src, int64_t ld, const int64_t* idx, int64_t
  * image: B split once into bf16 limbs in MFMA fragment order by cb_agg_gemm_image_f32 (transpose = 1: B = W^T);
  * cb_agg_gemm_image_bytes(256, 256) bytes, 16-byte aligned, L2 resident (384 KB).
  * acc_init (may be NULL; [N, ld_init] fp32, may alias the aggregated output): the reduction of a row starts from these partial sums — the
- * LAST pass of a node-sharded aggregation (cb_spmm_csr_acc_f32 / cb_spmm_csr_fused_acc_f32 + the GEMM), so that a rank's last halo pass
- * also produces the next layer's Z / this layer's dX.
+ * LAST pass of a node-sharded aggregation (cb_spmm_csr_f32 / cb_spmm_csr_fused_f32 with acc_init + the GEMM), so that a rank's last halo
+ * pass also produces the next layer's Z / this layer's dX.
  * A tile hand-over that times out is recorded in the device error word (cb_device_status); these calls return CB_E_DEVICE while it is set.
  * ---------------------------------------------------------------------------------- */
 size_t cb_agg_gemm_image_bytes(int64_t K, int64_t N);
 int cb_agg_gemm_image_f32(const float* W, int64_t ld, int64_t K, int64_t N, int transpose, void* image, size_t image_bytes, void* stream);
-int cb_spmm_gemm_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
-                     const float* row_scale, const float* bias, int relu, const float* acc_init, int64_t ld_init, float* out, int64_t ld_out,
-                     int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws,
-                     size_t ws_bytes, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out,
-                     int64_t ld_gout, void* stream);
-int cb_spmm_gemm_fused_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                           int64_t E, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, const float* mix_src,
-                           int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                           uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                           int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                           const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
+int cb_spmm_gemm_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, int relu,
+                     const float* acc_init, int64_t ld_init, float* out, int64_t ld_out, const void* image, const float* g_rowscale,
+                     const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream);
+/* skip_next != 0: a forward that no backward follows (evaluation / metrics passes, GCN.py:100-140 under no_grad): the stored activations have
+ * no reader — the next layer's Z leaves this kernel — so the rows the persistent kernel finishes are NOT written to out_next (the hub rows
+ * pass through it, its other contents are undefined afterwards; NULL is accepted when n_hubs == 0).  g_out as above. */
+int cb_spmm_gemm_fused_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
+                           const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix,
+                           float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only,
+                           float* out_act, int64_t ld_act, float* out_next, int64_t ld_next, int32_t skip_next, const void* image,
                            const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream);
-/* cb_spmm_gemm_fused_f32 for a forward that no backward follows (evaluation / metrics passes, GCN.py:100-140 under no_grad): the stored
- * activations have no reader — the next layer's Z leaves this kernel — so the rows the persistent kernel finishes are NOT written to
- * out_next (the hub rows pass through it, its other contents are undefined afterwards; NULL is accepted when n_hubs == 0).  g_out as above. */
-int cb_spmm_gemm_fused_eval_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                                int64_t E, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, const float* mix_src,
-                                int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                                uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                                int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                                const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
-                                const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream);
 /* The output Linear as the tail of the LAST layer's aggregation (round 5): GCN.py:133-138 `layers_MLP[-1](F.dropout(x))` reads exactly the rows
  * the last trunk store has just made — logits = out_next @ W_out^T + b_out leave the aggregation kernel (C <= 64 classes; the four multiplying
  * wavefronts of a block take the four 32 x 32 blocks of a tile's 64 x 64 output), the separate head GEMM and its re-read of the [N, 256]
  * activations disappear.  Same limb products in the same order as cb_gemm_nn_f32.  head_image: cb_agg_gemm_head_image_f32 of the nn.Linear
  * weight [C, 256] (transpose = 1) — 256 x 64 with zero columns beyond C; logits [N, ld_logits >= C], 16-byte aligned.  Other arguments as
- * cb_spmm_gemm_fused_f32.  _eval: a forward that no backward follows — the last layer's activations are not written at all. */
+ * cb_spmm_gemm_fused_f32.  skip_next != 0: a forward that no backward follows — the last layer's activations are not written at all. */
 size_t cb_agg_gemm_head_image_bytes(int64_t K, int64_t C);
 int cb_agg_gemm_head_image_f32(const float* W, int64_t ld, int64_t K, int64_t C, int transpose, void* image, size_t image_bytes, void* stream);
-int cb_spmm_gemm_fused_head_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                                int64_t E, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias, const float* mix_src,
-                                int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                                uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                                int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows, const int32_t* hub_chunk_ptr,
-                                void* ws, size_t ws_bytes, const void* head_image, const float* head_bias, int64_t C, float* logits,
-                                int64_t ld_logits, void* stream);
-int cb_spmm_gemm_fused_head_eval_f32(const float* acc_init, int64_t ld_init, const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N,
-                                     int64_t E, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* bias,
-                                     const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                     const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act,
-                                     int64_t ld_act, float* out_next, int64_t ld_next, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                                     const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* head_image,
-                                     const float* head_bias, int64_t C, float* logits, int64_t ld_logits, void* stream);
+int cb_spmm_gemm_fused_head_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
+                                const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix,
+                                float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only,
+                                float* out_act, int64_t ld_act, float* out_next, int64_t ld_next, int32_t skip_next, const void* head_image,
+                                const float* head_bias, int64_t C, float* logits, int64_t ld_logits, void* stream);
 /* Fault injection for the failure path above (tests): one wavefront waits with a short spin bound for a hand-over that never comes;
  * cb_device_status() must then report CB_E_DEVICE. */
 int cb_agg_gemm_handover_selftest(void* stream);
@@ -625,28 +556,24 @@ int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const uint64_t* x
                            void* stream);
 
 /* The sum-first GCNConv + store of the rows-only training forward in one persistent kernel (replaces GCN.py:213-256 with the sum taken first,
- * then :127-133 on a subset of the node rows: cb_spmm_csr_colscale_f32 followed by cb_gemm_nn_store_rows_f32 — the same values bit for bit):
+ * then :127-133 on a subset of the node rows: cb_spmm_csr_f32 with col_scale followed by cb_gemm_nn_store_rows_f32 — the same values bit for bit):
  *     out   = H[v] = sum_{u in row v} col_scale[u] * h[u]                  [N, 256] (stored: the backward's source-side level reads it)
  *     act   = relu(g_rowscale[m] * (H @ B)[m] + bias)                      -> out_act [N, ld_act] if given
  *     g_out = dropout_{seed, node row}(c_act * act + c_mix * mix_src[mix_index[m] | row_ids[m]])
  *     relu_bits[row_ids[m]][0..3] = the mask words of act > 0 (AND kept by the dropout unless bits_relu_only), as cb_gemm_nn_store_rows_f32
  * row_ids (int64 [N]): the node row of each CSR row; the dropout mask is drawn at (row0 + row_ids[m]).  d must be 256, fp32 rows, 16-byte aligned;
  * image: cb_agg_gemm_image_f32 of W.  A tile hand-over that times out is recorded in the device error word (cb_device_status). */
-int cb_spmm_gemm_store_rows_f32(const int32_t* rowptr, const int32_t* col, int32_t col_flags, int64_t N, int64_t E, const float* h, int64_t ld_h,
-                                int64_t d, const float* col_scale, float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                                const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, const void* image,
-                                const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src, int64_t ld_mix,
-                                const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev,
-                                int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* g_out,
-                                int64_t ld_gout, void* stream);
+int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* col_scale, float* out, int64_t ld_out,
+                                const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src,
+                                int64_t ld_mix, const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed,
+                                const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act,
+                                float* g_out, int64_t ld_gout, void* stream);
 
 /* One label-propagation step, elementwise passes folded into the aggregation's store (Label_propagation_model/outcome_correlation.py:137-143
  * with alpha_term and post_step = clamp(0, 1), as trainer_node_classification.py:33-63 drives it):
  *     out[v, :] = post_scale[v] * clamp(row_scale[v] * sum_{u in row v} h[u, :] + c_mix * mix[v, :], 0, 1)      (post_scale NULL: 1) */
-int cb_spmm_csr_lp_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
-                       const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, const float* post_scale, float* out,
-                       int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks, const int32_t* hub_rows,
-                       const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
+int cb_spmm_csr_lp_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* mix, int64_t ld_mix,
+                       float c_mix, const float* post_scale, float* out, int64_t ld_out, void* stream);
 
 /* One propagation step of general_outcome_correlation (Label_propagation_model/outcome_correlation.py:128-145) for every normalised adjacency and
  * post-step of Correct & Smooth, next to cb_spmm_csr_lp_f32 (same kernels, same hub plan; lo = 0, hi = 1, fix_rows = NULL is that entry bit for bit):
@@ -655,10 +582,9 @@ int cb_spmm_csr_lp_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int
  * mix[v, :] (fix_inputs, :194-199, whose fixed values ARE the mix rows).  With A_norm = diag(R) A diag(S) — DAD: R = S = D^-1/2; DA: R = D^-1, S = 1;
  * AD: R = 1, S = D^-1 (:51-55) — and the state s_t = S (.) result_t as h: row_scale = alpha R, c_mix = 1 - alpha (alpha_term) or 1, post_scale = S
  * (NULL on the last step, which returns result itself).  The CSR is by destination; the graph is symmetric (to_undirected, :41). */
-int cb_spmm_csr_prop_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, const float* h, int64_t ld_h, int64_t d,
-                         const float* row_scale, const float* mix, int64_t ld_mix, float c_mix, float lo, float hi, const uint8_t* fix_rows,
-                         const float* post_scale, float* out, int64_t ld_out, int32_t hub_threshold, int32_t n_hubs, int32_t n_chunks,
-                         const int32_t* hub_rows, const int32_t* hub_chunk_ptr, void* ws, size_t ws_bytes, void* stream);
+int cb_spmm_csr_prop_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* row_scale, const float* mix, int64_t ld_mix,
+                         float c_mix, float lo, float hi, const uint8_t* fix_rows, const float* post_scale, float* out, int64_t ld_out,
+                         void* stream);
 
 /* Row passes of Correct & Smooth (csrc/cb_cs.hip).  label_rows: uint8 [N], non-zero = label row (the layout of fix_rows above); labels: int64 [N];
  * Cp >= C: the row width of the matrices the aggregation reads (padding columns are written as 0).  Workspace of the first: cb_cs_workspace_bytes.

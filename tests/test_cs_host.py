@@ -83,20 +83,23 @@ def test_c_abi_of_the_correct_and_smooth_entries():
         n_args = len([a for a in re.search(name + r'\s*\((.*?)\)\s*;', hdr, flags=re.S).group(1).split(',') if a.strip() and a.strip() != 'void'])
         assert n_args == len(_lib.SIGNATURES[name][1]), (name, n_args, len(_lib.SIGNATURES[name][1]))
     L = _lib.load()
-    assert L.cb_version() == 4
+    assert L.cb_version() == 5
     inf = float('inf')
     p8 = ctypes.c_void_p(8)
     # cb_spmm_csr_prop_f32: argument checks answer before anything is launched
-    assert L.cb_spmm_csr_prop_f32(None, None, -1, 0, None, 0, 0, None, None, 0, 0.5, 0.0, 1.0, None, None, None, 0, 1, 0, 0, None, None, None, 0, None) == -1
-    assert L.cb_spmm_csr_prop_f32(None, None, 4, 0, None, 0, 4, None, None, 0, 0.5, 1.0, 0.0, None, None, None, 0, 1, 0, 0, None, None, None, 0, None) == -1
+    def view(n_rows, rowptr=None, hub=(1, 0, 0, None, None)):
+        return _lib.CsrView(rowptr=rowptr, col=None, col_flags=0, n_rows=n_rows, n_edges=0, hub_threshold=hub[0], n_hubs=hub[1], n_chunks=hub[2],
+                            hub_rows=hub[3], hub_chunk_ptr=hub[4], ws=None, ws_bytes=0)
+    assert L.cb_spmm_csr_prop_f32(view(-1), None, 0, 0, None, None, 0, 0.5, 0.0, 1.0, None, None, None, 0, None) == -1
+    assert L.cb_spmm_csr_prop_f32(view(4), None, 0, 4, None, None, 0, 0.5, 1.0, 0.0, None, None, None, 0, None) == -1
     assert b'lo <= hi' in L.cb_last_error()
-    assert L.cb_spmm_csr_prop_f32(None, None, 4, 0, None, 0, 4, None, None, 0, 0.5, float('nan'), inf, None, None, None, 0, 1, 0, 0, None, None, None, 0, None) == -1
-    assert L.cb_spmm_csr_prop_f32(None, None, 4, 0, None, 4, 4, None, None, 4, 0.5, -inf, inf, None, None, None, 4, 1, 0, 0, None, None, None, 0, None) == -1
+    assert L.cb_spmm_csr_prop_f32(view(4), None, 0, 4, None, None, 0, 0.5, float('nan'), inf, None, None, None, 0, None) == -1
+    assert L.cb_spmm_csr_prop_f32(view(4), None, 4, 4, None, None, 4, 0.5, -inf, inf, None, None, None, 4, None) == -1
     assert b'null pointer' in L.cb_last_error()
-    assert L.cb_spmm_csr_prop_f32(p8, None, 4, 0, p8, 3, 4, None, p8, 4, 0.5, 0.0, 1.0, None, None, p8, 4, 1, 0, 0, None, None, None, 0, None) == -1
+    assert L.cb_spmm_csr_prop_f32(view(4, p8), p8, 3, 4, None, p8, 4, 0.5, 0.0, 1.0, None, None, p8, 4, None) == -1
     assert b'leading dimension' in L.cb_last_error()
-    assert L.cb_spmm_csr_prop_f32(p8, None, 4, 0, p8, 4, 4, None, p8, 4, 0.5, 0.0, 1.0, None, None, p8, 4, 64, 2, 3, p8, p8, None, 0, None) == -3
-    assert L.cb_spmm_csr_prop_f32(None, None, 2 ** 31, 0, None, 0, 4, None, None, 0, 0.5, 0.0, 1.0, None, None, None, 0, 1, 0, 0, None, None, None, 0, None) == -2
+    assert L.cb_spmm_csr_prop_f32(view(4, p8, (64, 2, 3, p8, p8)), p8, 4, 4, None, p8, 4, 0.5, 0.0, 1.0, None, None, p8, 4, None) == -3
+    assert L.cb_spmm_csr_prop_f32(view(2 ** 31), None, 0, 4, None, None, 0, 0.5, 0.0, 1.0, None, None, None, 0, None) == -2
     # the row kernels: workspace query, missing workspace, bad mode / shapes
     assert L.cb_cs_workspace_bytes(0, 7) == 0 and L.cb_cs_workspace_bytes(100, 7) == 4 * 4 and L.cb_cs_workspace_bytes(10 ** 7, 48) == 4 * 1024
     assert L.cb_cs_residual_init_f32(p8, 7, p8, p8, 100, 7, 7, None, p8, None, p8, None, 0, None) == -3

@@ -106,7 +106,7 @@ def test_fused_store_gemm_equals_fused_store_then_gemm(n, T, p):
         bits_r, nxt_r, _ = trunk._fused_spmm(G, z, bias, mix, 0.9, 0.1, p, 4242)
         assert torch.equal(bits, bits_r) and torch.equal(nxt, nxt_r)
         assert torch.equal(zn, gemm.mm_nn(nxt_r, w, rowscale=a, addend=addend))
-    # a forward that no backward follows (cb_spmm_gemm_fused_eval_f32): no mask words, the stored activations are not written, Z_next the same bits
+    # a forward that no backward follows (cb_spmm_gemm_fused_f32 with skip_next): no mask words, the stored activations are not written, Z_next the same bits
     b2, n2, z2 = trunk._fused_gemm_launch(G, z, bias, x0, 0.9, 0.1, p, 4242, weight_image(w), a, le, want_bits=False)
     nxt_mix = trunk._fused_spmm(G, z, bias, x0, 0.9, 0.1, p, 4242)[1]
     assert b2 is None and n2 is None and torch.equal(z2, gemm.mm_nn(nxt_mix, w, rowscale=a, addend=le))
@@ -196,7 +196,7 @@ def _acc_init_case(n, T):
 @pytest.mark.parametrize('n,T,p', [(5003, 16, 0.1), (20000, 256, 0.0)], ids=['5003-16-0.1-True', '20000-256-0.0-True'])
 def test_acc_init_forms_equal_the_two_kernel_forms(n, T, p):
     """The ACC forms (node-sharded path: the last halo pass of a rank's aggregation is the aggregation + GEMM kernel on top of the running
-    sums of the earlier passes): cb_spmm_gemm_fused_f32 with acc_init is bit-identical to cb_spmm_csr_fused_acc_f32 followed by
+    sums of the earlier passes): cb_spmm_gemm_fused_f32 with acc_init is bit-identical to cb_spmm_csr_fused_f32 with acc_init followed by
     cb_gemm_nn_f32 — hub rows included (the hub finish kernel adds the partial sums of its rows)."""
     from gnn_tail_generalization_amd import _lib, gemm, trunk
     from gnn_tail_generalization_amd.graph import weight_image
@@ -210,7 +210,7 @@ def test_acc_init_forms_equal_the_two_kernel_forms(n, T, p):
 
 @pytest.mark.parametrize('n,T', [(70001, 64), (777, 8)])
 def test_acc_init_plain_form_equals_the_two_kernel_form(n, T):
-    """The plain ACC form: cb_spmm_gemm_f32 with acc_init is bit-identical to cb_spmm_csr_acc_f32 followed by cb_gemm_nn_f32 — hub rows
+    """The plain ACC form: cb_spmm_gemm_f32 with acc_init is bit-identical to cb_spmm_csr_f32 with acc_init followed by cb_gemm_nn_f32 — hub rows
     included — and finishes the running sums in place."""
     from gnn_tail_generalization_amd import gemm
     from gnn_tail_generalization_amd.graph import weight_image

@@ -251,7 +251,7 @@ def test_edge_weight_form_matches_reference(name):
 
 @pytest.mark.parametrize('d,dtype', [(256, torch.float32), (512, torch.float32), (40, torch.float32), (7, torch.float32), (256, torch.bfloat16)])
 def test_in_place_accumulation_skips_rows_without_edges(d, dtype):
-    """Intermediate halo passes of the node-sharded aggregation: cb_spmm_csr_acc_f32 with out == acc_init and no epilogue neither reads nor
+    """Intermediate halo passes of the node-sharded aggregation: cb_spmm_csr_f32 with out == acc_init and no epilogue neither reads nor
     writes rows that have no edge in the slice's CSR.  A rectangular CSR in which most rows are empty (runs of empty rows at the start, in the
     middle and at the end of wavefront row blocks, a hub row, an empty row right after a hub row) gives, in place, exactly the out-of-place
     sums — and the same through the bf16-stored source rows of the bf16 wire."""

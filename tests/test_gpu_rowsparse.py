@@ -145,7 +145,7 @@ def test_rows_only_forward_equals_the_dense_step(conn, se, layers, n_loss_rows, 
     same loss and gradients up to the association of sums — (sum a X) W against sum a (X W) — and the ReLUs that association flips at zero.
     below = CB_ROWS_ONLY_BELOW, what the layer UNDER the last one does: '2' (default) — its sum first too, on the rows the last layer reads (S_1: aggregate,
     GEMM on |S_1| rows, store; the backward's level 1 contracts the saved aggregate; needs a layer under it and no table on it, else as '1');
-    '1' — Z-first on S_1 (cb_spmm_csr_fused_rows_f32: the fused store over a subset of the rows; 'Residual': its ReLU output, the last layer's mix
+    '1' — Z-first on S_1 (cb_spmm_csr_fused_f32 with row_ids: the fused store over a subset of the rows; 'Residual': its ReLU output, the last layer's mix
     source, lives there too); '0' — on all rows."""
     from gnn_tail_generalization_amd import trunk
     calls, subset_launches, on_rows = [], [], []
@@ -219,7 +219,7 @@ def test_rows_only_forward_returns_the_loss_rows_and_poison(monkeypatch):
 @pytest.mark.parametrize('se,layers', [('000', 3), ('111', 3), ('000', 2), ('100', 4)])
 def test_rows_only_forward_of_the_non_residual_stack(se, layers, monkeypatch):
     """stack.py (NoRes: F -> H -> ... -> C): the last aggregation (class width) on the loss rows, the last transform on the rows it gathers (S_1), the last
-    hidden layer's aggregation + store on S_1 (cb_spmm_csr_fused_rows_f32).  Same sums in the same order as the all-rows forward: the loss is the same to
+    hidden layer's aggregation + store on S_1 (cb_spmm_csr_fused_f32 with row_ids).  Same sums in the same order as the all-rows forward: the loss is the same to
     the last bit, the gradients equal the dense backward's as the row-sparse backward's do."""
     from gnn_tail_generalization_amd import stack
     subset_launches = []

@@ -88,7 +88,7 @@ def test_c_abi_of_the_student_kernels():
         n_args = len([a for a in re.search(name + r'\s*\((.*?)\)\s*;', hdr, flags=re.S).group(1).split(',') if a.strip() and a.strip() != 'void'])
         assert n_args == len(_lib.SIGNATURES[name][1]), (name, n_args, len(_lib.SIGNATURES[name][1]))
     loaded = _lib.load()
-    assert loaded.cb_version() == 4
+    assert loaded.cb_version() == 5
     assert loaded.cb_ln_gelu_drop_bwd_workspace_bytes(65536, 256) == 2048 * 3 * 256 * 4
     # argument checks answer before anything is launched: a width the row kernels do not hold in registers, a missing workspace
     assert loaded.cb_ln_gelu_drop_fwd_f32(None, 4, 513, None, None, 1e-5, 0.0, 0, None, None, None, None) == -1

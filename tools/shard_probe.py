@@ -5,7 +5,7 @@ d = 256 and turns the rows on the busiest peer link into predicted link times.
 
 Two pipelines are probed side by side (--mode both):
   pull   round 3's: pull-only halo plan cut by owner row chunk, row-chunked producers (layer GEMM chunk k -> pack k -> send k), interior
-         pass, per-slice halo passes (cb_spmm_csr_acc_f32), the last one with the epilogue; the layer GEMM is a kernel of its own.
+         pass, per-slice halo passes (cb_spmm_csr_f32 with acc_init), the last one with the epilogue; the layer GEMM is a kernel of its own.
   cover  this round's default: push / pull vertex cover per rank pair (dist.choose_cover; pack = aggregation over the send CSR),
          positional slices, and the LAST halo pass is the aggregation + GEMM kernel on top of the running sums (cb_spmm_gemm_f32 /
          cb_spmm_gemm_fused_f32 with acc_init) — the next stage's matrix exists when that kernel ends.
