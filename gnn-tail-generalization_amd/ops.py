@@ -101,7 +101,9 @@ def dropout(x, p, training=True, seed=None, offset=0):
 
 def dropout_keep_mask(shape, p, seed, device, offset=0):
     """The boolean keep-mask `dropout` uses for (seed, shape) — for parity tests that inject the same
-    mask into the oracle."""
+    mask into the oracle.  The mask is pinned bit for bit to the host restatement of Philox4x32-10
+    (oracle/coldbrew_oracle.py dropout_keep_mask) over offsets up to 2^40, seeds up to 2^62 and the device seed word
+    (tests/test_philox_host.py, tests/test_gpu_philox.py)."""
     ones = torch.ones(shape, dtype=torch.float32, device=device)
     return _dropout_raw(ones, p, seed, offset) > 0
 

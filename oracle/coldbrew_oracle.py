@@ -472,3 +472,62 @@ def semlp_replacement(le_guess, teacher_se, k):
         sels.append(select)
         wts.append(w[0])
     return torch.cat(outs, dim=0), torch.stack(sels), torch.stack(wts)
+
+
+# --------------------------------------------------------------------------------------
+# Dropout keep-mask: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's
+# philox4x32 with 10 rounds).  include/coldbrew_hip.h promises a Philox4x32-10 draw of (seed, 64-bit flat index) for cb_dropout_f32 and every
+# fused dropout site; how the two fill the generator's words is the project's own choice, set down in csrc/cb_philox.h: counter = (lo32(q), hi32(q),
+# 0x243F6A88, 0x85A308D3) with q = flat index / 4, key = (lo32(seed), hi32(seed)), element i reads word i & 3 and is kept iff word >= float32(p) * 2^32
+# (truncated, saturating).  Written from the published algorithm; Random123's kat_vectors pin it (tests/test_philox_host.py).
+# --------------------------------------------------------------------------------------
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57          # round multipliers
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85          # Weyl increments of the key (golden ratio, sqrt(3) - 1)
+DROPOUT_C2, DROPOUT_C3 = 0x243F6A88, 0x85A308D3        # the two counter words the project fixes (first digits of pi)
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32 with 10 rounds on broadcastable integer arrays of 32-bit words -> uint32 [..., 4].  One round maps the counter
+    (c0, c1, c2, c3) under the key (k0, k1) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); the key is bumped by
+    (W0, W1) between rounds (not after the last one)."""
+    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & _M32 for v in (c0, c1, c2, c3, k0, k1)])
+    for r in range(10):
+        if r:
+            k0 = (k0 + np.uint64(PHILOX_W0)) & _M32
+            k1 = (k1 + np.uint64(PHILOX_W1)) & _M32
+        p0 = np.uint64(PHILOX_M0) * c0                 # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def dropout_words(seed, quad):
+    """The four 32-bit words of quad `quad` (= flat element index // 4) under the 64-bit `seed`: counter (lo32(quad), hi32(quad), C2, C3),
+    key (lo32(seed), hi32(seed))."""
+    s = int(seed) % (1 << 64)
+    q = np.asarray(quad, dtype=np.uint64)
+    return philox4x32_10(q & _M32, q >> np.uint64(32), DROPOUT_C2, DROPOUT_C3, s & 0xFFFFFFFF, s >> 32)
+
+
+def dropout_threshold(p):
+    """An element is kept iff its 32-bit word >= this: float32(p) * 2^32 in double, truncated, saturating at 0xFFFFFFFF."""
+    t = float(np.float32(p)) * 4294967296.0
+    return 0xFFFFFFFF if t >= 4294967295.0 else int(t)
+
+
+def dropout_scale(p):
+    """1 / (1 - p) in float32 arithmetic."""
+    return np.float32(1) / (np.float32(1) - np.float32(p))
+
+
+def dropout_keep_mask(shape, p, seed, offset=0, seed_dev=0):
+    """bool array `shape`: the element at flat index i = offset + (row-major local index) is kept iff word[i & 3] of quad i >> 2 under the
+    seed (seed + seed_dev) mod 2^64 is >= dropout_threshold(p)   (include/coldbrew_hip.h, cb_dropout_f32)."""
+    n = int(np.prod(shape, dtype=np.int64))
+    offset = int(offset)
+    q0 = offset >> 2
+    nq = ((offset + n + 3) >> 2) - q0
+    words = dropout_words(int(seed) + int(seed_dev), np.uint64(q0) + np.arange(nq, dtype=np.uint64))
+    lo = offset & 3
+    return (words.reshape(-1)[lo:lo + n] >= np.uint32(dropout_threshold(p))).reshape(shape)

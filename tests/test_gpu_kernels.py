@@ -109,6 +109,7 @@ def test_dropout_properties(n):
     p, seed = 0.3, 123456789
     y = ops.dropout(x, p, True, seed=seed)
     keep = ops.dropout_keep_mask((n,), p, seed, DEV)
+    assert torch.equal(keep.cpu(), torch.from_numpy(orc.dropout_keep_mask((n,), p, seed)))      # the host restatement of Philox4x32-10
     torch.testing.assert_close(y.detach(), torch.where(keep, x.detach() / (1 - p), torch.zeros_like(x)), rtol=1e-6, atol=0)
     assert torch.equal(y, ops.dropout(x, p, True, seed=seed))                 # pure function of (seed, index)
     if n > 1000:
