@@ -483,8 +483,6 @@ static int launch_agg_gemm(const cb_csr_view& g, const float* h, int64_t ld_h, E
   return CB_OK;
 }
 
-static inline bool ag_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace cb
 
 using namespace cb;
@@ -507,7 +505,7 @@ extern "C" int cb_agg_gemm_image_f32(const float* W, int64_t ld, int64_t K, int6
   CB_CHECK_ARG(K == kKD && N == kND, CB_E_INVALID, "cb_agg_gemm_image_f32: the fused dense part is built for 256 x 256 weights (got %lld x %lld)",
                (long long)K, (long long)N);
   CB_CHECK_ARG(W && image && ld >= (transpose ? K : N), CB_E_INVALID, "cb_agg_gemm_image_f32: null pointer / bad leading dimension");
-  CB_CHECK_ARG(image_bytes >= cb_agg_gemm_image_bytes(K, N) && ag_al16(image), CB_E_WORKSPACE, "cb_agg_gemm_image_f32: image buffer too small or misaligned");
+  CB_CHECK_ARG(image_bytes >= cb_agg_gemm_image_bytes(K, N) && aligned16(image), CB_E_WORKSPACE, "cb_agg_gemm_image_f32: image buffer too small or misaligned");
   // B[k][n] = W[k][n] (transpose = 0) or W[n][k] (transpose = 1: the dX contraction multiplies by W^T)
   const int64_t sk = transpose ? 1 : ld, sn = transpose ? ld : 1;
   hipLaunchKernelGGL(k_weight_image, dim3(kNS * kNT * 64 / 256), dim3(256), 0, (hipStream_t)stream, W, sk, sn, (uint4*)image, kNS);
@@ -524,9 +522,9 @@ static int agg_gemm_common_checks(const char* who, const cb_csr_view* g, cb_csr_
   if (rc != CB_OK || v.n_rows == 0) return rc;
   CB_CHECK_ARG(v.n_rows < INT32_MAX - kTM, CB_E_RANGE, "%s: size exceeds the int32 contract", who);
   CB_CHECK_ARG(h && image && g_out, CB_E_INVALID, "%s: null pointer", who);
-  CB_CHECK_ARG(ag_al16(h) && ld_h % 4 == 0 && ld_h >= d && ag_al16(image) && ag_al16(g_out) && ld_gout % 4 == 0 && ld_gout >= kND &&
-                   (!g_addend || (ag_al16(g_addend) && ld_add % 4 == 0 && ld_add >= kND)) &&
-                   (!acc_init || (ag_al16(acc_init) && ld_init % 4 == 0 && ld_init >= d)),
+  CB_CHECK_ARG(aligned16(h) && ld_h % 4 == 0 && ld_h >= d && aligned16(image) && aligned16(g_out) && ld_gout % 4 == 0 && ld_gout >= kND &&
+                   (!g_addend || (aligned16(g_addend) && ld_add % 4 == 0 && ld_add >= kND)) &&
+                   (!acc_init || (aligned16(acc_init) && ld_init % 4 == 0 && ld_init >= d)),
                CB_E_INVALID, "%s: 16-byte aligned rows of at least 256 floats required", who);
   return CB_OK;
 }
@@ -540,7 +538,7 @@ extern "C" int cb_spmm_gemm_f32(const cb_csr_view* g, const float* h, int64_t ld
   cb_csr_view v;
   const int rc = agg_gemm_common_checks("cb_spmm_gemm_f32", g, v, d, h, ld_h, image, g_addend, ld_add, g_out, ld_gout, acc_init, ld_init);
   if (rc != CB_OK || v.n_rows == 0) return rc;
-  CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d, CB_E_INVALID, "cb_spmm_gemm_f32: 16-byte aligned output rows required");
+  CB_CHECK_ARG(out && aligned16(out) && ld_out % 4 == 0 && ld_out >= d, CB_E_INVALID, "cb_spmm_gemm_f32: 16-byte aligned output rows required");
   Epilogue ep{row_scale, bias, relu, acc_init, ld_init, v.col_flags};
   GemmTail gt{(const uint4*)image, g_rowscale, g_addend, ld_add, g_out, ld_gout};
   if (acc_init) return launch_agg_gemm<false, true>(v, h, ld_h, ep, out, ld_out, (hipStream_t)stream, FusedEpi{}, gt);
@@ -559,8 +557,8 @@ extern "C" int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h,
   cb_csr_view v;
   const int rc = agg_gemm_common_checks("cb_spmm_gemm_store_rows_f32", g, v, d, h, ld_h, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
   if (rc != CB_OK || v.n_rows == 0) return rc;
-  CB_CHECK_ARG(out && ag_al16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids && (!mix_src || (ag_al16(mix_src) && ld_mix % 4 == 0 && ld_mix >= kND)) &&
-                   (!out_act || (ag_al16(out_act) && ld_act % 4 == 0 && ld_act >= kND)) && (!relu_bits || ag_al16(relu_bits)),
+  CB_CHECK_ARG(out && aligned16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids && (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0 && ld_mix >= kND)) &&
+                   (!out_act || (aligned16(out_act) && ld_act % 4 == 0 && ld_act >= kND)) && (!relu_bits || aligned16(relu_bits)),
                CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: null pointer or misaligned rows");
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: dropout p / row offset out of range");
   Epilogue ep{nullptr, nullptr, 0, nullptr, 0, v.col_flags};
@@ -586,8 +584,8 @@ static int spmm_gemm_fused_impl(const char* who, const cb_csr_view* g, const flo
   cb_csr_view v;
   const int rc = agg_gemm_common_checks(who, g, v, d, h, ld_h, image, g_addend, ld_add, g_out, n_out > 0 ? kND : ld_gout, acc_init, ld_init);
   if (rc != CB_OK || v.n_rows == 0) return rc;
-  CB_CHECK_ARG((out_next || (skip_next && v.n_hubs == 0)) && ag_al16(out_next) && ld_next % 4 == 0 && ld_next >= d &&
-                   (!mix_src || (ag_al16(mix_src) && ld_mix % 4 == 0)) && (!out_act || (ag_al16(out_act) && ld_act % 4 == 0 && ld_act >= d)),
+  CB_CHECK_ARG((out_next || (skip_next && v.n_hubs == 0)) && aligned16(out_next) && ld_next % 4 == 0 && ld_next >= d &&
+                   (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0)) && (!out_act || (aligned16(out_act) && ld_act % 4 == 0 && ld_act >= d)),
                CB_E_INVALID, "%s: 16-byte aligned rows required", who);
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "%s: dropout p out of range", who);
   Epilogue ep{row_scale, bias, 1, acc_init, ld_init, v.col_flags};
@@ -626,7 +624,7 @@ extern "C" int cb_agg_gemm_head_image_f32(const float* W, int64_t ld, int64_t K,
   CB_CHECK_ARG(cb_agg_gemm_head_image_bytes(K, C) > 0, CB_E_INVALID, "cb_agg_gemm_head_image_f32: K must be 256 and 1 <= C <= 64 (got %lld x %lld)", (long long)K,
                (long long)C);
   CB_CHECK_ARG(W && image && ld >= (transpose ? K : C), CB_E_INVALID, "cb_agg_gemm_head_image_f32: null pointer / bad leading dimension");
-  CB_CHECK_ARG(image_bytes >= cb_agg_gemm_head_image_bytes(K, C) && ag_al16(image), CB_E_WORKSPACE, "cb_agg_gemm_head_image_f32: image buffer too small or misaligned");
+  CB_CHECK_ARG(image_bytes >= cb_agg_gemm_head_image_bytes(K, C) && aligned16(image), CB_E_WORKSPACE, "cb_agg_gemm_head_image_f32: image buffer too small or misaligned");
   const int64_t sk = transpose ? 1 : ld, sn = transpose ? ld : 1;
   hipLaunchKernelGGL(k_weight_image_narrow, dim3(kNS * kNTn * 64 / 256), dim3(256), 0, (hipStream_t)stream, W, sk, sn, (uint4*)image, kNS, (int)C);
   CB_LAUNCH_CHECK();
@@ -644,7 +642,7 @@ extern "C" int cb_spmm_gemm_fused_head_f32(const cb_csr_view* g, const float* ac
   const bool empty = g && g->n_rows == 0;
   CB_CHECK_ARG(C >= 1 && C <= 32 * kNTn && (empty || (logits && ld_logits >= C)), CB_E_INVALID, "%s: 1 <= C <= 64 logits per row expected", who);
   // (the common checks want a 256-wide 16-byte aligned tail output: the narrow tail has its own rule — any ld >= C, float4 stores where ld % 4 == 0)
-  CB_CHECK_ARG(empty || ((uintptr_t)logits % 16) == 0, CB_E_INVALID, "%s: logits must be 16-byte aligned", who);
+  CB_CHECK_ARG(empty || aligned16(logits), CB_E_INVALID, "%s: logits must be 16-byte aligned", who);
   return spmm_gemm_fused_impl(who, g, acc_init, ld_init, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0, relu_bits,
                               bits_relu_only, out_act, ld_act, out_next, ld_next, skip_next, head_image, nullptr, nullptr, 0, logits, ld_logits, stream,
                               head_bias, (int)C);

@@ -38,7 +38,17 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 
 static inline int blocks_for(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
 
+// the library's one alignment predicate: float4 / dwordx4 accesses need it of every row start
+static inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// sum over the 64 lanes of a wavefront, every lane gets it: a fixed-order butterfly (deterministic)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 
 // a*x + b*y and x*s + b with ONE fixed rounding sequence wherever they occur (residual mix: cb_axpby_f32 and the fused aggregation
 // store; aggregation epilogue: plain and fused store).  Left to the compiler's contraction choice, the fused and the operator-by-

@@ -172,8 +172,6 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
   }
 }
 
-static inline bool fr_al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace cb
 
 using namespace cb;
@@ -188,7 +186,7 @@ extern "C" size_t cb_front_image_bytes(int64_t K) {
 extern "C" int cb_front_image_f32(const float* W, int64_t ld, int64_t K, int transpose, void* image, size_t image_bytes, void* stream) {
   CB_CHECK_ARG(cb_front_image_bytes(K) > 0, CB_E_INVALID, "cb_front_image_f32: K must be 64 or 128 (got %lld)", (long long)K);
   CB_CHECK_ARG(W && image && ld >= (transpose ? K : kND), CB_E_INVALID, "cb_front_image_f32: null pointer / bad leading dimension");
-  CB_CHECK_ARG(image_bytes >= cb_front_image_bytes(K) && fr_al16(image), CB_E_WORKSPACE, "cb_front_image_f32: image buffer too small or misaligned");
+  CB_CHECK_ARG(image_bytes >= cb_front_image_bytes(K) && aligned16(image), CB_E_WORKSPACE, "cb_front_image_f32: image buffer too small or misaligned");
   const int64_t sk = transpose ? 1 : ld, sn = transpose ? ld : 1;
   const int ns = (int)(K / 16);
   hipLaunchKernelGGL(k_weight_image, dim3(ns * kNT * 64 / 256), dim3(256), 0, (hipStream_t)stream, W, sk, sn, (uint4*)image, ns);
@@ -205,9 +203,9 @@ extern "C" int cb_trunk_front_f32(const float* x, int64_t ld_x, int64_t M, int64
   CB_CHECK_ARG(M < ((int64_t)1 << 31) * kTM / 2, CB_E_RANGE, "cb_trunk_front_f32: size out of range");
   if (M == 0) return CB_OK;
   CB_CHECK_ARG(x && image_in && image_0 && x0 && z0, CB_E_INVALID, "cb_trunk_front_f32: null pointer");
-  CB_CHECK_ARG(fr_al16(x) && ld_x % 4 == 0 && ld_x >= K && fr_al16(image_in) && fr_al16(image_0) && fr_al16(x0) && ld_x0 % 4 == 0 && ld_x0 >= kND &&
-                   fr_al16(z0) && ld_z % 4 == 0 && ld_z >= kND && (!addend || (fr_al16(addend) && ld_add % 4 == 0 && ld_add >= kND)) &&
-                   (!x0_drop || (fr_al16(x0_drop) && ld_drop % 4 == 0 && ld_drop >= kND)) && (!relu_bits || (uintptr_t)relu_bits % 8 == 0),
+  CB_CHECK_ARG(aligned16(x) && ld_x % 4 == 0 && ld_x >= K && aligned16(image_in) && aligned16(image_0) && aligned16(x0) && ld_x0 % 4 == 0 && ld_x0 >= kND &&
+                   aligned16(z0) && ld_z % 4 == 0 && ld_z >= kND && (!addend || (aligned16(addend) && ld_add % 4 == 0 && ld_add >= kND)) &&
+                   (!x0_drop || (aligned16(x0_drop) && ld_drop % 4 == 0 && ld_drop >= kND)) && (!relu_bits || (uintptr_t)relu_bits % 8 == 0),
                CB_E_INVALID, "cb_trunk_front_f32: 16-byte aligned rows required");
   FrontArgs fa{x, ld_x, (const uint4*)image_in, bias_in, (const uint4*)image_0, rowscale, addend, ld_add, x0, ld_x0, (unsigned long long*)relu_bits,
                x0_drop, ld_drop, z0, ld_z, M};

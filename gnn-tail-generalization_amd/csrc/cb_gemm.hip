@@ -166,8 +166,6 @@ static inline int tn_splits(int64_t M, int tiles) {
   return (int)s;
 }
 
-static inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 // CB_GEMM_PLAIN_F32=1 keeps every contraction on the fp32-input MFMA (v_mfma_f32_32x32x2_f32) instead of the
 // three-limb bf16 path of cb_gemm_limb.hip
 static inline bool use_limb3() {
@@ -226,15 +224,15 @@ static int launch_nn(const float* A, int64_t lda, const float* B, int64_t ldb, v
   const int nrb = (int)((M + T::BM - 1) / T::BM), ncb = (int)((N + T::BN - 1) / T::BN);
   const int64_t groups = (nrb + 7) / 8;
   const dim3 grid((unsigned)(groups * 8 * ncb));
-  const bool aligned = al16(A) && al16(B) && lda % 4 == 0 && ldb % 4 == 0;
-  const int c_vec_ok = ((uintptr_t)C % (OUT_BF16 ? 8 : 16) == 0) && ldc % 4 == 0 && (!ep.addend || (al16(ep.addend) && ep.ld_add % 4 == 0));
+  const bool aligned = aligned16(A) && aligned16(B) && lda % 4 == 0 && ldb % 4 == 0;
+  const int c_vec_ok = ((uintptr_t)C % (OUT_BF16 ? 8 : 16) == 0) && ldc % 4 == 0 && (!ep.addend || (aligned16(ep.addend) && ep.ld_add % 4 == 0));
   if constexpr (!OUT_BF16) {
     int k_chunk = 0;
     const int splits = nn_splitk(M, N, K, T::BM, T::BN, &k_chunk);
     if (splits && ws && ws_bytes >= (size_t)splits * M * N * sizeof(float)) {
       const GemmEpilogue raw{};
       const dim3 grid2(grid.x, (unsigned)splits);
-      const int pv = ((uintptr_t)ws % 16 == 0) && N % 4 == 0;
+      const int pv = aligned16(ws) && N % 4 == 0;
       if (aligned)
         hipLaunchKernelGGL((k_gemm_nn<WM, WN, true, false, BK, WTN>), grid2, dim3(256), 0, st, A, lda, B, ldb, ws, N, M, (int)N, (int)K, raw, nrb, ncb, pv, k_chunk);
       else
@@ -261,7 +259,7 @@ static int launch_tn(const float* A, int64_t lda, const float* G, int64_t ldg, c
   const int nsplit = tn_splits(M, tiles_i * tiles_j);
   int64_t rows_per_split = (M + nsplit - 1) / nsplit;
   rows_per_split = (rows_per_split + 31) / 32 * 32;   // whole K steps of either kernel family
-  const bool aligned = al16(A) && al16(G) && lda % 4 == 0 && ldg % 4 == 0;
+  const bool aligned = aligned16(A) && aligned16(G) && lda % 4 == 0 && ldg % 4 == 0;
   const dim3 grid((unsigned)(tiles_i * tiles_j), (unsigned)nsplit);
   CB_CHECK_ARG(!(gdrop || adrop) || (use_limb3() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)), CB_E_INVALID,
                "TN contraction with operand dropout: three-limb path only (check cb_gemm_tn_gdrop_supported first)");
@@ -403,7 +401,7 @@ extern "C" size_t cb_gemm_tn_workspace_bytes(int64_t M, int64_t K1, int64_t K2) 
 // by cb_trunk_store_rows_f32, whose results this reproduces bit for bit).
 extern "C" int cb_gemm_nn_store_rows_supported(const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, int64_t M, int64_t N,
                                                int64_t K) {
-  return use_limb3() && N == 256 && M > 0 && limb3_nn_eligible(A, lda, B, ldb, N, K) && al16(C) && ldc % 4 == 0 ? 1 : 0;
+  return use_limb3() && N == 256 && M > 0 && limb3_nn_eligible(A, lda, B, ldb, N, K) && aligned16(C) && ldc % 4 == 0 ? 1 : 0;
 }
 
 extern "C" int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
@@ -416,8 +414,8 @@ extern "C" int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const floa
   if (M == 0) return CB_OK;
   CB_CHECK_ARG(A && B && C && row_index && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID,
                "cb_gemm_nn_store_rows_f32: null pointer or leading dimension too small");
-  CB_CHECK_ARG(cb_gemm_nn_store_rows_supported(A, lda, B, ldb, C, ldc, M, N, K) && (!addend || (al16(addend) && ld_add % 4 == 0)) &&
-                   (!mix_src || (al16(mix_src) && ld_mix % 4 == 0 && ld_mix >= N)) && (!out_act || (al16(out_act) && ld_act % 4 == 0 && ld_act >= N)) &&
+  CB_CHECK_ARG(cb_gemm_nn_store_rows_supported(A, lda, B, ldb, C, ldc, M, N, K) && (!addend || (aligned16(addend) && ld_add % 4 == 0)) &&
+                   (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0 && ld_mix >= N)) && (!out_act || (aligned16(out_act) && ld_act % 4 == 0 && ld_act >= N)) &&
                    (!relu_bits || (uintptr_t)relu_bits % 8 == 0),
                CB_E_INVALID, "cb_gemm_nn_store_rows_f32: shape / alignment outside the fused form (cb_gemm_nn_store_rows_supported)");
   GemmEpilogue ep{rowscale, addend, ld_add, bias, 1, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, 0};
@@ -488,7 +486,7 @@ extern "C" int cb_gemm_tn_gdrop_f32(const float* A, int64_t lda, const float* G,
 static inline int instage_splits(int64_t M) { return tn_splits(M, 2); }
 
 extern "C" int cb_gemm_tn_instage_supported(const float* g, const float* mfold, const float* X, int64_t ldx, int64_t M, int64_t K2) {
-  return use_limb3() && K2 > 64 && K2 <= 128 && K2 % 4 == 0 && ldx % 4 == 0 && ldx >= K2 && ldx < (1 << 22) && al16(g) && al16(mfold) && al16(X) && M > 0 &&
+  return use_limb3() && K2 > 64 && K2 <= 128 && K2 % 4 == 0 && ldx % 4 == 0 && ldx >= K2 && ldx < (1 << 22) && aligned16(g) && aligned16(mfold) && aligned16(X) && M > 0 &&
                  instage_splits(M) >= 256
              ? 1
              : 0;
@@ -539,7 +537,7 @@ extern "C" int cb_gemm_nn_indrop_f32(const float* A, int64_t lda, const float* B
   CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_indrop_f32: size out of range");
   if (M == 0 || N == 0) return CB_OK;
   CB_CHECK_ARG(C && A && B && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID, "cb_gemm_nn_indrop_f32: null pointer or bad ld");
-  CB_CHECK_ARG(cb_gemm_nn_indrop_supported(A, lda, B, ldb, C, ldc, C, ldc, M, N, K) && (!addend || (al16(addend) && ld_add % 4 == 0)), CB_E_INVALID,
+  CB_CHECK_ARG(cb_gemm_nn_indrop_supported(A, lda, B, ldb, C, ldc, C, ldc, M, N, K) && (!addend || (aligned16(addend) && ld_add % 4 == 0)), CB_E_INVALID,
                "cb_gemm_nn_indrop_f32: shape / alignment outside the fused form (cb_gemm_nn_indrop_supported)");
   GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
   ep.adrop = DropSpec{dropout_threshold(a_drop_p), 1.f / (1.f - a_drop_p), a_seed, seed_dev, row0, K};

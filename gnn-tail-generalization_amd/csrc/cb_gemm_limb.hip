@@ -213,8 +213,6 @@ int launch_tn_instage(const float* g, const float* mfold, const uint64_t* x0_bit
   return CB_OK;
 }
 
-static inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 // Register prefetch depth 1 everywhere (2 / 3 measured no gain: profiles/r01_*); the weight operand split once per launch and staged by
 // LDS-DMA measured neutral (8.23 vs 8.08 ms on 10M x 256 x 256, profiles/r02_gemm_presplit.md: the K loop is bound by the six MFMA passes
 // at the power-limited clock, not by instruction issue) and is not kept.
@@ -224,7 +222,7 @@ static int launch_nn_l3_t(const float* A, int64_t lda, const float* B, int64_t l
   using T = LTile<WM, WN, WTN>;
   const int nrb = (int)((M + T::BM - 1) / T::BM), ncb = (int)((N + T::BN - 1) / T::BN);
   const int64_t groups = (nrb + 7) / 8;
-  const int c_vec_ok = ((uintptr_t)C % (OUT_BF16 ? 8 : 16) == 0) && ldc % 4 == 0 && (!ep.addend || (al16(ep.addend) && ep.ld_add % 4 == 0));
+  const int c_vec_ok = ((uintptr_t)C % (OUT_BF16 ? 8 : 16) == 0) && ldc % 4 == 0 && (!ep.addend || (aligned16(ep.addend) && ep.ld_add % 4 == 0));
   const dim3 grid((unsigned)(groups * 8 * ncb));
   if constexpr (!OUT_BF16 && WM == 2 && WTN == 4) {
     if (ep.out2) {    // dual-output epilogue (dropped copy): the wide-tile fp32 kernel only, see limb3_nn_dual_eligible
@@ -258,15 +256,15 @@ static int launch_nn_l3_t(const float* A, int64_t lda, const float* B, int64_t l
 
 // float4 access to both operands, lane offsets in 32 bits
 bool limb3_nn_eligible(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t N, int64_t K) {
-  return al16(A) && al16(B) && lda % 4 == 0 && ldb % 4 == 0 && K % 4 == 0 && N % 4 == 0 && K > 0 && lda < (1 << 22) && ldb < (1 << 22);
+  return aligned16(A) && aligned16(B) && lda % 4 == 0 && ldb % 4 == 0 && K % 4 == 0 && N % 4 == 0 && K > 0 && lda < (1 << 22) && ldb < (1 << 22);
 }
 
 // the dual-output epilogue exists for the wide (128 x 256) fp32 tile with vector stores on both outputs
 bool limb3_nn_dual_eligible(const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, const float* C2, int64_t ldc2,
                             int64_t M, int64_t N, int64_t K, const GemmEpilogue& ep) {
   // below one wide tile per CU the 128 x 128 tile + a separate elementwise pass is faster (see launch_nn_limb3)
-  return N > 128 && ((M + 127) / 128) * ((N + 255) / 256) >= 256 && limb3_nn_eligible(A, lda, B, ldb, N, K) && al16(C) && al16(C2) && ldc % 4 == 0 && ldc2 % 4 == 0 &&
-         (!ep.addend || (al16(ep.addend) && ep.ld_add % 4 == 0));
+  return N > 128 && ((M + 127) / 128) * ((N + 255) / 256) >= 256 && limb3_nn_eligible(A, lda, B, ldb, N, K) && aligned16(C) && aligned16(C2) && ldc % 4 == 0 && ldc2 % 4 == 0 &&
+         (!ep.addend || (aligned16(ep.addend) && ep.ld_add % 4 == 0));
 }
 
 size_t limb3_nn_workspace_bytes(int64_t, int64_t) { return 0; }      // (the three-limb NN kernels need no workspace)
@@ -306,7 +304,7 @@ static void launch_tn_l3_t(const float* A, int64_t lda, const float* G, int64_t 
 }
 
 bool limb3_tn_eligible(const float* A, int64_t lda, const float* G, int64_t ldg, int64_t K1, int64_t K2) {
-  return al16(A) && al16(G) && lda % 4 == 0 && ldg % 4 == 0 && K1 % 4 == 0 && K2 % 4 == 0 && lda < (1 << 22) && ldg < (1 << 22);
+  return aligned16(A) && aligned16(G) && lda % 4 == 0 && ldg % 4 == 0 && K1 % 4 == 0 && K2 % 4 == 0 && lda < (1 << 22) && ldg < (1 << 22);
 }
 
 int launch_tn_limb3(const float* A, int64_t lda, const float* G, int64_t ldg, const float* rowscale, float* partial, int64_t M,

@@ -20,14 +20,6 @@ constexpr int kMaxFwdBlocks = 256 * 8;
 constexpr int kMaxBwdWaves = 256 * 8;        // partial rows of the backward's column sums
 constexpr int kMaxBlocks = 256 * 8;          // flat kernels; == cb_reduce_workspace_bytes() / 4
 
-static inline int aligned16(const void* a) { return ((uintptr_t)a % 16) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // keep-mask factors of the 4 elements at flat indices f0 .. f0+3 (f0 need not be a multiple of 4): what cb_dropout_f32 draws there
 __device__ __forceinline__ void keep4_flat(uint64_t seed, int64_t f0, int sub, uint32_t thresh, float scale, float (&m)[4]) {
   // sub = f0 & 3 is wave-uniform and the same in every slab of a row: every lane's f0 is row * d + a multiple of 4

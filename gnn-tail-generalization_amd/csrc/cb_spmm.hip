@@ -158,11 +158,11 @@ extern "C" int cb_spmm_csr_f32(const cb_csr_view* g, const void* h, int32_t h_bf
   ep.col_scale = col_scale;
   ep.acc_skip_empty = acc_init && acc_init == out && ld_init == ld_out && !row_scale && !bias && !relu;      // raw in-place pass: rows without edges stay untouched
   hipStream_t st = (hipStream_t)stream;
-  const bool ini16 = !acc_init || (((uintptr_t)acc_init % 16 == 0) && ld_init % 4 == 0);
+  const bool ini16 = !acc_init || (aligned16(acc_init) && ld_init % 4 == 0);
   const bool ini8 = !acc_init || (((uintptr_t)acc_init % 8 == 0) && ld_init % 2 == 0);
   if (!h_bf16) {
     const float* hf = (const float*)h;
-    const bool al16 = ((uintptr_t)h % 16 == 0) && ((uintptr_t)out % 16 == 0) && (ld_h % 4 == 0) && (ld_out % 4 == 0) && (d % 4 == 0) && ini16;
+    const bool al16 = aligned16(h) && aligned16(out) && (ld_h % 4 == 0) && (ld_out % 4 == 0) && (d % 4 == 0) && ini16;
     const bool al8 = ((uintptr_t)h % 8 == 0) && ((uintptr_t)out % 8 == 0) && (ld_h % 2 == 0) && (ld_out % 2 == 0) && (d % 2 == 0) && ini8;
     CB_CHECK_ARG(!v.col_flags || (al16 && d % 256 == 0), CB_E_INVALID, "%s: flagged column ids need d %% 256 == 0 and 16-byte aligned rows", who);
     if (col_scale) {
@@ -176,7 +176,7 @@ extern "C" int cb_spmm_csr_f32(const cb_csr_view* g, const void* h, int32_t h_bf
     return launch_spmm<1>(v, hf, ld_h, d, ep, out, ld_out, st);
   }
   const bf16_t* hb = (const bf16_t*)h;
-  const bool al8 = ((uintptr_t)h % 8 == 0) && ((uintptr_t)out % 16 == 0) && (ld_h % 4 == 0) && (ld_out % 4 == 0) && (d % 4 == 0) && ini16;
+  const bool al8 = ((uintptr_t)h % 8 == 0) && aligned16(out) && (ld_h % 4 == 0) && (ld_out % 4 == 0) && (d % 4 == 0) && ini16;
   const bool al4 = ((uintptr_t)h % 4 == 0) && ((uintptr_t)out % 8 == 0) && (ld_h % 2 == 0) && (ld_out % 2 == 0) && (d % 2 == 0) && ini8;
   CB_CHECK_ARG(!v.col_flags || (al8 && d % 256 == 0), CB_E_INVALID, "%s: flagged column ids need d %% 256 == 0 and 8-byte aligned rows", who);
   if (al8 && d >= 256) return launch_spmm<4, false, bf16_t>(v, hb, ld_h, d, ep, out, ld_out, st);
@@ -240,11 +240,11 @@ extern "C" int cb_spmm_csr_fused_f32(const cb_csr_view* g, const int32_t* row_id
   CB_CHECK_ARG(h && out_next, CB_E_INVALID, "%s: null pointer", who);
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "%s: dropout p out of range", who);
   CB_CHECK_ARG(!row_ids || (!acc_init && !h_bf16), CB_E_INVALID, "%s: a row subset needs fp32 rows and no running sums", who);
-  const bool al = ((uintptr_t)h % (h_bf16 ? 8 : 16) == 0) && ((uintptr_t)out_next % 16 == 0) && ld_h % 4 == 0 && ld_next % 4 == 0 &&
-                  (!mix_src || ((uintptr_t)mix_src % 16 == 0 && ld_mix % 4 == 0)) &&
-                  (!out_act || ((uintptr_t)out_act % 16 == 0 && ld_act % 4 == 0));
+  const bool al = ((uintptr_t)h % (h_bf16 ? 8 : 16) == 0) && aligned16(out_next) && ld_h % 4 == 0 && ld_next % 4 == 0 &&
+                  (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0)) &&
+                  (!out_act || (aligned16(out_act) && ld_act % 4 == 0));
   CB_CHECK_ARG(al && ld_h >= d && ld_next >= d, CB_E_INVALID, "%s: 16-byte aligned rows required", who);
-  CB_CHECK_ARG(!acc_init || ((uintptr_t)acc_init % 16 == 0 && ld_init % 4 == 0 && ld_init >= d), CB_E_INVALID,
+  CB_CHECK_ARG(!acc_init || (aligned16(acc_init) && ld_init % 4 == 0 && ld_init >= d), CB_E_INVALID,
                "%s: acc_init must be 16-byte aligned rows of at least d floats", who);
   Epilogue ep{row_scale, bias, 1, acc_init, ld_init, v.col_flags};
   FusedEpi fe{};
@@ -272,8 +272,8 @@ extern "C" int cb_spmm_csr_store_bwd_f32(const cb_csr_view* g, const float* h, i
   if (rc != CB_OK || v.n_rows == 0) return rc;
   CB_CHECK_ARG(h && out_gr && relu_bits, CB_E_INVALID, "%s: null pointer", who);
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "%s: dropout p / row offset out of range", who);
-  CB_CHECK_ARG(((uintptr_t)h % 16 == 0) && ((uintptr_t)out_gr % 16 == 0) && ld_h % 4 == 0 && ld_gr % 4 == 0 && ld_h >= d && ld_gr >= d &&
-                   (!out_g || ((uintptr_t)out_g % 16 == 0 && ld_g % 4 == 0 && ld_g >= d)) && ((uintptr_t)relu_bits % 8 == 0),
+  CB_CHECK_ARG(aligned16(h) && aligned16(out_gr) && ld_h % 4 == 0 && ld_gr % 4 == 0 && ld_h >= d && ld_gr >= d &&
+                   (!out_g || (aligned16(out_g) && ld_g % 4 == 0 && ld_g >= d)) && ((uintptr_t)relu_bits % 8 == 0),
                CB_E_INVALID, "%s: 16-byte aligned rows required", who);
   Epilogue ep{row_scale, nullptr, 0, nullptr, 0, v.col_flags};
   FusedEpi fe{};
@@ -344,7 +344,7 @@ extern "C" int cb_spmm_csr_store_bwd_mix_f32(const cb_csr_view* g, const float* 
   const int64_t N = v.n_rows;
   CB_CHECK_ARG(h && out_gr && out_m && relu_bits, CB_E_INVALID, "%s: null pointer", who);
   CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "%s: dropout p / row offset out of range", who);
-  CB_CHECK_ARG(((uintptr_t)h % 16 == 0) && ((uintptr_t)out_gr % 16 == 0) && ((uintptr_t)out_m % 16 == 0) && ld_h % 4 == 0 && ld_gr % 4 == 0 && ld_m % 4 == 0 &&
+  CB_CHECK_ARG(aligned16(h) && aligned16(out_gr) && aligned16(out_m) && ld_h % 4 == 0 && ld_gr % 4 == 0 && ld_m % 4 == 0 &&
                    ld_h >= d && ld_gr >= d && ld_m >= d && ((uintptr_t)relu_bits % 8 == 0),
                CB_E_INVALID, "%s: 16-byte aligned rows required", who);
   CB_CHECK_ARG(n_mix >= 0 && n_mix <= 2 && (n_mix == 0 || (mix_g && mix_pos && mix_seeds)), CB_E_INVALID, "%s: 0..2 compact mix operands", who);
@@ -359,7 +359,7 @@ extern "C" int cb_spmm_csr_store_bwd_mix_f32(const cb_csr_view* g, const float* 
   fe.out_act = out_m; fe.ld_act = ld_m; fe.out_next = out_gr; fe.ld_next = ld_gr; fe.d = (int)d;
   fe.mx_n = n_mix; fe.mx_c = c_mix;
   for (int q = 0; q < n_mix; ++q) {
-    CB_CHECK_ARG(mix_g[q] && mix_pos[q] && (uintptr_t)mix_g[q] % 16 == 0, CB_E_INVALID, "%s: null or misaligned mix operand %d", who, q);
+    CB_CHECK_ARG(mix_g[q] && mix_pos[q] && aligned16(mix_g[q]), CB_E_INVALID, "%s: null or misaligned mix operand %d", who, q);
     fe.mx_g[q] = mix_g[q]; fe.mx_pos[q] = mix_pos[q]; fe.mx_seed[q] = mix_seeds[q];
   }
   fe.cs_partial = colsum ? (float*)ws2 : nullptr;

@@ -378,7 +378,7 @@ extern "C" int cb_topk_replace_f32(const float* q, int64_t ldq, const float* t, 
   int rb, ctl, ns, tps;
   topk_geometry(B, N, rb, ctl, ns, tps);
   hipStream_t st = (hipStream_t)stream;
-  const int aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)t % 16 == 0) && ldq % 4 == 0 && ldt % 4 == 0;
+  const int aligned = aligned16(q) && aligned16(t) && ldq % 4 == 0 && ldt % 4 == 0;
   static const bool plain = getenv("CB_GEMM_PLAIN_F32") != nullptr;
   if (aligned && !plain && D % 4 == 0 && ldq < (1 << 22) && ldt < (1 << 22))
     hipLaunchKernelGGL(k_topk_scores_l3, dim3((unsigned)rb, (unsigned)ns), dim3(256), 0, st, q, ldq, t, ldt, B, (int)N, (int)D, (int)K,

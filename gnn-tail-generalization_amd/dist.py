@@ -20,7 +20,7 @@ parallel, which a peer-by-peer order would give up):
 
     for k: [producer of row chunk k, e.g. the layer GEMM] -> pack slice k -> all_to_all_single(async)   [RCCL stream, xGMI]
     interior pass: raw sums over local columns                [compute stream, under the exchange]
-    for k: wait(k) -> halo pass k on top of the running sums (cb_spmm_csr_acc_f32); the last one applies the epilogue
+    for k: wait(k) -> halo pass k on top of the running sums (cb_spmm_csr_f32 with acc_init); the last one applies the epilogue
 
 so pack k+1, the GEMM rows of chunk k+1 and halo pass k-1 all run while slice k is on the links; what stays
 exposed is the first chunk's producer + pack and the last slice's halo pass.  K = 1 is the two-pass form of
@@ -28,7 +28,7 @@ round 2 (bit for bit).  COLDBREW_OVERLAP=0 keeps the single-pass form (one CSR o
 after a blocking exchange); COLDBREW_EXCHANGE=allgather the all-gather baseline (equal-row partition only);
 COLDBREW_HALO_WIRE=bf16 (opt-in, outside the 1e-4 parity) halves the bytes on the links: the pack kernel
 writes bf16 (cb_gather_rows_bf16_f32) and the halo passes read the wire buffer as it arrived
-(cb_spmm_csr_acc_bf16_f32) — no conversion pass on either side.
+(cb_spmm_csr_f32 with h_bf16 and acc_init) — no conversion pass on either side.
 Push / pull cover (default, COLDBREW_HALO_COVER=0 switches it off): a remote edge u -> v can be served by shipping the SOURCE row h[u]
 (pull: what the plain halo does) or by shipping the owner-side PARTIAL SUM of the destination row, sum of h[u] over the owner's sources
 of v (push).  Per ordered rank pair the requester picks a vertex cover of the pair's remote-edge bipartite graph (every edge to its

@@ -1,4 +1,4 @@
-"""Normalisation tricks of GNN_model/norm_tricks.py on hand-written reductions (csrc/cb_elementwise.hip):
+"""Normalisation tricks of GNN_model/norm_tricks.py on hand-written reductions (csrc/cb_norms.hip):
 node_norm (row-wise), mean_norm / pair_norm / BatchNorm1d (column statistics), each with its backward.
 Only [d]-sized vectors are touched by torch arithmetic; every pass over an [N, d] matrix is a HIP kernel."""
 import contextlib

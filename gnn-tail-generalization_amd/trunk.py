@@ -193,6 +193,13 @@ def _spmm_t(graph, gr):
     return graph.spmm(gr, transpose=True)
 
 
+def _colsum_ws(lib, rows, d, device, want=True):
+    """(colsum [d], its workspace, the workspace's size in bytes) for the column sums of a [rows, d] pass; (None, a 16-byte buffer, 0) if not wanted."""
+    colsum = torch.empty(d, dtype=torch.float32, device=device) if want else None
+    wsb = lib.cb_colsum_workspace_bytes(rows, d) if want else 0
+    return colsum, torch.empty(max(wsb, 16), dtype=torch.uint8, device=device), wsb
+
+
 def _layer_bwd_fold(g, bits, row_scale, p, seed, row0, c_act, c_mix, want_colsum, mix_g, mix_pos, mix_seeds, out=None, cs=None):
     """cb_trunk_layer_bwd_fold_f32: layer 0's store backward on all rows that also folds the mix gradients — (b * dY', dbias, m) with
     m = c_mix * (dropout_bwd(g) + sum_q dropout_bwd_q(mix_g[q])); mix_pos[q]: None for a dense operand, else its int32 position map.
@@ -203,13 +210,9 @@ def _layer_bwd_fold(g, bits, row_scale, p, seed, row0, c_act, c_mix, want_colsum
     if out is None:
         out = torch.empty_like(g)
     m = torch.empty_like(g)
-    colsum = torch.empty(d, dtype=torch.float32, device=g.device) if want_colsum else None
-    wsb = lib.cb_colsum_workspace_bytes(rows, d) if want_colsum else 0
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=g.device)
+    colsum, ws, wsb = _colsum_ws(lib, rows, d, g.device, want_colsum)
     k = len(mix_g)
-    colsum2 = torch.empty(d, dtype=torch.float32, device=g.device) if cs is not None else None
-    ws2b = lib.cb_colsum_workspace_bytes(rows, d) if cs is not None else 0
-    ws2 = torch.empty(max(ws2b, 16), dtype=torch.uint8, device=g.device) if cs is not None else None
+    colsum2, ws2, ws2b = _colsum_ws(lib, rows, d, g.device) if cs is not None else (None, None, 0)
     with torch.cuda.device(g.device):
         _lib.check(lib.cb_trunk_layer_bwd_fold_f32(_lib.ptr(g), _lib.ptr(bits), _lib.ptr(row_scale), _lib.ptr(out), rows, d, float(p), ctypes.c_uint64(seed),
                                                    ops.seed_dev_ptr(), int(row0), float(c_act), float(c_mix), k,
@@ -232,9 +235,7 @@ def _layer_bwd(g, bits, row_scale, gx0, accumulate, p, seed, row0, c_act, c_mix,
     rows, d = g.shape
     if out is None:
         out = torch.empty(g.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=g.device)
-    colsum = torch.empty(d, dtype=torch.float32, device=g.device) if want_colsum else None
-    wsb = lib.cb_colsum_workspace_bytes(rows, d) if want_colsum else 0
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=g.device)
+    colsum, ws, wsb = _colsum_ws(lib, rows, d, g.device, want_colsum)
     with torch.cuda.device(g.device):
         _lib.check(lib.cb_trunk_layer_bwd_f32(_lib.ptr(g), _lib.ptr(bits), _lib.ptr(row_scale), _lib.ptr(out), int(out_bf16),
                                               _lib.ptr(gx0), int(accumulate), rows, d, float(p), ctypes.c_uint64(seed), ops.seed_dev_ptr(),
@@ -249,9 +250,7 @@ def _layer_bwd_rows(g_c, rows_idx, bits, row_scale, p, seed, row0, c_act, want_c
     lib = _lib.load()
     n_c, d = g_c.shape
     out = torch.empty_like(g_c) if out is None else out
-    colsum = torch.empty(d, dtype=torch.float32, device=g_c.device) if want_colsum else None
-    wsb = lib.cb_colsum_workspace_bytes(n_c, d) if want_colsum else 0
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=g_c.device)
+    colsum, ws, wsb = _colsum_ws(lib, n_c, d, g_c.device, want_colsum)
     with torch.cuda.device(g_c.device):
         _lib.check(lib.cb_trunk_layer_bwd_rows_f32(_lib.ptr(g_c), _lib.ptr(rows_idx), n_c, _lib.ptr(bits), _lib.ptr(row_scale), _lib.ptr(out), d, float(p),
                                                    ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), float(c_act), _lib.ptr(g2), ctypes.c_uint64(seed2),
@@ -264,9 +263,7 @@ def _input_bwd(g, add, act, p, seed, row0):
     lib = _lib.load()
     rows, d = g.shape
     out = torch.empty_like(g)
-    colsum = torch.empty(d, dtype=torch.float32, device=g.device)
-    wsb = lib.cb_colsum_workspace_bytes(rows, d)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=g.device)
+    colsum, ws, wsb = _colsum_ws(lib, rows, d, g.device)
     with torch.cuda.device(g.device):
         _lib.check(lib.cb_trunk_input_bwd_f32(_lib.ptr(g), _lib.ptr(add), _lib.ptr(act), _lib.ptr(out), rows, d, float(p),
                                               ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(colsum), _lib.ptr(ws), wsb,
@@ -283,9 +280,7 @@ def _input_bwd_multi(g, seed, g_mix, seeds_mix, c_mix, act, p, row0, act_bits=No
     lib = _lib.load()
     rows, d = g.shape
     out = torch.empty_like(g)
-    colsum = torch.empty(d, dtype=torch.float32, device=g.device)
-    wsb = lib.cb_colsum_workspace_bytes(rows, d)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=g.device)
+    colsum, ws, wsb = _colsum_ws(lib, rows, d, g.device)
     n = len(g_mix)
     ptrs = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in g_mix])
     seeds = (ctypes.c_uint64 * max(n, 1))(*[int(s) for s in seeds_mix])

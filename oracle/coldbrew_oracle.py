@@ -531,3 +531,46 @@ def dropout_keep_mask(shape, p, seed, offset=0, seed_dev=0):
     words = dropout_words(int(seed) + int(seed_dev), np.uint64(q0) + np.arange(nq, dtype=np.uint64))
     lo = offset & 3
     return (words.reshape(-1)[lo:lo + n] >= np.uint32(dropout_threshold(p))).reshape(shape)
+
+
+# --------------------------------------------------------------------------------------
+# Column sums: the two-stage order of the library's fixed-order reductions (no float atomics).  include/coldbrew_hip.h promises that the column sums
+# of cb_trunk_layer_bwd_f32, its _rows / _fold forms, cb_trunk_input_bwd_f32 / _multi_cs_f32 and cb_act_bwd_f32 do not depend on scheduling and that
+# the trunk entries agree bit for bit; this is the order itself, in float32 (tests/test_colsum_host.py, tests/test_gpu_colsum_order.py).
+#   stage 1  nb = min(ceil(rows / 64), 2048) blocks, block b owning the rpb = ceil(rows / nb) rows from b * rpb on; row lane j of `row_lanes` adds rows
+#            b * rpb + j, + row_lanes, ... one after the other; the block's partial is (((0 + s_0) + s_1) + ...)
+#   stage 2  thread t of 256 adds partials t, t + 256, ... one after the other; a halving tree (off = 128 ... 1) over the 256 threads follows
+# row_lanes: 4 for the wave-per-row trunk kernels (csrc/cb_rowpass.h), 256 // min(64, ceil(d / 4)) for cb_act_bwd_f32.
+# --------------------------------------------------------------------------------------
+COLSUM_MAX_BLOCKS, COLSUM_THREADS = 2048, 256
+
+
+def colsum_two_stage(x, row_lanes, reverse_lanes=False):
+    """float32 [d]: the column sums of the float32 summands x [rows, d] in the kernels' order.  reverse_lanes adds the row lanes of a block last to
+    first instead — another order, for the tests that show the pinned one can be told from its neighbours."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rows, d = x.shape
+    nb = min(-(-rows // 64), COLSUM_MAX_BLOCKS)
+    rpb = -(-rows // nb)
+    steps = -(-rpb // row_lanes)
+    # [nb, steps, row_lanes, d] with zeros where a block or a lane has no row (s + 0 == s: the kernels' idle lanes hold 0 as well)
+    slab = np.zeros((nb * rpb, d), dtype=np.float32)
+    slab[:rows] = x
+    lanes = np.zeros((nb, steps * row_lanes, d), dtype=np.float32)
+    lanes[:, :rpb] = slab.reshape(nb, rpb, d)
+    lanes = lanes.reshape(nb, steps, row_lanes, d)
+    s = np.zeros((nb, row_lanes, d), dtype=np.float32)
+    for i in range(steps):
+        s = s + lanes[:, i]
+    partial = np.zeros((nb, d), dtype=np.float32)
+    for j in (reversed(range(row_lanes)) if reverse_lanes else range(row_lanes)):
+        partial = partial + s[:, j]
+    t = np.zeros((COLSUM_THREADS, d), dtype=np.float32)
+    for p0 in range(0, nb, COLSUM_THREADS):
+        chunk = partial[p0:p0 + COLSUM_THREADS]
+        t[:len(chunk)] = t[:len(chunk)] + chunk
+    off = COLSUM_THREADS // 2
+    while off:
+        t[:off] = t[:off] + t[off:2 * off]
+        off //= 2
+    return t[0].copy()

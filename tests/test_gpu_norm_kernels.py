@@ -1,4 +1,4 @@
-"""The five norm kernels of csrc/cb_elementwise.hip (cb_node_norm_fwd/bwd_f32, cb_colstats_f32, cb_col_affine_f32, cb_col_bwd_combine_f32)
+"""The five norm kernels of csrc/cb_norms.hip (cb_node_norm_fwd/bwd_f32, cb_colstats_f32, cb_col_affine_f32, cb_col_bwd_combine_f32)
 through norms_hip.py and through the C ABI, against float64 on the CPU, at the sizes where their loops take a second trip: d > 64 per
 lane and ragged d in the node-norm kernels, d > 256 and row slabs longer than 64 rows in the column statistics, more than 256 partials
 in the finish kernel, more than 2048 x 256 elements in the element-wise pair.

@@ -17,7 +17,7 @@ words, so every element shows its mask bit.
 Call sites of keep4 (csrc/) and the test that reaches each:
   cb_elementwise.hip  k_dropout, aligned quad / straddling quad       test_dropout_equals_the_host_mask (offsets with offset & 3 == 0 / != 0), _scalar_branch_,
                                                                       _backward_, _adds_the_device_seed_word; two-kernel cases of test_gemm_output_dropout
-                      k_trunk_bwd seed / seed2                        test_layer_backward_draws_both_host_masks, _on_compact_rows_ (RIDX), test_single_operand_input_backward_ (MODE 1)
+  cb_trunk_bwd.hip    k_trunk_bwd seed / seed2                        test_layer_backward_draws_both_host_masks, _on_compact_rows_ (RIDX), test_single_operand_input_backward_ (MODE 1)
                       k_trunk_bwd_fold seed / fo.seed[q]              test_layer_backward_fold_draws_three_host_masks
                       k_trunk_input_bwd_multi seed / mt.seed[l]       test_input_backward_draws_four_host_masks
                       k_trunk_store_rows                              test_store_rows_draws_the_host_mask
