@@ -328,11 +328,14 @@ __global__ void __launch_bounds__(256) k_topk_finish(const Cand* __restrict__ pa
   }
   // win[] is descending; the reference's order is ascending (sortidx[-K:])
   const float mx = win[0].v;
+  // no winner at all: every score of this query was NaN (a NaN in the query row; no comparison accepts one).  The reference's softmax
+  // of NaN scores yields NaN, so the row says so instead of reading as a plausible row of zeros; idx stays -1.
+  const bool none = win[0].i < 0;
   float den = 0.f, wgt[KMAX];
   for (int r = K - 1; r >= 0; --r) { wgt[r] = (win[r].i >= 0) ? expf(win[r].v - mx) : 0.f; den += wgt[r]; }
-  for (int r = 0; r < K; ++r) wgt[r] = den > 0.f ? wgt[r] / den : 0.f;
+  for (int r = 0; r < K; ++r) wgt[r] = none ? NAN : (den > 0.f ? wgt[r] / den : 0.f);
   for (int c = lane; c < D; c += 64) {
-    float s = 0.f;
+    float s = none ? NAN : 0.f;
     for (int r = K - 1; r >= 0; --r)
       if (win[r].i >= 0) s += wgt[r] * T[(int64_t)win[r].i * ldt + c];
     out[q * D + c] = s;

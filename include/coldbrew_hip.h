@@ -408,6 +408,12 @@ int cb_col_bwd_combine_f32(const float* g, const float* xh, const float* xs, con
  * One fp32-MFMA sweep with a running top-K in LDS (the B x N score matrix is never written) + a merge kernel.
  * out_idx [B,K] / out_w [B,K] (nullable) receive the selection and the softmax weights in ascending score order
  * (the order of `sortidx[-K:]`).  1 <= K <= 8.  ws: cb_topk_replace_workspace_bytes(B, N, K).
+ * Ties follow one total order: larger score first, then larger index — what a stable ascending argsort followed by [-K:]
+ * selects (torch's default argsort is not stable, so the reference itself leaves ties open).
+ * NaN: a query row that holds a NaN scores NaN against every teacher row and has no winner; its out row and its K weights
+ * are NaN and its K indices -1, as the reference's softmax of NaN scores propagates it.  The other rows are unaffected.
+ * NaN in individual teacher rows is outside the contract: such a row never wins, and what the remaining rows yield is not
+ * specified.
  * ---------------------------------------------------------------------------------- */
 size_t cb_topk_replace_workspace_bytes(int64_t B, int64_t N, int64_t K);
 int cb_topk_replace_f32(const float* q, int64_t ldq, const float* t, int64_t ldt, int64_t B, int64_t N, int64_t D, int32_t K,
