@@ -7,14 +7,19 @@ Every `[Linear, LayerNorm, GELU, Dropout]` group of a getMLP stack (utils.py:885
 around the top-K replacement (ops.semlp_part2_input).  Modules are built lazily as in the reference — on the CPU with torch's generator,
 then moved: same-seed initial weights are bit-identical to the reference's.
 
-Not built (NotImplementedError names the reason): GraphMLP, has_NCloss, --SEMLP__include_part1out=0.
+GraphMLP (:158-208) is built as the reference's own public names — GraphMLP, get_neighbor_contrastive_loss, cosine_sim — on the fused
+neighbour-contrastive loss (ops.neighbor_contrastive_loss, csrc/cb_ncloss.hip) and trained by trainer.train_graphMLP() through the
+GraphMLPStudent holder below.
+
+Not built (NotImplementedError names the reason): --train_which=GraphMLP routed through SEMLP.forward_part2 / trainer.main() (a follow-up,
+DESIGN.md §0), has_NCloss, --SEMLP__include_part1out=0.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..utils import HipLinear
+from ..utils import D, HipLinear, graphUtils
 
 TOPK_KERNEL_MAX = 8      # cb_topk_replace_f32 keeps K <= 8 candidates per lane
 
@@ -243,3 +248,97 @@ class SEMLP(nn.Module):
         if node_idx is not None:
             q = q[torch.as_tensor(np.asarray(node_idx), device=q.device, dtype=torch.long)]
         return ops.se_topk_replace(q.to(self.teacherSE.device), self.teacherSE, int(self.topK_2_replace)).detach()
+
+
+class GraphMLP(nn.Module):
+    """GraphMLP (https://arxiv.org/abs/2106.04051) as the reference restates it (MLP_model/__init__.py:158-188): a [Linear, LayerNorm, GELU,
+    Dropout(0.6), Linear] stack of width 256, a Linear head, and the neighbour-contrastive loss of the batch embeddings against the r-th
+    power of the normalised adjacency.  Built in the reference's order on the CPU with torch's generator, then moved: same-seed weights are
+    bit-identical; state_dict keys model.0.*, model.1.*, model.4.*, out_proj.*.
+    Deviations: the loss is evaluated only while self.training (the reference also evaluates it in its eval forwards and never reads it
+    there; here eval forwards leave .loss_NContrastive = None); a batch_idx entry beyond the power's node count raises ValueError (the
+    reference: IndexError)."""
+
+    def __init__(self, args, train_mask):
+        super().__init__()
+        self.dropout = 0.6          # reported in the paper (:162-163)
+        self.hidden_dim = 256
+        self.args = args
+        self.model = getMLP([args.num_feats, self.hidden_dim, self.hidden_dim], dropout=self.dropout)
+        self.out_proj = HipLinear(self.hidden_dim, args.num_classes_bkup)
+        self.train_mask = train_mask
+        self.train_idx = torch.where(self.train_mask == True)[0]      # noqa: E712  (:169)
+        if self.args.batch_size > len(self.train_idx):
+            print(f'\n\n    Batch size too large...\n Changing batch_size from {self.args.batch_size} to {len(self.train_idx)}!\n\n')
+            self.args.batch_size = len(self.train_idx)
+        self.adj_pow = None
+        self.to(args.device)
+
+    def power(self, edge_index):
+        """The device form of A~^r, built on the host at the first call (normalize_adj -> sparse_power -> ops.SparsePower) and kept."""
+        if self.adj_pow is None:
+            adj = graphUtils.normalize_adj(edge_index.detach().cpu())
+            self.adj_pow = ops.SparsePower(graphUtils.sparse_power(adj, self.args.graphMLP_r), self.out_proj.weight.device)
+        return self.adj_pow
+
+    def forward(self, x, edge_index=None, batch_idx=None):
+        """x: the already gathered batch [B, F]; batch_idx: its node ids.  Returns utils.D with .emb [B, C] and .loss_NContrastive."""
+        power = self.power(edge_index)
+        z = self.model(x)
+        info = D()
+        info.loss_NContrastive = get_neighbor_contrastive_loss(z, power, batch_idx, self.args.graphMLP_tau) if self.training else None
+        info.emb = self.out_proj(z)
+        return info
+
+    def get_emb4linkp(self, x, edge_index, mask=None):
+        raise NotImplementedError
+
+
+def get_neighbor_contrastive_loss(z, adj_pow, batch_idx, tau):
+    """:190-198 on the fused kernels.  adj_pow: an ops.SparsePower, or a torch sparse tensor that is converted on every call."""
+    if not isinstance(adj_pow, ops.SparsePower):
+        adj_pow = ops.SparsePower(adj_pow, z.device)
+    return ops.neighbor_contrastive_loss(z, adj_pow, batch_idx, tau)
+
+
+def cosine_sim(x):
+    """:200-208: pair-wise cosine similarity [N, N] (GEMM + one scaling pass)."""
+    return ops.cosine_sim(x)
+
+
+class GraphMLPStudent(nn.Module):
+    """What the reference's SEMLP is while it trains GraphMLP (:51-75, :101-138 with SEMLP__downgrade_to_MLP): `alphas` ([1e-4, 1e-4], never given
+    a gradient) and `part2` = GraphMLP, so that the checkpoint has the reference's keys (alphas, part2.model.0.weight, ...,
+    part2.out_proj.bias) and loads from a reference checkpoint and into one.  part2 is built lazily by the first forward_part2, as there."""
+
+    def __init__(self, args, data):
+        super().__init__()
+        self.args = args
+        self.train_mask, self.test_mask = data.train_mask, data.test_mask
+        self.train_idx, self.test_idx = data.train_idx, data.test_idx
+        if self.args.batch_size > len(self.train_idx):
+            print(f'\n\n    Batch size too large...\n Changing batch_size from {self.args.batch_size} to {len(self.train_idx)}!\n\n')
+            self.args.batch_size = len(self.train_idx)
+        self.part2 = None
+        self.alphas = nn.Parameter(torch.tensor([0.0001, 0.0001]), requires_grad=True)
+        self.loss_NContrastive = None
+        self.on_build = None
+        self._idx = (None, None)
+
+    index_on_device = SEMLP.index_on_device
+
+    def forward_part2(self, x, batch_idx=None, edge_index=None):
+        if batch_idx is not None:
+            x = ops.gather_rows_by_index(x, self.index_on_device(batch_idx, x.device))
+        if self.part2 is None:
+            self.part2 = GraphMLP(self.args, self.train_mask)
+            if self.on_build is not None:
+                self.on_build('part2', self.part2)
+            if getattr(self, 'optfun', None) is not None:
+                self.opt = self.optfun(self.parameters(), lr=self.args.lr, weight_decay=self.args.weight_decay)
+        res = self.part2(x, edge_index=edge_index, batch_idx=batch_idx)
+        self.loss_NContrastive = res.loss_NContrastive
+        return res.emb
+
+    def forward(self, x, edge_index=None):
+        return

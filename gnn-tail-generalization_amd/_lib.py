@@ -151,6 +151,15 @@ SIGNATURES = {
     'cb_mse_rows_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
     'cb_part2_assemble_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
     'cb_part2_assemble_bwd_f32': (ctypes.c_int, [_P, _I64, _P, _P, _I64, _I64, _P, _P, _SZ, _P]),
+    'cb_ncloss_positions_i64': (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P]),
+    'cb_ncloss_row_norms_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P]),
+    'cb_cosine_scale_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _P]),
+    'cb_ncloss_uses_limb_core': (ctypes.c_int, [_P, _I64, _I64]),
+    'cb_ncloss_workspace_bytes': (_SZ, [_I64, _I32]),
+    'cb_ncloss_fwd_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_float, _P, _P, _P, _I64, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    'cb_ncloss_normalize_rows_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P]),
+    'cb_ncloss_bwd_slab_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_float, _P, _P, _I64, _I64, _I32, _P, _I64, _P]),
+    'cb_ncloss_bwd_finish_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -130,6 +130,49 @@ __device__ __forceinline__ void store_rowmajor_T(const RowFrag<BMT, BKT>& f, flo
 
 // "k-major" operand: global [k][n] with n contiguous (B of NN; both operands of TN): straight copy.
 // thread t: n quad = t % (BNT/4), k = t / (BNT/4) + (1024/BNT) * j
+// One tile of A[m0.., :] x B[n0.., :]^T with BOTH operands k-contiguous ("row" operands), fp32-input MFMA, LDS double-buffered: the K loop of the
+// sweeps that fold their score tiles instead of writing them (cb_topk.hip k_topk_scores, cb_ncloss.hip k_nc_sweep_f32).  acc must be zeroed by the
+// caller; on return every wavefront has passed the loop's last barrier, so smem is free for the epilogue.
+template <class TL>
+__device__ __forceinline__ void rowrow_tile_k_loop(const float* __restrict__ A, int64_t lda, int64_t m0, int64_t M, const float* __restrict__ B, int64_t ldb,
+                                                   int n0, int N, int D, int aligned, float* __restrict__ smem, int wr, int wc, int lane, int t,
+                                                   f32x16 (&acc)[2][2]) {
+  constexpr int BM = TL::BM, BN = TL::BN, LDA = TL::LDA, LDB = TL::LDB;
+  auto As = [&](int b) { return smem + b * (BK * LDA); };
+  auto Bs = [&](int b) { return smem + 2 * BK * LDA + b * (BK * LDB); };
+  const int nk = (D + BK - 1) / BK;
+  RowFrag<BM, BK> fa;
+  RowFrag<BN, BK> fb;
+  if (aligned) {
+    load_rowmajor<true, BM, BK>(fa, A, lda, m0, M, 0, D, t);
+    load_rowmajor<true, BN, BK>(fb, B, ldb, n0, N, 0, D, t);
+  } else {
+    load_rowmajor<false, BM, BK>(fa, A, lda, m0, M, 0, D, t);
+    load_rowmajor<false, BN, BK>(fb, B, ldb, n0, N, 0, D, t);
+  }
+  store_rowmajor_T<BM, BK>(fa, As(0), t);
+  store_rowmajor_T<BN, BK>(fb, Bs(0), t);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) {
+      if (aligned) {
+        load_rowmajor<true, BM, BK>(fa, A, lda, m0, M, (kt + 1) * BK, D, t);
+        load_rowmajor<true, BN, BK>(fb, B, ldb, n0, N, (kt + 1) * BK, D, t);
+      } else {
+        load_rowmajor<false, BM, BK>(fa, A, lda, m0, M, (kt + 1) * BK, D, t);
+        load_rowmajor<false, BN, BK>(fb, B, ldb, n0, N, (kt + 1) * BK, D, t);
+      }
+    }
+    mfma_tile_step<LDA, LDB, BK, 2>(As(cur), Bs(cur), wr, wc, lane, acc);
+    if (kt + 1 < nk) {
+      store_rowmajor_T<BM, BK>(fa, As(cur ^ 1), t);
+      store_rowmajor_T<BN, BK>(fb, Bs(cur ^ 1), t);
+    }
+    __syncthreads();
+  }
+}
+
 template <int BNT, int BKT>
 struct KFrag {
   float4 v[BNT * BKT / 1024];

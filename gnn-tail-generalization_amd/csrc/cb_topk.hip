@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) k_topk_scores(const float* __restrict__ Q
                                                      int64_t B, int N, int D, int K, int tiles_per_split, int n_col_tiles,
                                                      Cand* __restrict__ partial, int aligned) {
   using TL = Tile<2, 2, BK, 2>;
-  constexpr int BM = TL::BM, BN = TL::BN, LDA = TL::LDA, LDB = TL::LDB;
+  constexpr int BM = TL::BM, BN = TL::BN;
   __shared__ __attribute__((aligned(16))) float smem[TL::SMEM_FLOATS];
   __shared__ Cand s_cand[32][8][KMAX];
   __shared__ Cand s_run[BM][KMAX];
@@ -193,8 +193,6 @@ __global__ void __launch_bounds__(256) k_topk_scores(const float* __restrict__ Q
   __shared__ int s_qn;
   static_assert(sizeof(QCand) * QCAP <= sizeof(s_cand), "the candidate queue lives in the unfiltered fold's scratch (never used together)");
   const FoldState fs{s_cand, s_run, s_thr, reinterpret_cast<QCand*>(&s_cand[0][0][0]), &s_qn};
-  auto As = [&](int b) { return smem + b * (BK * LDA); };
-  auto Bs = [&](int b) { return smem + 2 * BK * LDA + b * (BK * LDB); };
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
   const int64_t m0 = (int64_t)blockIdx.x * BM;
   const int split = blockIdx.y;
@@ -206,41 +204,11 @@ __global__ void __launch_bounds__(256) k_topk_scores(const float* __restrict__ Q
   if (t == 0) s_qn = 0;
   __syncthreads();
   const int ct_begin = split * tiles_per_split, ct_end = min(n_col_tiles, ct_begin + tiles_per_split);
-  const int nk = (D + BK - 1) / BK;
   for (int ct = ct_begin; ct < ct_end; ++ct) {
     const int n0 = ct * BN;
     f32x16 acc[2][2];
     zero_acc<2>(acc);
-    RowFrag<BM, BK> fa;
-    RowFrag<BN, BK> fb;
-    if (aligned) {
-      load_rowmajor<true, BM, BK>(fa, Q, ldq, m0, B, 0, D, t);
-      load_rowmajor<true, BN, BK>(fb, T, ldt, n0, N, 0, D, t);
-    } else {
-      load_rowmajor<false, BM, BK>(fa, Q, ldq, m0, B, 0, D, t);
-      load_rowmajor<false, BN, BK>(fb, T, ldt, n0, N, 0, D, t);
-    }
-    store_rowmajor_T<BM, BK>(fa, As(0), t);
-    store_rowmajor_T<BN, BK>(fb, Bs(0), t);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) {
-        if (aligned) {
-          load_rowmajor<true, BM, BK>(fa, Q, ldq, m0, B, (kt + 1) * BK, D, t);
-          load_rowmajor<true, BN, BK>(fb, T, ldt, n0, N, (kt + 1) * BK, D, t);
-        } else {
-          load_rowmajor<false, BM, BK>(fa, Q, ldq, m0, B, (kt + 1) * BK, D, t);
-          load_rowmajor<false, BN, BK>(fb, T, ldt, n0, N, (kt + 1) * BK, D, t);
-        }
-      }
-      mfma_tile_step<LDA, LDB, BK, 2>(As(cur), Bs(cur), wr, wc, lane, acc);
-      if (kt + 1 < nk) {
-        store_rowmajor_T<BM, BK>(fa, As(cur ^ 1), t);
-        store_rowmajor_T<BN, BK>(fb, Bs(cur ^ 1), t);
-      }
-      __syncthreads();
-    }
+    rowrow_tile_k_loop<TL>(Q, ldq, m0, B, T, ldt, n0, N, D, aligned, smem, wr, wc, lane, t, acc);
     fold_filtered(acc, smem, fs, n0, N, K, t);
   }
   for (int i = t; i < BM * K; i += 256) {

@@ -12,6 +12,9 @@ Student MLPs (reference lines are MLP_model/__init__.py / utils.py / the trainer
   ln_gelu_dropout   dropout(gelu(layer_norm(z)))     utils.py:898-903 (one row kernel per getMLP group; linear_ln_gelu_dropout: + its Linear)
   mse_rows          mse(pred, target[row_index])     trainer_node_classification.py:96,108
   semlp_part2_input [x | a1 * replaced | a0 * guess] MLP_model/__init__.py:102-108
+GraphMLP (MLP_model/__init__.py:158-208):
+  neighbor_contrastive_loss  -mean log(num / den) over the cropped adjacency power   :190-198 (Gram sweep, no [B, B] matrix in the forward)
+  cosine_sim        (x @ x.T) / (|x_i| |x_j|)        :200-208
 """
 import ctypes
 import os
@@ -892,3 +895,148 @@ def semlp_part2_input(alphas, x, part1_out, teacher_se, k):
     if x.dim() != 2 or part1_out.dim() != 2 or x.shape[0] != part1_out.shape[0] or alphas.shape != (2,):
         raise ValueError('semlp_part2_input expects x [B, F], part1_out [B, D] and the two alphas')
     return _Part2InputFn.apply(alphas, _c(x.detach().float()), _c(part1_out.detach().float()), teacher_se, int(k))
+
+
+# ---------------------------------------------------------------------------------------------
+# GraphMLP (MLP_model/__init__.py:158-208): the sparse adjacency power on the device, the neighbour-contrastive loss, cosine_sim
+# ---------------------------------------------------------------------------------------------
+class SparsePower:
+    """Device form of the adjacency power A~^r (utils.py:1242-1248), built once from the coalesced COO tensor: int32 `rowptr` [n + 1] / `col`
+    and fp32 `val` with ascending columns, for the matrix and (`rowptr_t` / `col_t` / `val_t`) for its transpose — the graph need not be
+    symmetric and the backward of the loss reads columns.  `n` = number of nodes."""
+
+    def __init__(self, adj_pow, device):
+        adj = adj_pow.detach().coalesce().cpu()
+        if adj.dim() != 2 or adj.shape[0] != adj.shape[1]:
+            raise ValueError('SparsePower expects a square sparse matrix')
+        self.n, self.nnz = int(adj.shape[0]), int(adj._nnz())
+        if self.nnz >= 2 ** 31:
+            raise ValueError(f'SparsePower: {self.nnz} non-zeros do not fit the int32 index contract (nnz < 2^31)')
+        idx, val = adj.indices(), adj.values().float()
+        self.device = torch.device(device)
+        self.rowptr, self.col, self.val = self._csr(idx[0], idx[1], val)
+        self.rowptr_t, self.col_t, self.val_t = self._csr(idx[1], idx[0], val)
+
+    def _csr(self, r, c, v):
+        order = torch.argsort(r * self.n + c, stable=True)
+        rowptr = torch.zeros(self.n + 1, dtype=torch.int64)
+        rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=self.n), 0)
+        return (rowptr.to(torch.int32).to(self.device), c[order].to(torch.int32).to(self.device), v[order].contiguous().to(self.device))
+
+
+def _ncloss_slab_rows(B):
+    from .tuning import T
+    rows = int(T.ncloss_slab_rows)
+    if rows <= 0:
+        rows = max(((1 << 28) // max(int(B), 1)) // 128 * 128, 128)
+    if rows % 128:
+        raise ValueError(f'tuning.T.ncloss_slab_rows={rows} must be a multiple of 128')
+    return rows
+
+
+class _NCLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, power, idx, tau):
+        from .tuning import T
+        lib = _lib.load()
+        z = _c(z)
+        B, D = z.shape
+        dev = z.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        pos = torch.empty(power.n, dtype=torch.int32, device=dev)
+        rep = torch.empty(B, dtype=torch.int32, device=dev)
+        rinv, num, den, w, u = (torch.empty(B, **f32) for _ in range(5))
+        loss = torch.empty(1, **f32)
+        m_count = torch.empty(1, dtype=torch.int32, device=dev)
+        cap = int(T.ncloss_max_splits)
+        wsb = lib.cb_ncloss_workspace_bytes(B, cap)
+        ws = _ws(wsb, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_ncloss_positions_i64(_lib.ptr(idx), B, power.n, _lib.ptr(pos), _lib.ptr(rep), _lib.stream_ptr()), 'cb_ncloss_positions_i64')
+            _lib.check(lib.cb_ncloss_fwd_f32(_lib.ptr(z), D, B, D, float(tau), _lib.ptr(power.rowptr), _lib.ptr(power.col), _lib.ptr(power.val), power.n,
+                                             _lib.ptr(idx), _lib.ptr(pos), _lib.ptr(rep), cap, _lib.ptr(rinv), _lib.ptr(num), _lib.ptr(den), _lib.ptr(w),
+                                             _lib.ptr(u), _lib.ptr(loss), _lib.ptr(m_count), _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_ncloss_fwd_f32')
+        ctx.power, ctx.tau, ctx.cap = power, float(tau), cap
+        ctx.save_for_backward(z, idx, pos, rep, rinv, w, u)
+        m_count = m_count.reshape(())
+        ctx.mark_non_differentiable(num, den, m_count)
+        return loss.reshape(()), num, den, m_count
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        from . import gemm
+        lib = _lib.load()
+        z, idx, pos, rep, rinv, w, u = ctx.saved_tensors
+        p = ctx.power
+        B, D = z.shape
+        dev = z.device
+        g = g.detach().reshape(1).to(torch.float32).contiguous()
+        zhat = torch.empty_like(z)
+        dzh = torch.empty_like(z)
+        dz = torch.empty_like(z)
+        slab = min(_ncloss_slab_rows(B), (B + 127) // 128 * 128)
+        P = torch.empty((min(slab, B), B), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_ncloss_normalize_rows_f32(_lib.ptr(z), D, B, D, _lib.ptr(rinv), _lib.ptr(zhat), _lib.stream_ptr()), 'cb_ncloss_normalize_rows_f32')
+            for r0 in range(0, B, slab):
+                rows = min(slab, B - r0)
+                _lib.check(lib.cb_ncloss_bwd_slab_f32(_lib.ptr(z), D, B, D, ctx.tau, _lib.ptr(rinv), _lib.ptr(w), r0, rows, ctx.cap, _lib.ptr(P), B,
+                                                      _lib.stream_ptr()), 'cb_ncloss_bwd_slab_f32')
+                gemm.mm_nn(P[:rows], zhat, out=dzh[r0:r0 + rows])
+            _lib.check(lib.cb_ncloss_bwd_finish_f32(_lib.ptr(z), D, _lib.ptr(zhat), B, D, ctx.tau, _lib.ptr(rinv), _lib.ptr(u), _lib.ptr(p.rowptr), _lib.ptr(p.col),
+                                                    _lib.ptr(p.val), _lib.ptr(p.rowptr_t), _lib.ptr(p.col_t), _lib.ptr(p.val_t), p.n, _lib.ptr(idx), _lib.ptr(pos),
+                                                    _lib.ptr(rep), _lib.ptr(g), _lib.ptr(dzh), _lib.ptr(dz), _lib.stream_ptr()), 'cb_ncloss_bwd_finish_f32')
+        return dz, None, None, None
+
+
+def neighbor_contrastive_loss(z, power, batch_idx, tau, return_parts=False):
+    """GraphMLP's neighbour-contrastive loss of the batch embeddings z [B, D] (MLP_model/__init__.py:190-198) against the adjacency power
+    `power` (SparsePower) cropped to the nodes batch_idx (int64 vector, host or device; numpy accepted):
+        loss = -mean_{num_i != 0} log(num_i / den_i),  den_i = sum_{j != i} exp(cos_ij / tau),  num_i = sum_{j != i} power[b_i, b_j] exp(cos_ij / tau)
+    with no B x B matrix in the forward (cb_ncloss_fwd_f32) and a slab of one in the backward (tuning.T.ncloss_slab_rows).  A node drawn more
+    than once is represented by its last position (the reference's CPU behaviour).  Returns the 0-dim loss; with return_parts also
+    (num [B], den [B], M 0-dim int32), detached.  M == 0 gives NaN, the reference's mean of an empty tensor.
+    Deviation: a batch_idx entry outside [0, power.n) raises ValueError (the reference fails with an IndexError inside its crop); for a device
+    batch_idx this check reads one number back."""
+    _lib.require_device(z)
+    if not isinstance(power, SparsePower):
+        raise TypeError('neighbor_contrastive_loss expects an ops.SparsePower (MLP_model.get_neighbor_contrastive_loss converts a torch sparse tensor)')
+    if z.dim() != 2 or z.dtype != torch.float32 or z.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError('neighbor_contrastive_loss expects a float32 [B, D] matrix with B >= 1')
+    if not torch.is_tensor(batch_idx):
+        import numpy as np
+        batch_idx = torch.as_tensor(np.asarray(batch_idx))
+    if batch_idx.dim() != 1 or batch_idx.dtype not in (torch.int64, torch.int32) or batch_idx.numel() != z.shape[0]:
+        raise ValueError('neighbor_contrastive_loss: batch_idx must be an integer vector with one node id per row of z')
+    lo, hi = int(batch_idx.min()), int(batch_idx.max())
+    if lo < 0 or hi >= power.n:
+        raise ValueError(f'neighbor_contrastive_loss: batch_idx holds node ids in [{lo}, {hi}], the adjacency power has {power.n} nodes')
+    if power.device != z.device:
+        raise ValueError('neighbor_contrastive_loss: the SparsePower lives on another device than z')
+    idx = _c(batch_idx.to(device=z.device, dtype=torch.int64))
+    loss, num, den, m = _NCLossFn.apply(z, power, idx, float(tau))
+    return (loss, num, den, m) if return_parts else loss
+
+
+def ncloss_core(z):
+    """'limb' or 'fp32': the MFMA core the sweeps of neighbor_contrastive_loss take for this z (cb_ncloss_uses_limb_core)."""
+    z = _c(z)
+    return 'limb' if _lib.load().cb_ncloss_uses_limb_core(_lib.ptr(z), z.shape[1], z.shape[1]) else 'fp32'
+
+
+def cosine_sim(x):
+    """Pair-wise cosine similarity [N, N] of the rows of x (MLP_model/__init__.py:200-208): x @ x.T on the MFMA GEMM, then one pass that
+    scales element (i, j) by 1 / (|x_i| |x_j|).  Materialises [N, N], as its definition says; no gradient (the loss has its own operator)."""
+    from . import gemm
+    lib = _lib.load()
+    _lib.require_device(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError('cosine_sim expects a float32 [N, D] matrix')
+    x = _c(x.detach())
+    N, D = x.shape
+    s = gemm.mm_nn(x, x.t().contiguous())
+    nrm = torch.empty(N, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.cb_ncloss_row_norms_f32(_lib.ptr(x), D, N, D, _lib.ptr(nrm), None, _lib.stream_ptr()), 'cb_ncloss_row_norms_f32')
+        _lib.check(lib.cb_cosine_scale_f32(_lib.ptr(s), N, N, _lib.ptr(nrm), _lib.stream_ptr()), 'cb_cosine_scale_f32')
+    return s

@@ -5,7 +5,8 @@ eval_headtail__traintest_v2 :226-236, evaluate :672-681, cal_acc_rounded100 :683
 Same class/method names, same per-epoch record layout and return shapes; the forward/backward runs on the HIP path.
 --train_which=TeacherGNN, LP (pure label propagation), SEMLP (teacher -> best checkpoint -> collect_SE -> part 1: regression of the
 student onto the teacher's structural embeddings -> part 2: classification on [x | virtual neighbours | guess]) and StudentBaseMLP (the
-residual MLP on the features alone) are built; GraphMLP is not (MLP_model/__init__.py says why).  --correct_and_smooth=1 (build extension) runs
+residual MLP on the features alone) are built; GraphMLP trains through train_graphMLP() / tools/train_graphmlp.py (main() does not
+route --train_which=GraphMLP there yet: DESIGN.md §0).  --correct_and_smooth=1 (build extension) runs
 the reference's Correct & Smooth post-processing (Label_propagation_model) on the trained model's probabilities after any of them.
 """
 import contextlib
@@ -19,7 +20,7 @@ from . import _lib, ops
 from . import optim as cb_optim
 from .data import load_data
 from .GNN_model.GNN_normalizations import TeacherGNN
-from .MLP_model import SEMLP
+from .MLP_model import SEMLP, GraphMLPStudent
 from .utils import (getMLP, join, load_model, save_graph_analyze, save_model, set_arch_configs, toitem)
 
 
@@ -225,6 +226,68 @@ class trainer:
                     print(f'epoch {epoch}, acc test {toitem(acc_test):.2}')
         torch.cuda.synchronize(self.device)
         _lib.device_status()
+        save_model(self.seMLP, join(self.modeldir, 'seMLP'))
+        results_arr2D = np.array(results_arr2D).T
+        npy_dir = f'{self.resdir}/seMLP'
+        wzRec(results_arr2D[0], f'acc_test@{npy_dir.replace("/", "@")}', want_save_npy=1, npy_dir=npy_dir)
+        if not self.args.want_headtail:
+            return results_arr2D[[0]]              # [1, epochs]
+        return results_arr2D[[0, -3, -2, -1]]      # [4, epochs]
+
+    def train_graphMLP(self):
+        """The reference's part-2 loop (train_seMLP_part2, :126-207) as it runs for --train_which=GraphMLP (main :27-29: downgraded to the
+        features alone, part 2 = MLP_model.GraphMLP): per epoch one np.random.choice training batch — CrossEntropyLoss + loss_NContrastive *
+        graphMLP_reg, one optimiser step (with graphMLP_reg == 0 the term is still evaluated and added: 0 * NaN stays NaN, as there) — one
+        eval-mode test batch and, with --want_headtail, the head / tail (/ isolated) node sets.  Same record layout and return shape as
+        train_seMLP_part2; the weights go to <modeldir>/seMLP with the reference's keys (alphas, part2.model.*, part2.out_proj.*)."""
+        self.args.SEMLP__downgrade_to_MLP = 1
+        self.seMLP = GraphMLPStudent(self.args, self.data).to(self.device)
+        self.seMLP.train_idx = self.seMLP.train_idx.to('cpu')
+        self.seMLP.train_mask = self.seMLP.train_mask.to('cpu')
+        self.seMLP.test_idx = self.seMLP.test_idx.to('cpu')
+        print('-' * 30, '\n         Start training part2 of SEMLP (GraphMLP)\n', '-' * 30)
+        self.optimizer = None
+        self.seMLP.optfun = self.optfun
+        results_arr2D = []
+        lrn_targ = self.data.y
+        x, ei = self.data.x, self.data.edge_index
+        for epoch in range(self.epochs):
+            self.seMLP.train()
+            batch_idx_train = np.random.choice(self.seMLP.train_idx, self.args.batch_size)
+            part2_out_train = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx_train)
+            if self.optimizer is None:
+                self.optimizer = self.seMLP.opt
+            idx = self.seMLP.index_on_device(batch_idx_train, part2_out_train.device)
+            loss_train = ops.nll_logsoftmax(part2_out_train, lrn_targ[idx].contiguous(), None, int(idx.numel()))
+            loss_train = loss_train + self.seMLP.loss_NContrastive * self.args.graphMLP_reg
+            self.optimizer.zero_grad()
+            loss_train.backward()
+            self.optimizer.step()
+
+            self.seMLP.eval()
+            with torch.no_grad():
+                batch_idx_train = np.random.choice(self.seMLP.test_idx, self.args.batch_size)
+                part2_out_test = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx_train)
+                idx = self.seMLP.index_on_device(batch_idx_train, part2_out_test.device)
+                acc_test = evaluate(part2_out_test, lrn_targ[idx], None) * 100
+                result = [toitem(acc_test)]
+                if self.args.want_headtail:
+                    subsets = [self.data.large_deg_idx, self.data.small_deg_idx] + ([self.data.zero_deg_idx] if self.args.use_special_split else [])
+                    for batch_idx in subsets:
+                        out = self.seMLP.forward_part2(x, edge_index=ei, batch_idx=batch_idx)
+                        idx = self.seMLP.index_on_device(batch_idx, out.device)
+                        _train, test = self.eval_headtail__traintest_v2(out, lrn_targ[idx], idx, cal_acc_rounded100)
+                        result.append(test)
+            results_arr2D.append(result)
+            self.bag.setdefault('graphMLP_loss_train', []).append(loss_train.detach())
+            if epoch % 20 == 0:
+                if self.args.use_special_split:
+                    print(f'epoch {epoch}, acc test {toitem(acc_test):.2f}, head_tail_iso = {result[-3:]}')
+                else:
+                    print(f'epoch {epoch}, acc test {toitem(acc_test):.2}')
+        torch.cuda.synchronize(self.device)
+        _lib.device_status()
+        self.bag['graphMLP_loss_train'] = [float(v) for v in self.bag.get('graphMLP_loss_train', [])]
         save_model(self.seMLP, join(self.modeldir, 'seMLP'))
         results_arr2D = np.array(results_arr2D).T
         npy_dir = f'{self.resdir}/seMLP'

@@ -65,5 +65,11 @@ class Tuning:
     # a level orientation of the sharded row-sparse backward is built while the level keeps at most this share of the edges
     support_max_edge_frac: float = 0.9
 
+    # ---- neighbour-contrastive loss (ops.neighbor_contrastive_loss, cb_ncloss.hip) ----------------------------------------------------------
+    # rows of the backward's P slab (a multiple of 128).  0: the largest multiple of 128 with rows * B <= 2^28 floats (1 GiB), at least 128
+    ncloss_slab_rows: int = 0
+    # cap on the column slabs a row block's sweep is split into.  0: the rule of the top-K sweep (about four blocks per CU)
+    ncloss_max_splits: int = 0
+
 
 T = Tuning()

@@ -373,3 +373,80 @@ def load_model(net, cwd, verbose=True, strict=True, multiGPU=False):   # utils.p
         net.load_state_dict(sd, strict=strict)
     if verbose:
         print(f'---››››  LOAD success! from {cwd}\n\n\n')
+
+
+class graphUtils:
+    """The sparse-adjacency helpers GraphMLP's ingest uses (utils.py:1124-1137, 1204-1214, 1226-1276), with the reference's names and
+    signatures.  Host side: they take torch tensors (any device; the model hands them CPU tensors once per run, like datasets.py) and
+    return COALESCED torch sparse COO tensors."""
+
+    @staticmethod
+    def remove_self_loops(edge_index):                                      # utils.py:1124-1128
+        return edge_index[:, edge_index[0] != edge_index[1]]
+
+    @staticmethod
+    def add_self_loops(edge_index, num_nodes=None):                         # utils.py:1130-1137
+        if num_nodes is None:
+            num_nodes = int(edge_index.max() + 1)
+        loop = torch.arange(0, num_nodes, dtype=torch.long, device=edge_index.device)
+        return torch.cat([edge_index, torch.stack([loop, loop])], dim=1)
+
+    @staticmethod
+    def edge_index_to_sparse_adj(edge_index, num_nodes=None, edge_weight=None):      # utils.py:1204-1214 (multi-edges add up)
+        if num_nodes is None:
+            num_nodes = int(edge_index.max() + 1)
+        if edge_weight is None:
+            edge_weight = torch.ones(edge_index.shape[1], dtype=torch.float32, device=edge_index.device)
+        return torch.sparse_coo_tensor(edge_index, edge_weight.float(), size=(num_nodes, num_nodes), device=edge_index.device).coalesce()
+
+    @staticmethod
+    def normalize_adj(edge_index, num_nodes=None):
+        """A~ = D^-1/2 (A without self loops + I) D^-1/2 with D the row sums (utils.py:1226-1241); a multi-edge counts with its multiplicity.
+        The reference multiplies by a dense diag(D^-1/2) [N, N] turned sparse; here the values are scaled as (a_ij * d_j) * d_i in float32,
+        the association its two products `mm(D, mm(A, D))` produce."""
+        if num_nodes is None:
+            num_nodes = int(edge_index.max() + 1)
+        edge_index = graphUtils.add_self_loops(graphUtils.remove_self_loops(edge_index), num_nodes)
+        adj = graphUtils.edge_index_to_sparse_adj(edge_index, num_nodes)
+        idx, val = adj.indices(), adj.values()
+        deg = torch.zeros(num_nodes, dtype=torch.float32, device=val.device).index_add_(0, idx[0], val)
+        d = deg ** (-1 / 2)
+        return torch.sparse_coo_tensor(idx, (val * d[idx[1]]) * d[idx[0]], size=(num_nodes, num_nodes)).coalesce()
+
+    @staticmethod
+    def sparse_power(x, N):                                                 # utils.py:1242-1248
+        assert N > 0
+        x0 = x
+        for _ in range(N - 1):
+            x = torch.sparse.mm(x, x0)
+        return x.coalesce()
+
+    @staticmethod
+    def subgraph(subset, edge_index, edge_attr=None, relabel_nodes=True, num_nodes=None):
+        """The edges with both ends in `subset`, relabelled to positions in it (utils.py:1249-1267).  A node that occurs more than once in
+        `subset` is relabelled to its LAST position — what the reference's `n_idx[subset] = arange(len(subset))` leaves on the CPU, stated
+        here as a maximum so that it does not depend on the order in which an indexed assignment writes."""
+        device = edge_index.device
+        subset = torch.as_tensor(np.asarray(subset) if not torch.is_tensor(subset) else subset)
+        if subset.dtype == torch.bool:
+            subset = torch.where(subset)[0]
+        subset = subset.to(device=device, dtype=torch.long)
+        if num_nodes is None:
+            num_nodes = int(edge_index.max() + 1)
+        n_mask = torch.zeros(num_nodes, dtype=torch.bool, device=device)
+        n_mask[subset] = True
+        mask = n_mask[edge_index[0]] & n_mask[edge_index[1]]
+        edge_index = edge_index[:, mask]
+        edge_attr = edge_attr[mask] if edge_attr is not None else None
+        if relabel_nodes:
+            n_idx = torch.zeros(num_nodes, dtype=torch.long, device=device)
+            n_idx.scatter_reduce_(0, subset, torch.arange(subset.shape[0], device=device), reduce='amax', include_self=True)
+            edge_index = n_idx[edge_index]
+        return edge_index, edge_attr
+
+    @staticmethod
+    def crop_adj_to_subgraph(adj_mtx, subset_idx):                          # utils.py:1268-1276
+        adj_mtx = adj_mtx.coalesce()
+        n2 = len(subset_idx)
+        edge_index, edge_attr = graphUtils.subgraph(subset_idx, adj_mtx.indices(), adj_mtx.values(), relabel_nodes=True, num_nodes=adj_mtx.shape[0])
+        return torch.sparse_coo_tensor(edge_index, edge_attr, size=(n2, n2), device=adj_mtx.device).float().coalesce()

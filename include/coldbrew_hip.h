@@ -680,6 +680,58 @@ int cb_part2_assemble_f32(const float* x, int64_t F, const float* replaced, cons
 int cb_part2_assemble_bwd_f32(const float* g, int64_t F, const float* replaced, const float* part1_out, int64_t D, int64_t B,
                               float* dalphas, void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * GraphMLP's neighbour-contrastive loss (MLP_model/__init__.py:158-208; cb_ncloss.hip).  MFMA-bound Gram sweeps of the batch embeddings
+ * with themselves plus walks over the sparse adjacency power; no B x B matrix in the forward, a slab of one in the backward.
+ *     cos_ij = <z_i, z_j> * (rinv_i * rinv_j),  s_ij = exp(cos_ij / tau),  a = crop(adj_pow, batch_idx)      (:190-208, utils.py:1250-1276)
+ *     den_i = sum_{j != i} s_ij,  num_i = sum_{j != i} a_ij s_ij,  loss = -(1 / M) sum_{num_i != 0} log(num_i / den_i),  M = #{num_i != 0}
+ * The power arrives as CSR (int32 rowptr [n + 1] / col, fp32 val, columns ascending) and, for the backward, also as the CSR of its transpose.
+ * The sweeps evaluate s in fp32; the sparse walks (few pairs, but long sequential sums) work in float64 and round once per output element.
+ * No float atomics anywhere: every sum has a fixed order and two calls give the same bits.
+ * ---------------------------------------------------------------------------------- */
+
+/* pos [n]: the largest i with batch_idx[i] == node, else -1 (integer atomicMax: deterministic); rep [B]: pos[batch_idx[i]] == i.  Restates what
+ * `n_idx[subset] = torch.arange(...)` (utils.py:1261) leaves on the CPU for a batch drawn with replacement: the last occurrence represents the
+ * node, every other occurrence has an empty row and column in the cropped matrix.  An id outside [0, n) is never used as an index (rep = 0). */
+int cb_ncloss_positions_i64(const int64_t* batch_idx, int64_t B, int64_t n, int32_t* pos, int32_t* rep, void* stream);
+
+/* nrm[r] = |x_r|_2 and rinv[r] = 1 / |x_r|_2 of x [rows, D] (either may be NULL); a zero row gives rinv = inf, as `x_sum ** (-1)` (:207) does. */
+int cb_ncloss_row_norms_f32(const float* x, int64_t ldx, int64_t rows, int64_t D, float* nrm, float* rinv, void* stream);
+
+/* `cosine_sim` (:200-208) after the GEMM: s [N, N] = x @ x^T on entry, s_ij * (1 / (nrm_i * nrm_j)) on return.  N < 65536. */
+int cb_cosine_scale_f32(float* s, int64_t ld, int64_t N, const float* nrm, void* stream);
+
+/* 1 if the sweeps over z take the exact three-limb bf16-MFMA core (16-byte aligned rows, D % 4 == 0, CB_GEMM_PLAIN_F32 unset), 0 for the
+ * fp32-input MFMA core: the dispatch of cb_topk_replace_f32. */
+int cb_ncloss_uses_limb_core(const float* z, int64_t ldz, int64_t D);
+
+/* Forward.  z [B, D] (ldz), tau > 0; pos / rep from cb_ncloss_positions_i64; max_splits caps the number of column slabs a row block's sweep
+ * is split into (0: the rule of cb_topk_replace_f32, about four blocks per CU).  Writes rinv / num / den / w / u [B], loss [1], m_count [1]:
+ *     w_i = [num_i != 0] / (M tau den_i),  u_i = [num_i != 0] / (M tau num_i)      (the backward's row weights)
+ * M == 0 gives loss = NaN (the reference's mean of an empty tensor).  Four launches (row norms, sweep with the row-sum epilogue into
+ * per-slab partial sums in ws, one wavefront per batch row over the power's rows, a one-block finish); no host synchronisation.
+ * Traffic: the sweep reads z once per 128-row block and slab; 2 B^2 D flop.  ws: cb_ncloss_workspace_bytes(B, max_splits). */
+size_t cb_ncloss_workspace_bytes(int64_t B, int32_t max_splits);
+int cb_ncloss_fwd_f32(const float* z, int64_t ldz, int64_t B, int64_t D, float tau, const int32_t* rowptr, const int32_t* col,
+                      const float* val, int64_t n, const int64_t* batch_idx, const int32_t* pos, const int32_t* rep, int32_t max_splits,
+                      float* rinv, float* num, float* den, float* w, float* u, float* loss, int32_t* m_count, void* ws, size_t ws_bytes,
+                      void* stream);
+
+/* Backward (autograd of :190-208), with zh_i = z_i * rinv_i:
+ *     dzh_i = sum_{j != i} s_ij (w_i + w_j) zh_j - sum_j a_ij s_ij u_i zh_j - sum_j a_ji s_ji u_j zh_j
+ *     dz_i  = g * (dzh_i - <dzh_i, zh_i> zh_i) * rinv_i                                        (g: DEVICE pointer to the upstream scalar)
+ * cb_ncloss_normalize_rows_f32 writes zh [B, D] contiguous.  cb_ncloss_bwd_slab_f32 writes P [rows, ldp] = s_ij (w_i + w_j), 0 on the
+ * diagonal, for the batch rows row0 .. row0 + rows (row0 a multiple of 128) and all B columns: the caller multiplies it by zh with
+ * cb_gemm_nn_f32 into rows row0.. of dzh.  cb_ncloss_bwd_finish_f32 then subtracts the two sparse terms from dzh in place (one wavefront
+ * per batch row over the CSR row and the CSR row of the transpose; every row is written by its owner only) and writes dz [B, D]. */
+int cb_ncloss_normalize_rows_f32(const float* z, int64_t ldz, int64_t B, int64_t D, const float* rinv, float* zhat, void* stream);
+int cb_ncloss_bwd_slab_f32(const float* z, int64_t ldz, int64_t B, int64_t D, float tau, const float* rinv, const float* w, int64_t row0,
+                           int64_t rows, int32_t max_splits, float* P, int64_t ldp, void* stream);
+int cb_ncloss_bwd_finish_f32(const float* z, int64_t ldz, const float* zhat, int64_t B, int64_t D, float tau, const float* rinv, const float* u,
+                             const int32_t* rowptr, const int32_t* col, const float* val, const int32_t* rowptr_t, const int32_t* col_t,
+                             const float* val_t, int64_t n, const int64_t* batch_idx, const int32_t* pos, const int32_t* rep, const float* g,
+                             float* dzh, float* dz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
