@@ -7,6 +7,7 @@ The DGL-like query surface that GCNConv.forward touches is kept: in_degrees(),
 out_degrees(), number_of_edges(), number_of_nodes().
 """
 import math
+import typing
 
 import torch
 
@@ -266,7 +267,7 @@ class CSRGraph:
 
     def rows_only_fwd(self, plan):
         """Orientations of a rows-only forward that also evaluates the layer BELOW the last one on the rows the last layer reads — S_1, when the plan keeps
-        that support compact (else None): (fwd1, fwd0c, ids1, b1, s1) with fwd1 = the forward orientation on the rows of S_1 (sources: all node rows),
+        that support compact (else None): RowsOnlyFwd(fwd1, fwd0c, ids1, b1, s1) with fwd1 = the forward orientation on the rows of S_1 (sources: all node rows),
         fwd0c = the one on the rows of S_0 with its sources renumbered to positions in S_1 (every in-neighbour of a loss row is a member of S_1),
         ids1 = int32 node ids of S_1's rows, b1 = norm_in on them, s1 = the RowSpace.  Built once per plan."""
         hit = getattr(plan, '_rows_fwd', None)
@@ -280,7 +281,7 @@ class CSRGraph:
         fwd1 = self._support_fwd(s1, self.N, force=True)
         col_c = torch.index_select(s1.pos, 0, fwd0.col[:fwd0.E].long())
         fwd0c = CSRGraph.from_csr(fwd0.rowptr, col_c, s1.n, hub_threshold=self.hub_threshold)
-        plan._rows_fwd = (fwd1, fwd0c, s1.idx.to(torch.int32).contiguous(), self.norm_in[s1.idx].contiguous(), s1)
+        plan._rows_fwd = RowsOnlyFwd(fwd1, fwd0c, s1.idx.to(torch.int32).contiguous(), self.norm_in[s1.idx].contiguous(), s1)
         return plan._rows_fwd
 
     def _support_fwd(self, s0, n_out, force=False):
@@ -765,6 +766,22 @@ class RowSpace:
 
     def __init__(self, idx, pos, a):
         self.idx, self.pos, self.a, self.n = idx, pos, a, int(idx.numel())
+
+    def norm_in_of(self, graph):
+        """graph.norm_in on the rows of the space, gathered once and kept on the space."""
+        b = getattr(self, '_norm_in', None)
+        if b is None:
+            b = self._norm_in = graph.norm_in[self.idx].contiguous()
+        return b
+
+
+class RowsOnlyFwd(typing.NamedTuple):
+    """What CSRGraph.rows_only_fwd hands a rows-only forward (see there)."""
+    fwd1: object      # CSRGraph: the forward orientation on the rows of S_1, sources = all node rows
+    fwd0c: object     # CSRGraph: the one on the rows of S_0, sources renumbered to positions in S_1
+    ids1: object      # int32 node ids of S_1's rows
+    b1: object        # norm_in on them
+    s1: object        # the RowSpace of S_1
 
 
 class RowSupportPlan:

@@ -4,18 +4,24 @@
     for l < L:  X = dropout(X);  Y = GCNConv_l(X)  (widths F -> H -> ... -> H -> C);  X = relu(Y) for l < L - 1      GCN.py:109-131
     out = dropout(X)                                                                    (on the logits)             GCN.py:133
 
-One autograd node with the fused trunk's kernels (trunk.py): the dropout in front of layer 0 is applied by its GEMM while it stages x
-(cb_gemm_nn_indrop_f32), every hidden layer's aggregation stores ReLU mask words and the DROPPED activation in one pass (cb_spmm_csr_fused_f32
-without a mix source) and — between two hidden layers — also yields the next layer's transform (cb_spmm_gemm_fused_f32); the backward runs the
-reverse aggregation + dX contraction as one kernel (cb_spmm_gemm_f32), keeps ReLU masks as bits and regenerates dropout masks.  Hidden width
-256 (the fused store's row layout), one GPU or row shards (dist.ShardedGraph: the exchanges run inside the same helpers as the trunk's, the
-reverse aggregation + dX kernel as the last halo pass); every other shape takes the operator path (GCN.py _forward_modular), whose arithmetic and sequence
-of dropout seeds this node reproduces (tests/test_gpu_model.py::test_fused_stack_equals_modular_path; goldens case_nr_h256_*)."""
+One autograd node with the fused trunk's kernels and helpers (trunk.py; kernels per stage: DESIGN.md section 3, "Fused nodes"): ReLU masks are kept as
+bits, dropout masks are regenerated.  Hidden width 256 (the fused store's row layout), one GPU or row shards (dist.ShardedGraph); every other shape takes the
+operator path (GCN.py _forward_modular), whose arithmetic and sequence of dropout seeds this node reproduces
+(tests/test_gpu_model.py::test_fused_stack_equals_modular_path; goldens case_nr_h256_*)."""
+from typing import NamedTuple
+
 import torch
 
 from . import _lib, gemm, ops
-from .trunk import _exchanged, _fused_gemm, _fused_launch, _fused_spmm, _layer_bwd, _layer_bwd_rows, _spmm_t, agg_gemm_eligible, rows_only_enabled
+from .graph import weight_image
+from .trunk import (SavedRows, _collect_layer_params, _dw_regen, _exchanged, _fused_gemm, _fused_launch, _fused_spmm, _layer_bwd, _layer_bwd_rows, _layers,
+                    _save, _saved, _spmm_t, agg_gemm_eligible, rows_only_enabled)
 from .tuning import T
+
+
+StackCfg = NamedTuple('StackCfg', [('L', int), ('p', float), ('seeds', tuple), ('track', bool), ('loss_rows', object), ('rows_only', bool)])
+StackCfg.__doc__ = """What one call of the stack was asked for (second argument of _StackFn.apply): the fields of trunk.TrunkCfg that a stack without mix
+and bf16 rows has; seeds: L + 1 dropout seeds (one in front of every layer, one on the logits)."""
 
 
 def _plan_hint(graph, loss_rows, n_rows, ag, committed=False):
@@ -35,18 +41,28 @@ def eligible(tc, x, graph, want_les):
             and tc.args.dropout == tc.dropout and (hasattr(graph, 'spmm_gemm') or hasattr(graph, 'part')))
 
 
+def _rows_only(graph, cfg, n_rows, ag, bwd):
+    """(graph.RowsOnlyFwd, its plan) of a rows-only forward (trunk.py; one GPU, under the plan decision of the backward), else ro = None: the logits are read
+    on S_0 only, so the last aggregation (class width) runs on those rows, the last transform on the rows it gathers — S_1 —, and the last HIDDEN layer's
+    aggregation + store on S_1 too (cb_spmm_csr_fused_f32 with row_ids), wherever the plan keeps S_1 compact."""
+    if cfg.rows_only and bwd and cfg.L >= 2 and rows_only_enabled() and n_rows >= T.rows_only_min_nodes:
+        hint = _plan_hint(graph, cfg.loss_rows, n_rows, ag)
+        if hint is not None:
+            plan = graph.grad_support_plan(hint[0], cfg.L, max_frac=T.rowsparse_max_frac)
+            return graph.rows_only_fwd(plan), plan
+    return None, None
+
+
 class _StackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, cfg, x, *layer_params):
-        """layer_params = (W_0, bias_0, le_0 | None, W_1, ...).  cfg = (L, p, seeds[L + 1], track, loss_rows, rows_only): loss_rows = None or (bool mask [N],
-        count), the caller's promise that the output receives gradient in those rows only (ops.py "Row-sparse backward"); rows_only: ... and that it
-        READS the output in those rows only (trunk.py "Rows-only forward")."""
-        L, p, seeds, track, loss_rows_, rows_only = cfg
+        """layer_params = (W_0, bias_0, le_0 | None, W_1, ...); cfg: StackCfg."""
+        L, p, seeds, layers = cfg.L, cfg.p, cfg.seeds, _layers(layer_params)
         a, b = graph.norm_out, graph.norm_in
         row0 = int(getattr(graph, 'row_offset', 0))       # first global row of this rank's block (dropout masks are those of the unsharded tensor)
         x = x.contiguous()
-        bwd = bool(track) and any(ctx.needs_input_grad)
-        w0, _b0, le0 = layer_params[0:3]
+        bwd = bool(cfg.track) and any(ctx.needs_input_grad)
+        w0, _b0, le0 = layers[0]
         # layer 0: Z_0 = a * (dropout(x) W_0) + E_0, the dropout applied while the GEMM stages x where that form exists
         z = gemm.mm_nn_indrop(x, w0, p, seeds[0], row0, rowscale=a, addend=le0, out=_exchanged(graph, x.shape[0], w0.shape[1])) if p > 0 else None
         ctx.indrop = z is not None
@@ -58,31 +74,20 @@ class _StackFn(torch.autograd.Function):
         ag = agg_gemm_eligible(graph, 256, False)
         saved_in, saved_bits = [xd0], []
         z_ready = None
-        # Rows-only forward (trunk.py; one GPU, under the plan decision of the backward): the logits are read on S_0 only, so the last aggregation (class
-        # width) runs on those rows, the last layer's transform on the rows it gathers — S_1 —, and the last HIDDEN layer's aggregation + store on S_1 too
-        # (cb_spmm_csr_fused_f32 with row_ids), wherever the plan keeps S_1 compact.
-        ro = None
-        if rows_only and bwd and L >= 2 and rows_only_enabled() and x.shape[0] >= T.rows_only_min_nodes:
-            hint = _plan_hint(graph, loss_rows_, x.shape[0], ag)
-            if hint is not None:
-                plan_ = graph.grad_support_plan(hint[0], L, max_frac=T.rowsparse_max_frac)
-                ro = graph.rows_only_fwd(plan_)      # (fwd1, fwd0c, ids1, b1, s1) or None
-                if ro is not None:
-                    ro = ro + (plan_,)
+        ro, ro_plan = _rows_only(graph, cfg, x.shape[0], ag, bwd)
         for l in range(L - 1):            # hidden layers: aggregation with the ReLU / dropout store (+ the next hidden layer's transform)
-            _w, bias, _le = layer_params[3 * l: 3 * l + 3]
-            w1, _b1, le1 = layer_params[3 * (l + 1): 3 * (l + 1) + 3]
+            (_w, bias, _le), (w1, _b1, le1) = layers[l], layers[l + 1]
             sd = seeds[l + 1] if p > 0 else 0
             z = z_ready if z_ready is not None else z
             z_ready = None
             if ro is not None and l == L - 2:      # the last hidden layer: read by the last aggregation only, on S_1
-                ro[0].profile = getattr(graph, 'profile', None)
-                bits, cur, _ = _fused_launch(_lib.load(), graph, ro[0], z, None, bias, None, 1.0, 0.0, p, sd, False, want_bits=bwd, row_ids=ro[2], row_scale=ro[3])
-                s1 = ro[4]
+                ro.fwd1.profile = getattr(graph, 'profile', None)
+                bits, cur, _ = _fused_launch(_lib.load(), graph, ro.fwd1, z, None, bias, None, 1.0, 0.0, p, sd, False, want_bits=bwd, row_ids=ro.ids1,
+                                             row_scale=ro.b1)
+                s1 = ro.s1
                 le_c = ops.gather_rows_by_index(le1, s1.idx) if le1 is not None else None
                 z = gemm.mm_nn(cur, w1, rowscale=s1.a, addend=le_c)          # Z_{L-1} on the rows of S_1
             elif ag and l + 1 < L - 1:      # the next layer is H -> H: its transform leaves this layer's aggregation kernel
-                from .graph import weight_image
                 # (a forward that no backward follows leaves cur = None: the activations stayed on chip)
                 bits, cur, z_ready = _fused_gemm(graph, z, bias, None, 1.0, 0.0, p, sd, weight_image(w1), a, le1, want_bits=bwd)[:3]
             else:
@@ -92,45 +97,30 @@ class _StackFn(torch.autograd.Function):
                 saved_bits.append(bits)
                 saved_in.append(cur)
         z = z_ready if z_ready is not None else z
-        bias_last = layer_params[3 * (L - 1) + 1]
+        bias_last = layers[L - 1][1]
         # the last layer: no ReLU (GCN.py:127); then the dropout on the logits (GCN.py:133)
         if ro is not None:      # the logits on the loss rows (gathering the compact Z over the orientation renumbered to S_1)
-            plan_ = ro[5]
-            sp = plan_.space0
-            ro[1].profile = getattr(graph, 'profile', None)
-            b0 = getattr(sp, '_norm_in', None)
-            if b0 is None:
-                b0 = sp._norm_in = b[sp.idx].contiguous()
-            y_c = ro[1].spmm(z, row_scale=b0, bias=bias_last)
+            sp = ro_plan.space0
+            ro.fwd0c.profile = getattr(graph, 'profile', None)
+            y_c = ro.fwd0c.spmm(z, row_scale=sp.norm_in_of(graph), bias=bias_last)
             y = ops.expand_unread(y_c, sp, x.shape[0])      # the rows nobody may read: NaN (ops.unread_rows_fill)
             graph.rows_only_forwards = getattr(graph, 'rows_only_forwards', 0) + 1
         else:
             y = graph.aggregate(z, False, b, bias_last, False) if hasattr(graph, 'part') else graph.spmm(z, row_scale=b, bias=bias_last)
         out = ops._dropout_raw(y, p, seeds[L], row0 * y.shape[1]) if p > 0 else y
-        ctx.in_last_compact = bwd and ro is not None      # saved_in[L - 1] holds the rows of S_1 (= level 0's destination)
+        ctx.saved_rows = SavedRows('all', 'S1' if (bwd and ro is not None) else 'all')      # (no head; saved_in[L - 1] on S_1 = level 0's destination)
         ctx.graph, ctx.cfg = graph, cfg
         if bwd:
-            ctx.save_for_backward(*saved_in, *saved_bits, *[t for t in layer_params if t is not None])
-        ctx.le_present = [layer_params[3 * l + 2] is not None for l in range(L)]
+            _save(ctx, saved_in=saved_in, saved_bits=saved_bits, layer_params=layer_params)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        graph, (L, p, seeds, _track, loss_rows, _rows_only) = ctx.graph, ctx.cfg
-        sv = list(ctx.saved_tensors)
-        saved_in, saved_bits, rest = sv[:L], sv[L: 2 * L - 1], sv[2 * L - 1:]
-        lp, k = [], 0
-        for l in range(L):
-            w, bias = rest[k], rest[k + 1]
-            k += 2
-            le = None
-            if ctx.le_present[l]:
-                le = rest[k]
-                k += 1
-            lp.append((w, bias, le))
+        graph, cfg, sv = ctx.graph, ctx.cfg, _saved(ctx)
+        L, p, seeds, loss_rows, in_last_compact = cfg.L, cfg.p, cfg.seeds, cfg.loss_rows, ctx.saved_rows.x_below == 'S1'
+        saved_in, saved_bits, lp = sv['saved_in'], sv['saved_bits'], _layers(sv['layer_params'])
         a, b = graph.norm_out, graph.norm_in
-        row0 = int(getattr(graph, 'row_offset', 0))
-        sharded = hasattr(graph, 'part')
+        row0, sharded = int(getattr(graph, 'row_offset', 0)), hasattr(graph, 'part')
         need = ctx.needs_input_grad          # (graph, cfg, x, *layer_params)
         nw = lambda l: need[3 + 3 * l]       # noqa: E731
         nb = lambda l: need[3 + 3 * l + 1]   # noqa: E731
@@ -141,11 +131,11 @@ class _StackFn(torch.autograd.Function):
         # Row-sparse backward (one GPU; trunk.py / DESIGN.md section 1): under the caller's loss_rows promise the levels of the backward whose support
         # is small run on compact [|S_j|, .] matrices through the plan's renumbered orientations; the promise is checked on the device.
         plan = None
-        hint = _plan_hint(graph, loss_rows, gout.shape[0], ag, committed=ctx.in_last_compact)
+        hint = _plan_hint(graph, loss_rows, gout.shape[0], ag, committed=in_last_compact)
         if hint is not None:
             ops.check_rows_zero(gout, hint[0])
-            plan = graph.grad_support_plan(hint[0], L, max_frac=T.rowsparse_max_frac, count=not ctx.in_last_compact)      # (one use per step)
-        if ctx.in_last_compact and (plan is None or plan.levels[0][1] is None):
+            plan = graph.grad_support_plan(hint[0], L, max_frac=T.rowsparse_max_frac, count=not in_last_compact)      # (one use per step)
+        if in_last_compact and (plan is None or plan.levels[0][1] is None):
             raise RuntimeError('the forward ran its last layers on the loss rows\' supports (rows_only), but its backward finds no such plan: '
                                'CB_LOSS_ROWS / tuning.T / the mask changed between the forward and the backward')
         space = plan.space0 if plan is not None else None                        # row space of g / gr (None: all rows)
@@ -178,7 +168,7 @@ class _StackFn(torch.autograd.Function):
         a_sp = space.a if space is not None else a
         w_last = lp[L - 1][0]
         if nw(L - 1):
-            x_last = saved_in[L - 1] if ctx.in_last_compact else rows_of(saved_in[L - 1], space)      # (rows-only forward: already the rows of S_1)
+            x_last = saved_in[L - 1] if in_last_compact else rows_of(saved_in[L - 1], space)      # (rows-only forward: already the rows of S_1)
             grads[3 * (L - 1)] = gemm.mm_tn(x_last, gz, rowscale=a_sp)
         if nle(L - 1):
             grads[3 * (L - 1) + 2] = all_rows(gz, space)
@@ -195,8 +185,8 @@ class _StackFn(torch.autograd.Function):
             del g
             g = None
             level = level_of(L - 1 - l)
+            dst, a_dst = None, a         # the rows dL/dZ_l lives on (None: all rows) and their source-row factor
             if level is not None:        # a compact level of the plan: the level's own orientation, rows of S_{j+1} (or all rows) out
-                from .graph import weight_image
                 csr, dst = level
                 csr.profile = getattr(graph, 'profile', None)
                 a_dst = dst.a if dst is not None else a
@@ -206,23 +196,8 @@ class _StackFn(torch.autograd.Function):
                     gz = csr.spmm(gr)
                     if need[2]:
                         g = gemm.mm_nn(gz, w.t().contiguous(), rowscale=a_dst)
-                del gr
-                if nw(l):
-                    if l == 0 and ctx.indrop and dst is None:
-                        dw = gemm.mm_tn_adrop(saved_in[0], gz, p, seeds[0], row0, rowscale=a)
-                        if dw is None:
-                            dw = gemm.mm_tn(ops._dropout_raw(saved_in[0], p, seeds[0], row0 * saved_in[0].shape[1]), gz, rowscale=a)
-                        grads[0] = dw
-                    else:
-                        x_in = saved_in[l] if not (l == 0 and ctx.indrop) else ops._dropout_raw(saved_in[0], p, seeds[0], row0 * saved_in[0].shape[1])
-                        grads[3 * l] = gemm.mm_tn(rows_of(x_in, dst), gz, rowscale=a_dst)
-                if nle(l):
-                    grads[3 * l + 2] = all_rows(gz, dst)
-                del gz
                 space = dst
-                continue
-            if ag and l > 0:             # dL/dZ_l = A (b * dY') and a * (dL/dZ_l W_l^T) from one kernel (sharded: as the last halo pass)
-                from .graph import weight_image
+            elif ag and l > 0:           # dL/dZ_l = A (b * dY') and a * (dL/dZ_l W_l^T) from one kernel (sharded: as the last halo pass)
                 img = weight_image(w, transpose=True)
                 if sharded:
                     gz, g = graph.aggregate_finish(graph.aggregate_start(gr, True), True,
@@ -235,15 +210,13 @@ class _StackFn(torch.autograd.Function):
                     g = gemm.mm_nn(gz, w.t().contiguous(), rowscale=a)
             del gr
             if nw(l):
-                if l == 0 and ctx.indrop:      # the mask of the dropout in front of layer 0 is regenerated while the GEMM stages x
-                    dw = gemm.mm_tn_adrop(saved_in[0], gz, p, seeds[0], row0, rowscale=a)
-                    if dw is None:
-                        dw = gemm.mm_tn(ops._dropout_raw(saved_in[0], p, seeds[0], row0 * saved_in[0].shape[1]), gz, rowscale=a)
-                    grads[0] = dw
+                if l == 0 and ctx.indrop and dst is None:      # the mask of the dropout in front of layer 0 is regenerated while the GEMM stages x
+                    grads[0] = _dw_regen(saved_in[0], gz, p, seeds[0], row0, a)
                 else:
-                    grads[3 * l] = gemm.mm_tn(saved_in[l], gz, rowscale=a)
+                    x_in = saved_in[l] if not (l == 0 and ctx.indrop) else ops._dropout_raw(saved_in[0], p, seeds[0], row0 * saved_in[0].shape[1])
+                    grads[3 * l] = gemm.mm_tn(rows_of(x_in, dst), gz, rowscale=a_dst)
             if nle(l):
-                grads[3 * l + 2] = gz
+                grads[3 * l + 2] = all_rows(gz, dst)
             del gz
         d_x = None
         if need[2]:
@@ -256,23 +229,11 @@ def forward(tc, x, graph, loss_rows=None, rows_only=False):
     L = tc.num_layers
     p = float(tc.dropout) if tc.training else 0.0
     seeds = tuple(ops.next_seed() for _ in range(L + 1)) if p > 0 else (0,) * (L + 1)
-    params, se_reg_all = [], None
-    for conv in tc.layers_GCN:
-        le = conv.le if conv.whetherHasSE else None
-        params += [conv.weight, conv.bias, le]
-        if le is not None:
-            reg = ops.frobenius_norm(le)
-            if hasattr(graph, 'part'):      # row shards: the norm is over all ranks' rows
-                from .dist import allreduce_sum
-                reg = allreduce_sum(reg * reg, graph.group).sqrt()
-            conv.se_norm = reg.detach()
-            se_reg_all = reg if se_reg_all is None else se_reg_all + reg
-    if not all(c._allow_zero_in_degree for c in tc.layers_GCN):      # GCN.py:187-197
-        graph.check_zero_in_degree()
+    params, se_reg_all = _collect_layer_params(tc, graph)
     if loss_rows is not None:
         mask, count = loss_rows if isinstance(loss_rows, (tuple, list)) else (loss_rows, None)
         if mask.dtype != torch.bool or mask.dim() != 1 or mask.shape[0] != x.shape[0]:
             raise ValueError(f'loss_rows: a bool mask over the {x.shape[0]} rows expected, got {tuple(mask.shape)} {mask.dtype}')
         loss_rows = (mask, int(count) if count is not None else int(mask.sum().item()))
-    out = _StackFn.apply(graph, (L, p, seeds, torch.is_grad_enabled(), loss_rows, bool(rows_only) and loss_rows is not None), x, *params)
+    out = _StackFn.apply(graph, StackCfg(L, p, seeds, torch.is_grad_enabled(), loss_rows, bool(rows_only) and loss_rows is not None), x, *params)
     return out, se_reg_all
