@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import ops, tuning
 from ..utils import D, HipLinear, graphUtils
 
 TOPK_KERNEL_MAX = 8      # cb_topk_replace_f32 keeps K <= 8 candidates per lane
@@ -275,10 +275,16 @@ class GraphMLP(nn.Module):
         self.to(args.device)
 
     def power(self, edge_index):
-        """The device form of A~^r, built on the host at the first call (normalize_adj -> sparse_power -> ops.SparsePower) and kept."""
+        """The device form of A~^r, built on the host at the first call (normalize_adj -> sparse_power -> ops.SparsePower) and kept.  With
+        tuning.T.power_on_device and the model on a GPU only normalize_adj stays on the host: the products and the transpose run on the device
+        (ops.SparsePower.from_adjacency)."""
         if self.adj_pow is None:
             adj = graphUtils.normalize_adj(edge_index.detach().cpu())
-            self.adj_pow = ops.SparsePower(graphUtils.sparse_power(adj, self.args.graphMLP_r), self.out_proj.weight.device)
+            device = self.out_proj.weight.device
+            if tuning.T.power_on_device and device.type == 'cuda':
+                self.adj_pow = ops.SparsePower.from_adjacency(adj, self.args.graphMLP_r, device)
+            else:
+                self.adj_pow = ops.SparsePower(graphUtils.sparse_power(adj, self.args.graphMLP_r), device)
         return self.adj_pow
 
     def forward(self, x, edge_index=None, batch_idx=None):

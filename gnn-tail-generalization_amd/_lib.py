@@ -160,6 +160,13 @@ SIGNATURES = {
     'cb_ncloss_normalize_rows_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P]),
     'cb_ncloss_bwd_slab_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_float, _P, _P, _I64, _I64, _I32, _P, _I64, _P]),
     'cb_ncloss_bwd_finish_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    'cb_spgemm_offsets_workspace_bytes': (_SZ, [_I64]),
+    'cb_spgemm_entry_offsets_i64': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'cb_spgemm_chunk_workspace_bytes': (_SZ, [_I64]),
+    'cb_spgemm_chunk_count_f32': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P]),
+    'cb_spgemm_chunk_emit_f32': (ctypes.c_int, [_P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    'cb_csr_transpose_workspace_bytes': (_SZ, [_I64]),
+    'cb_csr_transpose_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@ namespace cb {
 size_t sort_u64_temp_bytes(int64_t n);
 
 // keys_out = keys_in sorted ascending by bits [0, end_bit) (stable); keys_in is used as the second buffer and destroyed.  n < 2^32.
+// Bits at and above end_bit are moved with the key and never compared: a payload there keeps its input order among equal keys (cb_spgemm.hip).
 int sort_u64(void* temp, size_t temp_bytes, uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit, hipStream_t st);
 
 }  // namespace cb

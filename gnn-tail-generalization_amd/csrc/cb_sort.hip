@@ -8,6 +8,7 @@
 //                   digit's total; a last single block turns the 256 totals into digit bases
 //   k_sort_scatter  the same blocks re-read their keys, repeat the match per round and write key -> base[digit] + scan[digit][block] +
 //                   (earlier wavefronts of the block) + (earlier rounds of the wavefront) + (lower lanes of the match group): stable.
+// The last pass masks its digit to end_bit: bits above it are never compared, so a payload there rides along in input order (cb_spgemm.hip).
 // Bound: HBM — 3 x 8 B per key and pass (two reads, one scattered write in runs of ~32 keys per (block, digit)).
 #include "cb_sort.h"
 
@@ -39,7 +40,7 @@ __device__ __forceinline__ void load_wave_keys(const uint64_t* __restrict__ in, 
   vmask_any = wave_base < n;
 }
 
-__global__ void __launch_bounds__(256) k_sort_hist(const uint64_t* __restrict__ in, int64_t n, int shift, uint32_t* __restrict__ hist, int64_t n_blocks) {
+__global__ void __launch_bounds__(256) k_sort_hist(const uint64_t* __restrict__ in, int64_t n, int shift, unsigned dmask, uint32_t* __restrict__ hist, int64_t n_blocks) {
   __shared__ uint32_t whist[4][256];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
 #pragma unroll
@@ -51,7 +52,7 @@ __global__ void __launch_bounds__(256) k_sort_hist(const uint64_t* __restrict__ 
     for (int r = 0; r < kSortItems; ++r) {
       const int64_t i = wave_base + (int64_t)r * 64 + lane;
       const bool valid = i < n;
-      const unsigned digit = valid ? (unsigned)((in[i] >> shift) & 0xffull) : 0u;
+      const unsigned digit = valid ? (unsigned)(in[i] >> shift) & dmask : 0u;
       const unsigned long long m = match_digit(digit, valid);
       if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) whist[w][digit] += (uint32_t)__popcll(m);      // the group's lowest lane; one lane per digit
     }
@@ -110,7 +111,7 @@ __global__ void __launch_bounds__(256) k_sort_digit_base(const uint64_t* __restr
   base[t] = s[t];
 }
 
-__global__ void __launch_bounds__(256) k_sort_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int64_t n, int shift,
+__global__ void __launch_bounds__(256) k_sort_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, int64_t n, int shift, unsigned dmask,
                                                       const uint32_t* __restrict__ scan, const uint64_t* __restrict__ base, int64_t n_blocks) {
   __shared__ uint32_t whist[4][256];
   __shared__ uint64_t wbase[4][256];
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint64_t* __restrict
 #pragma unroll
     for (int r = 0; r < kSortItems; ++r) {
       const bool valid = wave_base + (int64_t)r * 64 + lane < n;
-      const unsigned digit = valid ? (unsigned)((k[r] >> shift) & 0xffull) : 0u;
+      const unsigned digit = valid ? (unsigned)(k[r] >> shift) & dmask : 0u;
       const unsigned long long m = match_digit(digit, valid);
       if (valid && (m & below) == 0ull) whist[w][digit] += (uint32_t)__popcll(m);
     }
@@ -147,7 +148,7 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint64_t* __restrict
 #pragma unroll
     for (int r = 0; r < kSortItems; ++r) {
       const bool valid = wave_base + (int64_t)r * 64 + lane < n;
-      const unsigned digit = valid ? (unsigned)((k[r] >> shift) & 0xffull) : 0u;
+      const unsigned digit = valid ? (unsigned)(k[r] >> shift) & dmask : 0u;
       const unsigned long long m = match_digit(digit, valid);
       uint64_t pos = 0;
       if (valid) pos = mine[digit];                                   // every lane of the group reads the cursor ...
@@ -179,13 +180,15 @@ int sort_u64(void* temp, size_t temp_bytes, uint64_t* keys_in, uint64_t* keys_ou
   uint64_t *src = keys_in, *dst = keys_out;
   const int passes = (end_bit + 7) / 8;
   for (int p = 0; p < passes; ++p) {
-    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nb), dim3(256), 0, st, src, n, 8 * p, hist, nb);
+    // the last pass reads the bits below end_bit only: whatever a key holds above them rides along and keeps its input order (stable)
+    const unsigned dmask = end_bit - 8 * p >= 8 ? 0xffu : (1u << (end_bit - 8 * p)) - 1u;
+    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nb), dim3(256), 0, st, src, n, 8 * p, dmask, hist, nb);
     CB_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sort_scan, dim3(256), dim3(1024), 0, st, hist, nb, scan, total);
     CB_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sort_digit_base, dim3(1), dim3(256), 0, st, total, base);
     CB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, 8 * p, scan, base, nb);
+    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, 8 * p, dmask, scan, base, nb);
     CB_LAUNCH_CHECK();
     uint64_t* tmp = src; src = dst; dst = tmp;
   }

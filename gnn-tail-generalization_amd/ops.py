@@ -15,6 +15,7 @@ Student MLPs (reference lines are MLP_model/__init__.py / utils.py / the trainer
 GraphMLP (MLP_model/__init__.py:158-208):
   neighbor_contrastive_loss  -mean log(num / den) over the cropped adjacency power   :190-198 (Gram sweep, no [B, B] matrix in the forward)
   cosine_sim        (x @ x.T) / (|x_i| |x_j|)        :200-208
+  spgemm_csr / csr_transpose / SparsePower.from_adjacency   the adjacency power A~^r on the device (utils.py:1242-1248; expand - sort - compress)
 """
 import ctypes
 import os
@@ -922,6 +923,185 @@ class SparsePower:
         rowptr = torch.zeros(self.n + 1, dtype=torch.int64)
         rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=self.n), 0)
         return (rowptr.to(torch.int32).to(self.device), c[order].to(torch.int32).to(self.device), v[order].contiguous().to(self.device))
+
+    @classmethod
+    def from_adjacency(cls, adj, r, device):
+        """The same object built on the device from A~ itself (`adj`: coalesced square sparse COO tensor, host or device): A~ is uploaded once as
+        int32 CSR, r - 1 products P <- P A~ (spgemm_csr; the association of graphUtils.sparse_power) give the power, csr_transpose the
+        second orientation.  r = 1 is the upload plus the transpose.  No host build, no CPU fallback."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.HipExtensionError('SparsePower.from_adjacency builds the power on an MI355X device; there is no CPU fallback '
+                                         '(SparsePower(graphUtils.sparse_power(adj, r), device) is the host build)')
+        if int(r) < 1:
+            raise ValueError(f'SparsePower.from_adjacency: r = {r} (r >= 1)')
+        if not adj.is_sparse or adj.dim() != 2 or adj.shape[0] != adj.shape[1]:
+            raise ValueError('SparsePower expects a square sparse matrix')
+        if not adj.is_coalesced():
+            raise ValueError('SparsePower.from_adjacency expects a coalesced tensor (row-major sorted, no duplicates)')
+        n, nnz = int(adj.shape[0]), int(adj._nnz())
+        if nnz >= 2 ** 31 or n >= 2 ** 31:
+            raise ValueError(f'SparsePower: {nnz} non-zeros / {n} nodes do not fit the int32 index contract (< 2^31)')
+        _stage('upload')
+        idx, val = adj.indices().to(device), adj.values().detach().to(device).float().contiguous()
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+        rowptr[1:] = torch.cumsum(torch.bincount(idx[0], minlength=n), 0)
+        a = (rowptr.to(torch.int32), idx[1].to(torch.int32).contiguous(), val)
+        p = a
+        for _ in range(int(r) - 1):
+            p = spgemm_csr(*p, *a, n)
+        self = cls.__new__(cls)
+        self.n, self.nnz, self.device = n, int(p[1].numel()), device
+        self.rowptr, self.col, self.val = p
+        self.rowptr_t, self.col_t, self.val_t = csr_transpose(*p, n)
+        _stage('end')
+        return self
+
+
+_stage_hook = None      # tools/bench_power.py: called with the name of a stage of the device build where it begins
+
+
+def _stage(name):
+    if _stage_hook is not None:
+        _stage_hook(name)
+
+
+def _check_range(rc, what):
+    """CB_E_RANGE (a size beyond the int32 index contract) is the caller's ValueError; everything else goes through _lib.check."""
+    if rc == -2:
+        msg = _lib.load().cb_last_error()
+        raise ValueError(f'{what}: {msg.decode() if msg else "size exceeds the int32 index contract"}')
+    _lib.check(rc, what)
+
+
+def _bits(n):
+    """Bits that hold every value of [0, n)."""
+    return max(int(n) - 1, 0).bit_length()
+
+
+def spgemm_plan(row_products, n_cols, chunk_products):
+    """Host planner of spgemm_csr: cuts the rows of A into chunks, each a maximal run of consecutive rows whose products (row_products[i] of
+    row i) fit `chunk_products`, at least one row (a row with more products than the budget is a chunk of its own).  A chunk's sort key holds
+    the product number, the row inside the chunk and the column: bits(chunk_products) + bits(rows) + bits(n_cols) <= 64, so a chunk holds at
+    most 2^(64 - pb - cb) rows.  Returns (chunks, (pb, rb, cb)): [(row0, row1), ...] tiling [0, m) in order, and the bits of product number,
+    row (of the largest chunk) and column.  ValueError where no split fits 64 bits."""
+    import numpy as np
+    rp = row_products.detach().cpu().numpy() if torch.is_tensor(row_products) else np.asarray(row_products)
+    rp = rp.astype(np.int64).reshape(-1)
+    budget, n_cols = int(chunk_products), int(n_cols)
+    if budget < 1 or n_cols < 0 or (rp < 0).any():
+        raise ValueError('spgemm_plan: chunk_products >= 1, n_cols >= 0 and row_products >= 0 expected')
+    pb, cb = _bits(budget), _bits(max(n_cols, 2))
+    if pb + cb > 64:
+        raise ValueError(f'spgemm_plan: {pb} product bits (chunk_products = {budget}) and {cb} column bits (n_cols = {n_cols}) do not fit a 64-bit key')
+    max_rows = 1 << min(64 - pb - cb, 31)
+    m = int(rp.size)
+    cum = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(rp)])
+    chunks, r0 = [], 0
+    while r0 < m:
+        r1 = int(np.searchsorted(cum, cum[r0] + budget, side='right')) - 1      # the last r1 with cum[r1] - cum[r0] <= budget
+        r1 = min(max(r1, r0 + 1), r0 + max_rows, m)
+        chunks.append((r0, r1))
+        r0 = r1
+    return chunks, (pb, _bits(max((b - a for a, b in chunks), default=1)), cb)
+
+
+def _csr_args(who, rowptr, col, val, n_cols):
+    """int32 / int32 / fp32 contiguous device CSR + the checks that keep the kernels' indices inside their arrays (one host read)."""
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or val.shape != col.shape:
+        raise ValueError(f'{who}: rowptr [m + 1], col [nnz] and val [nnz] expected')
+    rowptr, col, val = _c(rowptr.to(torch.int32)), _c(col.to(torch.int32)), _c(val.float())
+    nnz, n_cols = int(col.numel()), int(n_cols)
+    if not 0 <= n_cols < 2 ** 31:
+        raise ValueError(f'{who}: {n_cols} columns do not fit the int32 index contract')
+    bad = [rowptr[0] != 0, rowptr[-1] != nnz, (rowptr[1:] < rowptr[:-1]).any()]
+    if nnz:
+        bad += [col.min() < 0, col.max() >= n_cols]
+    if bool(torch.stack(bad).any()):
+        raise ValueError(f'{who}: not a CSR matrix with {n_cols} columns (rowptr must ascend from 0 to nnz, columns lie in [0, n_cols))')
+    return rowptr, col, val
+
+
+def spgemm_csr(rowptr_a, col_a, val_a, rowptr_b, col_b, val_b, n_cols, chunk_products=None):
+    """C = A B of two device CSR matrices (int32 rowptr / col, fp32 val; B has n_cols columns and as many rows as A has columns) as
+    (rowptr, col, val) with ascending columns (cb_spgemm.hip: expand - sort - compress).  C[i, j] is the sequential fp32 sum of its
+    separately rounded products in the order of A's entries in row i; an entry exists where a product exists, even if the sum is 0.0; the bits
+    depend neither on the call nor on `chunk_products` (default tuning.T.spgemm_chunk_products), which bounds the workspace: the rows are
+    walked in the chunks of spgemm_plan, one host read per chunk.  nnz(C) >= 2^31 raises ValueError from the running count."""
+    lib = _lib.load()
+    _lib.require_device(rowptr_a, col_a, val_a, rowptr_b, col_b, val_b)
+    from .tuning import T
+    budget = int(T.spgemm_chunk_products if chunk_products is None else chunk_products)
+    if not 1 <= budget < 2 ** 31:
+        raise ValueError(f'spgemm_csr: chunk_products = {budget} (a chunk\'s products are int32-indexed: 1 <= chunk_products < 2^31)')
+    _stage('checks + entry offsets')
+    dev = rowptr_a.device
+    m, k, n_cols = int(rowptr_a.numel()) - 1, int(rowptr_b.numel()) - 1, int(n_cols)
+    rowptr_a, col_a, val_a = _csr_args('spgemm_csr (A)', rowptr_a, col_a, val_a, k)
+    rowptr_b, col_b, val_b = _csr_args('spgemm_csr (B)', rowptr_b, col_b, val_b, n_cols)
+    nnz_a = int(col_a.numel())
+    ent_off = torch.empty(nnz_a + 1, dtype=torch.int64, device=dev)
+    n_bad = torch.empty(1, dtype=torch.int32, device=dev)
+    rowptr = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        wsb = lib.cb_spgemm_offsets_workspace_bytes(nnz_a)
+        ws = _ws(wsb, dev)
+        _check_range(lib.cb_spgemm_entry_offsets_i64(_lib.ptr(col_a), nnz_a, _lib.ptr(rowptr_b), k, _lib.ptr(ent_off), _lib.ptr(n_bad),
+                                                     _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_spgemm_entry_offsets_i64')
+        if int(n_bad.item()):
+            raise ValueError('spgemm_csr: an entry of A points outside B')
+        _stage('plan (host)')
+        row_off = ent_off[rowptr_a.long()].cpu()                  # products in front of every row of A
+        chunks, _ = spgemm_plan(row_off[1:] - row_off[:-1], n_cols, budget)
+        row_off = row_off.tolist()
+        wsb = lib.cb_spgemm_chunk_workspace_bytes(max((row_off[r1] - row_off[r0] for r0, r1 in chunks), default=0))
+        ws = _ws(wsb, dev)
+        cols, vals, base = [], [], 0
+        for r0, r1 in chunks:
+            prods, cnt = row_off[r1] - row_off[r0], 0
+            if prods:
+                _stage('expand + sort + head scan')
+                _check_range(lib.cb_spgemm_chunk_count_f32(_lib.ptr(rowptr_a), _lib.ptr(col_a), _lib.ptr(val_a), _lib.ptr(rowptr_b), _lib.ptr(col_b),
+                                                           _lib.ptr(val_b), _lib.ptr(ent_off), r0, r1, k, n_cols, prods, _lib.ptr(count),
+                                                           _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_spgemm_chunk_count_f32')
+                cnt = int(count.item())
+            if base + cnt >= 2 ** 31:      # before anything of that size is allocated
+                raise ValueError(f'spgemm_csr: the product holds at least {base + cnt} entries after row {r1}: beyond the int32 index contract (nnz < 2^31)')
+            _stage('compress + rowptr')
+            c = torch.empty(cnt, dtype=torch.int32, device=dev)
+            v = torch.empty(cnt, dtype=torch.float32, device=dev)
+            _check_range(lib.cb_spgemm_chunk_emit_f32(_lib.ptr(ws), wsb, r0, r1, n_cols, prods, cnt, base, _lib.ptr(rowptr), _lib.ptr(c), _lib.ptr(v),
+                                                      _lib.stream_ptr()), 'cb_spgemm_chunk_emit_f32')
+            cols.append(c)
+            vals.append(v)
+            base += cnt
+        rowptr[m:] = base
+    _stage('concatenate')
+    if len(cols) == 1:
+        return rowptr, cols[0], vals[0]
+    if not cols:
+        return rowptr, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+    return rowptr, torch.cat(cols), torch.cat(vals)
+
+
+def csr_transpose(rowptr, col, val, n_cols):
+    """The transpose of a device CSR matrix with n_cols columns as (rowptr_t [n_cols + 1], col_t, val_t), columns ascending; val_t is a
+    bit-exact permutation of val (cb_csr_transpose_f32)."""
+    lib = _lib.load()
+    _lib.require_device(rowptr, col, val)
+    _stage('transpose')
+    rowptr, col, val = _csr_args('csr_transpose', rowptr, col, val, n_cols)
+    dev, m, n, nnz = rowptr.device, int(rowptr.numel()) - 1, int(n_cols), int(col.numel())
+    rowptr_t = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    col_t = torch.empty(nnz, dtype=torch.int32, device=dev)
+    val_t = torch.empty(nnz, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        wsb = lib.cb_csr_transpose_workspace_bytes(nnz)
+        ws = _ws(wsb, dev)
+        _check_range(lib.cb_csr_transpose_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(val), m, n, nnz, _lib.ptr(rowptr_t), _lib.ptr(col_t),
+                                              _lib.ptr(val_t), _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_csr_transpose_f32')
+    return rowptr_t, col_t, val_t
 
 
 def _ncloss_slab_rows(B):

@@ -71,5 +71,15 @@ class Tuning:
     # cap on the column slabs a row block's sweep is split into.  0: the rule of the top-K sweep (about four blocks per CU)
     ncloss_max_splits: int = 0
 
+    # ---- adjacency power on the device (ops.spgemm_csr / ops.SparsePower.from_adjacency, cb_spgemm.hip) -------------------------------------
+    # products one chunk of the sparse x sparse product expands at most (a single row with more gets a chunk of its own).  A MEMORY bound, not a
+    # measured break-even: 24 B of workspace per product, 1.5 GiB at 2^26, about 2 GB with the chunk's compact result beside it; the result's
+    # bits do not depend on it
+    spgemm_chunk_products: int = 1 << 26
+    # GraphMLP.power() builds A~^r with the device product when the model lives on a GPU (off: normalize_adj -> sparse_power -> SparsePower on the
+    # host: 13.3 s against 38.8 ms at the S-arxiv shape, r = 2, profiles/power.md).  Off until a later change flips it: the two builds agree to
+    # the last bit on the tested graphs, but every GraphMLP test so far runs the host build
+    power_on_device: bool = False
+
 
 T = Tuning()

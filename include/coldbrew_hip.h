@@ -732,6 +732,48 @@ int cb_ncloss_bwd_finish_f32(const float* z, int64_t ldz, const float* zhat, int
                              const float* val_t, int64_t n, const int64_t* batch_idx, const int32_t* pos, const int32_t* rep, const float* g,
                              float* dzh, float* dz, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * fp32 sparse x sparse product C = A B and the exact transpose of a CSR matrix (cb_spgemm.hip): GraphMLP's adjacency power A~^r
+ * (utils.py:1242-1248) without the host.  A is m x k, B is k x n_cols, both int32 CSR (rowptr / col) with fp32 values; C comes back as int32
+ * CSR with ascending columns.  Contract:
+ *   - C[i, j] is the sequential fp32 sum of its products A[i, k] * B[k, j] in the order of A's entries in row i (ascending k for a coalesced
+ *     A); each product is rounded to fp32 on its own and the first addend is the first product.  No float atomics; two calls give the same
+ *     bits and the result does not depend on the chunking.
+ *   - an entry exists where at least one product exists, also where the sum is 0.0 (torch.sparse.mm + coalesce).
+ *   - indices are int32, product counts and offsets int64; nnz(C) >= 2^31 is CB_E_RANGE, found from the running count of the chunks.
+ * The caller walks the rows in chunks (a maximal run of consecutive rows whose products fit a budget, at least one row) so that the
+ * workspace follows the budget, not the graph: about 24 B per product of the largest chunk.  Per chunk one host read of *count.
+ * ---------------------------------------------------------------------------------- */
+
+/* ent_off [nnz_a + 1] (int64): ent_off[e] = sum over A's entries e' < e of the length of B's row col_a[e']; ent_off[nnz_a] = all products.
+ * The products of rows [r0, r1) of A are ent_off[rowptr_a[r1]] - ent_off[rowptr_a[r0]].  n_bad [1]: entries of A whose column lies outside
+ * [0, k) or whose row of B has a negative length; they count no products. */
+size_t cb_spgemm_offsets_workspace_bytes(int64_t nnz_a);
+int cb_spgemm_entry_offsets_i64(const int32_t* col_a, int64_t nnz_a, const int32_t* rowptr_b, int64_t k, int64_t* ent_off, int32_t* n_bad,
+                                void* ws, size_t ws_bytes, void* stream);
+
+/* Rows [row0, row1) of A times B, first half: expands the chunk's n_products products (n_products must be the difference of ent_off
+ * above; < 2^31) into ws, sorts them by (row, col) and writes the number of distinct (row, col) to *count (DEVICE int64).  The bits of
+ * n_products, row1 - row0 and n_cols must fit 64 together (CB_E_RANGE otherwise: fewer rows per chunk).  ws:
+ * cb_spgemm_chunk_workspace_bytes(n_products); it carries the chunk to cb_spgemm_chunk_emit_f32 and must not be touched in between. */
+size_t cb_spgemm_chunk_workspace_bytes(int64_t n_products);
+int cb_spgemm_chunk_count_f32(const int32_t* rowptr_a, const int32_t* col_a, const float* val_a, const int32_t* rowptr_b, const int32_t* col_b,
+                              const float* val_b, const int64_t* ent_off, int64_t row0, int64_t row1, int64_t k, int64_t n_cols,
+                              int64_t n_products, int64_t* count, void* ws, size_t ws_bytes, void* stream);
+
+/* Second half, with `count` read back by the host: col_out / val_out [count] = the chunk's entries (rows ascending, columns ascending inside
+ * a row) and rowptr[row0 .. row1) = nnz_base + the entries of the chunk before each row (rowptr: C's whole [m + 1] array; the caller writes
+ * rowptr[m]).  nnz_base = entries of the chunks before this one; nnz_base + count >= 2^31 is CB_E_RANGE.  A chunk without products
+ * (n_products == 0, count == 0) needs no ws. */
+int cb_spgemm_chunk_emit_f32(const void* ws, size_t ws_bytes, int64_t row0, int64_t row1, int64_t n_cols, int64_t n_products, int64_t count,
+                             int64_t nnz_base, int32_t* rowptr, int32_t* col_out, float* val_out, void* stream);
+
+/* The transpose of an m x n CSR matrix with nnz entries: rowptr_t [n + 1], col_t / val_t [nnz], columns (the matrix's rows) ascending.  The
+ * values are moved, not recomputed: val_t is a permutation of val.  One radix sort over the column bits; ws 16 B per entry + the sort's. */
+size_t cb_csr_transpose_workspace_bytes(int64_t nnz);
+int cb_csr_transpose_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t m, int64_t n, int64_t nnz, int32_t* rowptr_t,
+                         int32_t* col_t, float* val_t, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
