@@ -16,6 +16,10 @@ GraphMLP (MLP_model/__init__.py:158-208):
   neighbor_contrastive_loss  -mean log(num / den) over the cropped adjacency power   :190-198 (Gram sweep, no [B, B] matrix in the forward)
   cosine_sim        (x @ x.T) / (|x_i| |x_j|)        :200-208
   spgemm_csr / csr_transpose / SparsePower.from_adjacency   the adjacency power A~^r on the device (utils.py:1242-1248; expand - sort - compress)
+The teacher's edge-wise term (trainer_node_classification.py:417-438, 507-563; utils.py:754-791):
+  LinkSampler       positive / negative edge samples on the device CSR (binary search in a row; counter-based draws)
+  linkp_loss_eva    BCE-with-logits of the DistMult scores + MRR over index pairs; gradient as one [N, D] matrix, no atomics
+  cal_MRR           the MRR of held scores
 """
 import ctypes
 import os
@@ -1220,3 +1224,190 @@ def cosine_sim(x):
         _lib.check(lib.cb_ncloss_row_norms_f32(_lib.ptr(x), D, N, D, _lib.ptr(nrm), None, _lib.stream_ptr()), 'cb_ncloss_row_norms_f32')
         _lib.check(lib.cb_cosine_scale_f32(_lib.ptr(s), N, N, _lib.ptr(nrm), _lib.stream_ptr()), 'cb_cosine_scale_f32')
     return s
+
+
+# ---------------------------------------------------------------------------------------------
+# the teacher's edge-wise (link-prediction) term: trainer_node_classification.py:417-438, 507-563; utils.py:754-791  (cb_linkp.hip)
+# ---------------------------------------------------------------------------------------------
+LINKP_MODES = {'train': 0, 'test': 1}
+
+
+def _linkp_view(graph):
+    v = _lib.CsrView(graph.rowptr.data_ptr(), graph.col.data_ptr(), 0, graph.N, graph.E, 1, 0, 0, None, None, None, 0)
+    v._keep = (graph.rowptr, graph.col)
+    return v
+
+
+class LinkSampler:
+    """Positive and negative edge samples of `gen_pn_edges` / `my_negative_sampling` (trainer_node_classification.py:507-563) drawn on the device
+    CSR: a positive is one of the edges whose endpoints are both inside (mode 'train') or both outside (mode 'test') the train mask, uniform with
+    replacement, multiplicity and self loops as edge_index has them; a negative is a pair that is no edge in either direction and no self pair,
+    with both endpoints train nodes ('train') or at least one endpoint outside the train split ('test').  Built once per (graph, train_mask): the
+    per-mode prefix arrays of valid edges per row (one host read each: V = 0 raises ValueError), the ascending list of train nodes and the int32
+    counter of failed negative slots.  Every draw is a pure function of (seed, slot, try): Philox4x32-10, restated on the host in
+    tests/linkp_ref.py.  Deviations from the reference, which loops on the host until at least samp_size_n pairs survive its mask filter and then
+    uses all of them (a variable count, one synchronisation per batch): the count is exactly n rounded up to even (fixed shapes, no
+    synchronisation), and the endpoints are drawn from the allowed node set instead of filtering uniform non-edges by the mask, which gives the
+    same conditional distribution."""
+
+    def __init__(self, graph, train_mask):
+        from .graph import CSRGraph
+        if type(graph) is not CSRGraph or graph.n_cols != graph.N or graph.row_offset != 0:
+            raise ValueError('LinkSampler needs a whole square graph.CSRGraph (segmented and node-sharded graphs are out of scope)')
+        _lib.require_device(train_mask)
+        if train_mask.dtype != torch.bool or train_mask.dim() != 1 or train_mask.numel() != graph.N or train_mask.device != graph.device:
+            raise ValueError(f'LinkSampler: train_mask must be a bool vector of {graph.N} nodes on the device of the graph')
+        lib = _lib.load()
+        self.graph, self.mask = graph, _c(train_mask)
+        self._m8 = self.mask.view(torch.uint8)
+        self.train_nodes = torch.nonzero(self.mask).reshape(-1).to(torch.int32)      # ascending
+        self.n_train = int(self.train_nodes.numel())
+        self.failed = torch.zeros(1, dtype=torch.int32, device=graph.device)
+        self._prefix = {}
+        self._lib = lib
+
+    def _valid(self, mode):
+        hit = self._prefix.get(mode)
+        if hit is None:
+            g = self.graph
+            counts = torch.empty(g.N, dtype=torch.int32, device=g.device)
+            with torch.cuda.device(g.device):
+                _lib.check(self._lib.cb_linkp_valid_counts_i32(ctypes.byref(_linkp_view(g)), _lib.ptr(self._m8), LINKP_MODES[mode], _lib.ptr(counts),
+                                                               _lib.stream_ptr()), 'cb_linkp_valid_counts_i32')
+            prefix = torch.zeros(g.N + 1, dtype=torch.int32, device=g.device)
+            prefix[1:] = torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)      # E < 2^31
+            V = int(prefix[-1].item())
+            if V == 0:
+                raise ValueError(f'LinkSampler: no edge has both endpoints {"inside" if mode == "train" else "outside"} the train split (mode {mode!r})')
+            hit = self._prefix[mode] = (prefix, V)
+        return hit
+
+    @staticmethod
+    def _mode(mode):
+        if mode not in LINKP_MODES:
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")      # (:519-520)
+        return LINKP_MODES[mode]
+
+    def positives(self, mode, n, seed=None):
+        """int32 [2, n]: row 0 = source, row 1 = destination of n valid edges of `mode`."""
+        m = self._mode(mode)
+        prefix, V = self._valid(mode)
+        g = self.graph
+        n = int(n)
+        if n < 0:
+            raise ValueError('LinkSampler.positives: n >= 0 required')
+        seed = next_seed() if seed is None else int(seed)
+        out = torch.empty((2, n), dtype=torch.int32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(self._lib.cb_linkp_positives_i32(ctypes.byref(_linkp_view(g)), _lib.ptr(self._m8), m, _lib.ptr(prefix), V, n,
+                                                        ctypes.c_uint64(seed % 2 ** 64), seed_dev_ptr(), _lib.ptr(out), _lib.stream_ptr()),
+                       'cb_linkp_positives_i32')
+        return out
+
+    def negatives(self, mode, n, seed=None):
+        """int32 [2, n rounded up to even]: columns 2 s and 2 s + 1 hold (u, v) and (v, u).  A slot that found no pair holds -1 and counts in
+        `failed` (check())."""
+        m = self._mode(mode)
+        g = self.graph
+        n = int(n)
+        if n < 0:
+            raise ValueError('LinkSampler.negatives: n >= 0 required')
+        n += n & 1
+        if mode == 'train' and self.n_train == 0:
+            raise ValueError('LinkSampler.negatives: the train split is empty')
+        seed = next_seed() if seed is None else int(seed)
+        out = torch.empty((2, n), dtype=torch.int32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(self._lib.cb_linkp_negatives_i32(ctypes.byref(_linkp_view(g)), _lib.ptr(self._m8), m, _lib.ptr(self.train_nodes), self.n_train, n,
+                                                        ctypes.c_uint64(seed % 2 ** 64), seed_dev_ptr(), _lib.ptr(out), _lib.ptr(self.failed),
+                                                        _lib.stream_ptr()), 'cb_linkp_negatives_i32')
+        return out
+
+    def check(self):
+        """Reads the counter of failed negative slots (a host synchronisation: call it where the loss is read anyway), clears it, and raises
+        RuntimeError if any slot of the draws since the last check found no pair in its tries."""
+        n = int(self.failed.item())
+        if n:
+            self.failed.zero_()
+            raise RuntimeError(f'LinkSampler: {n} negative slot(s) found no non-edge in {int(self._lib.cb_linkp_max_tries())} tries (their columns hold -1)')
+
+
+def _linkp_pairs(who, t, device):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 2 or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'linkp_loss_eva: {who} must be an int32 / int64 [2, n] tensor')
+    _lib.require_device(t)
+    if t.device != device:
+        raise ValueError(f'linkp_loss_eva: {who} lives on another device than the embeddings')
+    return _c(t.to(torch.int32))
+
+
+class _LinkpLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, pos, neg):
+        lib = _lib.load()
+        e = emb if emb.stride(1) == 1 and emb.stride(0) >= emb.shape[1] else emb.contiguous()
+        N, D = e.shape
+        P, Nn = pos.shape[1], neg.shape[1]
+        dev = e.device
+        scores = torch.empty(P + Nn, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        mrr = torch.empty(1, dtype=torch.float32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_linkp_loss_fwd_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(pos), P, _lib.ptr(neg) if Nn else None, Nn, _lib.ptr(scores),
+                                                 _lib.ptr(loss), _lib.ptr(mrr), _lib.ptr(status), _lib.stream_ptr()), 'cb_linkp_loss_fwd_f32')
+        ctx.save_for_backward(e, pos, neg, scores)
+        mrr, status = mrr.reshape(()), status.reshape(())
+        ctx.mark_non_differentiable(mrr, scores, status)
+        return loss.reshape(()), mrr, scores, status
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        lib = _lib.load()
+        e, pos, neg, scores = ctx.saved_tensors
+        N, D = e.shape
+        P, Nn = pos.shape[1], neg.shape[1]
+        dev = e.device
+        g = g.detach().reshape(1).to(torch.float32).contiguous()
+        demb = torch.empty((N, D), dtype=torch.float32, device=dev)
+        wsb = lib.cb_linkp_bwd_workspace_bytes(P, Nn)
+        ws = _ws(wsb, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_linkp_loss_bwd_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(pos), P, _lib.ptr(neg) if Nn else None, Nn, _lib.ptr(scores),
+                                                 _lib.ptr(g), _lib.ptr(demb), D, _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_linkp_loss_bwd_f32')
+        return demb, None, None
+
+
+def linkp_loss_eva(h_src, pos, neg, return_parts=False):
+    """`linkp_loss_eva` (utils.py:759-774) of the DistMult scores <h_src[h], h_src[t]> over the positive pairs pos [2, P] (P >= 1) and the negative
+    pairs neg [2, Nn] (int32 or int64, narrowed): (loss, mrr), loss = binary_cross_entropy_with_logits(scores, [1] * P + [0] * Nn) as a 0-dim tensor
+    with an autograd node, mrr = cal_MRR as a 0-dim device tensor (no host read in here).  h_src is the full [N, D] float32 embedding matrix (rows
+    may be strided); the four gathered [S, D] matrices of the reference are never materialised, and the gradient arrives as one [N, D] matrix whose
+    untouched rows are exactly zero, built without atomics: bit-identical from call to call.  Ties between a negative and its positive count for the
+    positive (the reference's sort + nonzero gives that when its sort happens to be stable and is undefined otherwise).  A pair with an index
+    outside [0, N) — the -1 of a failed LinkSampler slot — is never used as an index: loss and mrr are then NaN and `status` counts such pairs.
+    return_parts: also (scores [P + Nn], status 0-dim int32), detached."""
+    _lib.require_device(h_src)
+    if h_src.dim() != 2 or h_src.dtype != torch.float32 or h_src.shape[0] < 1 or h_src.shape[1] < 1:
+        raise ValueError('linkp_loss_eva expects a float32 [N, D] embedding matrix')
+    pos = _linkp_pairs('pos', pos, h_src.device)
+    neg = _linkp_pairs('neg', neg, h_src.device)
+    if pos.shape[1] < 1:
+        raise ValueError('linkp_loss_eva: at least one positive pair is required (the MRR is a mean over the positives)')
+    loss, mrr, scores, status = _LinkpLossFn.apply(h_src, pos, neg)
+    return (loss, mrr, scores, status) if return_parts else (loss, mrr)
+
+
+def cal_MRR(pos_score, neg_score):
+    """`cal_MRR` (utils.py:776-791) as a 0-dim device tensor: k = len(neg) // len(pos) negatives per positive (the rest is dropped),
+    rank_i = 1 + #{negatives of group i above pos_i}, mean of 1 / rank in float64, rounded once.  Ties count for the positive."""
+    lib = _lib.load()
+    _lib.require_device(pos_score, neg_score)
+    ps, ns = _c(pos_score.detach().reshape(-1)), _c(neg_score.detach().reshape(-1))
+    if ps.dtype != torch.float32 or ns.dtype != torch.float32 or ps.numel() < 1:
+        raise ValueError('cal_MRR expects float32 scores and at least one positive')
+    mrr = torch.empty(1, dtype=torch.float32, device=ps.device)
+    with torch.cuda.device(ps.device):
+        _lib.check(lib.cb_linkp_mrr_f32(_lib.ptr(ps), ps.numel(), _lib.ptr(ns) if ns.numel() else None, ns.numel(), _lib.ptr(mrr), _lib.stream_ptr()),
+                   'cb_linkp_mrr_f32')
+    return mrr.reshape(())

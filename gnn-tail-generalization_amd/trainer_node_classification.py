@@ -603,6 +603,96 @@ class trainer:
         self.optimizer.step()
         return self._checked(loss.item()), linkp_train, linkp_test
 
+    # -- the edge-wise (link-prediction) term: trainer_node_classification.py:417-438, 507-563 -------------------------------------------
+    # New entry points next to training_loss / run_trainSet / train_teacherGNN, which keep refusing the edge-wise loss: those promise the model that
+    # only the train rows of its output are read, and this objective reads res.commonEmb on the sampled rows.
+    def link_sampler(self):
+        """The ops.LinkSampler of (the cached device graph, data.train_mask): built at the first call, off the step."""
+        if getattr(self, '_link_sampler', None) is None or self._link_sampler_of is not self.data.train_mask:
+            self._link_sampler, self._link_sampler_of = ops.LinkSampler(self.graph(), self.data.train_mask), self.data.train_mask
+        return self._link_sampler
+
+    def gen_pn_edge_index(self, mode):
+        """(pos [2, P], neg [2, Nn]) of `gen_pn_edges` (:507-532) as index pairs: P = samp_size_p; Nn = samp_size_n_train ('train') or
+        samp_size_p * samp_size_n_test_times_p ('test'), rounded up to even.  The embedding rows are gathered inside the loss."""
+        s = self.link_sampler()
+        a = self.args
+        n_neg = a.samp_size_n_train if mode == 'train' else a.samp_size_p * a.samp_size_n_test_times_p
+        return s.positives(mode, a.samp_size_p), s.negatives(mode, n_neg)
+
+    def training_loss_linkp(self):
+        """Forward + objective of run_trainSet with the edge-wise term (:386-394, 417-426): a full forward (no loss_rows, no rows_only: the
+        edge loss reads res.commonEmb on sampled rows); if has_loss_component_nodewise, lossa_semantic * nll(log_softmax(out[train]))
+        + se_reg * sum ||E|| (the reference adds the regulariser inside that branch, :393-394); + lossa_structure * the train-mode edge loss.  Returns (loss, linkp_train, linkp_test): the two MRRs as 0-dim device
+        tensors, linkp_test from a test-mode sample scored on the same embeddings (:420-422).
+        Deviation: the reference starts from `loss = -1` (:384) and so reports loss - 1 when the node-wise term is off; that constant is not
+        carried over (the gradient is the same)."""
+        a = self.args
+        if not getattr(a, 'has_loss_component_edgewise', False):
+            raise ValueError('training_loss_linkp() builds the edge-wise term: set args.has_loss_component_edgewise (tools/train_linkp.py does)')
+        if getattr(self, '_n_train', None) is None:
+            self._n_train = int(self.data.train_mask.sum().item())
+        res = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index)
+        loss = None
+        if a.has_loss_component_nodewise:
+            loss = ops.nll_logsoftmax(res.emb4classi_full, self.data.y, self.data.train_mask, self._n_train) * a.TeacherGNN.lossa_semantic
+            if self.teacherGNN.se_reg_all is not None:
+                loss = loss + a.se_reg * self.teacherGNN.se_reg_all
+        emb = res.commonEmb      # "for linkp, must use full node embs (without applying train_mask!!)" (:418)
+        loss_structure, linkp_train = ops.linkp_loss_eva(emb, *self.gen_pn_edge_index('train'))
+        _, linkp_test = ops.linkp_loss_eva(emb.detach(), *self.gen_pn_edge_index('test'))
+        loss_structure = loss_structure * a.TeacherGNN.lossa_structure
+        loss = loss_structure if loss is None else loss + loss_structure
+        return loss, linkp_train, linkp_test
+
+    def run_trainSet_linkp(self):
+        self.teacherGNN.train()
+        assert self.args.has_loss_component_nodewise or self.args.has_loss_component_edgewise, \
+            'setting no node-wise and no edge-wise loss for teacherGNN! at least set one of them!'
+        loss, linkp_train, linkp_test = self.training_loss_linkp()
+        if self.args.has_loss_component_nodewise:
+            self._headtail_metrics()
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        value = self._checked(loss.item())
+        self.link_sampler().check()      # the loss has just been read: a negative slot that found no pair raises here
+        return value, float(linkp_train.item()), float(linkp_test.item())
+
+    def evaluate_linkp(self, model, mode):
+        """The MRR of a fresh `mode` sample on the eval-mode embeddings of `model` (:440-449)."""
+        if mode not in ('train', 'test'):
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
+        model.eval()
+        with torch.no_grad():
+            emb = model.get_emb4linkp(self.data.x, self.data.edge_index)
+            _, mrr = ops.linkp_loss_eva(emb, *self.gen_pn_edge_index(mode))
+        self.link_sampler().check()
+        return float(mrr.item())
+
+    def train_teacherGNN_linkp(self):
+        """train_teacherGNN with the edge-wise term in the objective: the same record layout ([loss_train (log), acc_train, acc_test, linkp_train,
+        linkp_test (+ head / tail / iso)], one column per epoch), rows 3 and 4 now real.  Eager steps only (no --hip_graph, no --resume).
+        Returns the whole record array [5 (+ 2 or 3), epochs]."""
+        self.setup_teacherGNN()
+        results_arr2D = []
+        for epoch in range(self.epochs):
+            self.epoch = epoch
+            loss_train, linkp_train, linkp_test = self.run_trainSet_linkp()
+            acc_train, acc_val, acc_test, loss_val = self.run_testSet()
+            results_arr2D.append([np.log(loss_train), acc_train * 100, acc_test * 100, linkp_train, linkp_test])
+            if self.args.want_headtail and self.args.has_loss_component_nodewise:
+                results_arr2D[-1].extend(self.bag['head_tail_iso'])
+            if epoch % 20 == 0:
+                print(f'Ep{epoch:03d}, acc @ train/test: {acc_train * 100:.1f}, {acc_test * 100:.1f}; MRR @ train/test: {linkp_train:.3f}, {linkp_test:.3f}')
+        save_model(self.teacherGNN, join(self.modeldir, 'teacherGNN'))
+        results_arr2D = np.array(results_arr2D).T
+        npy_dir = f'{self.resdir}/teacherGNN'
+        tag = npy_dir.replace('/', '@')
+        for row, name in enumerate(['loss_train', 'acc_train', 'acc_test', 'linkp_train', 'linkp_test']):
+            wzRec(results_arr2D[row], f'{name}@{tag}', want_save_npy=1, npy_dir=npy_dir)
+        return results_arr2D
+
     @staticmethod
     def _checked(value):
         """The loss has just been read (host synchronisation): a device-side error recorded by a kernel of this step — a tile hand-over

@@ -450,3 +450,35 @@ class graphUtils:
         n2 = len(subset_idx)
         edge_index, edge_attr = graphUtils.subgraph(subset_idx, adj_mtx.indices(), adj_mtx.values(), relabel_nodes=True, num_nodes=adj_mtx.shape[0])
         return torch.sparse_coo_tensor(edge_index, edge_attr, size=(n2, n2), device=adj_mtx.device).float().coalesce()
+
+
+# ---------------------------------------------------------------------------------------------
+# link prediction on already gathered rows (utils.py:754-791): thin forms over ops.linkp_loss_eva / ops.cal_MRR, which work on index pairs
+# into the full embedding matrix and are what the trainer calls
+# ---------------------------------------------------------------------------------------------
+def _linkp_stack(mats):
+    """The row matrices stacked into one matrix, and for each of them the row numbers it got."""
+    rows, at = [], 0
+    for m in mats:
+        rows.append(torch.arange(at, at + m.shape[0], device=m.device, dtype=torch.int32))
+        at += m.shape[0]
+    return torch.cat(mats, dim=0), rows
+
+
+def calc_score(h_emb, t_emb):
+    """DistMult scores sum(h * t, -1) of the row pairs (utils.py:754-757), detached: the loss has its own operator."""
+    from . import ops
+    emb, (h, t) = _linkp_stack([h_emb.detach(), t_emb.detach()])
+    return ops.linkp_loss_eva(emb, torch.stack([h, t]), torch.empty((2, 0), dtype=torch.int32, device=emb.device), return_parts=True)[2]
+
+
+def linkp_loss_eva(h_emb, t_emb, nh_emb, nt_emb):
+    """(predict_loss, mrr) of utils.py:759-774 for gathered positive (h, t) and negative (nh, nt) rows; the mrr is a 0-dim device tensor."""
+    from . import ops
+    emb, (h, t, nh, nt) = _linkp_stack([h_emb, t_emb, nh_emb, nt_emb])
+    return ops.linkp_loss_eva(emb, torch.stack([h, t]), torch.stack([nh, nt]))
+
+
+def cal_MRR(pos_score, neg_score):
+    from . import ops
+    return ops.cal_MRR(pos_score, neg_score)

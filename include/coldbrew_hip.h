@@ -774,6 +774,57 @@ size_t cb_csr_transpose_workspace_bytes(int64_t nnz);
 int cb_csr_transpose_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t m, int64_t n, int64_t nnz, int32_t* rowptr_t,
                          int32_t* col_t, float* val_t, void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * The teacher's edge-wise (link-prediction) term (trainer_node_classification.py:417-438, 507-563; utils.py:754-791; cb_linkp.hip): positive and
+ * negative edge samplers on the by-dst CSR (row v lists the sources u of the edges u -> v, columns ascending), the DistMult scores, the
+ * binary cross-entropy with logits, the MRR and the gradient of the loss with respect to the embedding matrix.
+ * The graph arrives as a cb_csr_view of which rowptr / col / n_rows / n_edges are read (square, plain column ids: col_flags == 0).
+ * mask [N] uint8: the train mask.  mode 0 = train (a node is valid if mask != 0), mode 1 = test (valid if mask == 0).
+ * Random draws: Philox4x32-10 (the generator of cb_dropout_f32, same fixed counter words 2 and 3), key = the 64-bit seed (+ *seed_dev when
+ * seed_dev != NULL: the device seed word of a captured step), counter = the 64-bit draw number slot * CB_LINKP_MAX_TRIES + try.  With the four
+ * output words r0..r3 a draw gives the integers hi64((r0 << 32 | r1) * n) and hi64((r2 << 32 | r3) * n) of [0, n).
+ * No float atomics; no host synchronisation; two calls with the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+#define CB_LINKP_MAX_TRIES 64
+int cb_linkp_max_tries(void);
+
+/* counts [N]: the number of entries of row v with a valid column if v is valid itself, else 0 (multiplicity and self loops counted as stored).
+ * The caller scans it into prefix [N + 1] (int32, prefix[0] = 0, prefix[N] = n_valid); once per (graph, mask, mode), off the step. */
+int cb_linkp_valid_counts_i32(const cb_csr_view* g, const uint8_t* mask, int32_t mode, int32_t* counts, void* stream);
+
+/* out [2, P]: P draws, uniform with replacement over the n_valid valid edges (np.random.choice(n_valid, samp_size_p), :523); row 0 = source
+ * (column id), row 1 = destination (CSR row).  One wavefront per draw (try 0 of its slot, first integer): binary search of prefix for the row,
+ * then the row is walked 64 columns at a time.  n_valid > 0.  A prefix that does not belong to (g, mask, mode) gives (-1, -1), never a fault. */
+int cb_linkp_positives_i32(const cb_csr_view* g, const uint8_t* mask, int32_t mode, const int32_t* prefix, int64_t n_valid, int64_t P,
+                           uint64_t seed, const uint64_t* seed_dev, int32_t* out, void* stream);
+
+/* out [2, Nn], Nn even: slot s < Nn / 2 writes (u, v) to column 2 s and (v, u) to column 2 s + 1 (`force_undirected=True`, :546).  mode 0: u and v
+ * are train_nodes[first integer], train_nodes[second integer] (train_nodes [n_train]: the train nodes, ascending); mode 1: the two integers of
+ * [0, N) themselves, rejected if both are train nodes.  Rejected in both modes: u == v, u in row v, v in row u.  A slot that finds no pair in
+ * CB_LINKP_MAX_TRIES tries writes -1 to its four cells and adds 1 to *n_failed (int32, integer atomic; the caller zeroes and reads it). */
+int cb_linkp_negatives_i32(const cb_csr_view* g, const uint8_t* mask, int32_t mode, const int32_t* train_nodes, int64_t n_train, int64_t Nn,
+                           uint64_t seed, const uint64_t* seed_dev, int32_t* out, int32_t* n_failed, void* stream);
+
+/* `linkp_loss_eva` (utils.py:759-774) on index pairs instead of gathered rows: emb [N, D] (ld >= D), pos [2, P], neg [2, Nn], P >= 1.
+ *     scores [P + Nn]: <emb[h_e], emb[t_e]> in fp32 (one wavefront per edge; float4 loads when D % 4 == 0, ld % 4 == 0 and emb is 16-byte aligned)
+ *     loss = mean_e max(s_e, 0) - s_e y_e + log1p(exp(-|s_e|)),  y = 1 for the P positives, 0 for the Nn negatives
+ *     mrr  = mean_i 1 / rank_i,  rank_i = 1 + #{j in [i k, (i + 1) k): neg_j > pos_i},  k = Nn / P (k = 0: every rank is 1); ties count for the positive
+ * loss and mrr are summed in float64 in one fixed order by one block and rounded once.  status [1]: the number of edges with an endpoint
+ * outside [0, N) (a failed sampler slot holds -1): such an edge is never used as an index, its score is NaN and so are loss and mrr. */
+int cb_linkp_loss_fwd_f32(const float* emb, int64_t ld, int64_t N, int64_t D, const int32_t* pos, int64_t P, const int32_t* neg, int64_t Nn,
+                          float* scores, float* loss, float* mrr, int32_t* status, void* stream);
+
+/* `cal_MRR` (utils.py:776-791) for callers that hold scores: the finishing kernel of cb_linkp_loss_fwd_f32 without the loss. */
+int cb_linkp_mrr_f32(const float* pos_score, int64_t P, const float* neg_score, int64_t Nn, float* mrr, void* stream);
+
+/* Backward: ds_e = g (sigmoid(s_e) - y_e) / (P + Nn) (g: DEVICE pointer to the upstream scalar); demb [N, D] (ldd >= D) =
+ * sum_e ds_e (emb[t_e] into row h_e, emb[h_e] into row t_e); rows no sample touches are zero.  The 2 (P + Nn) contributions are sorted by
+ * destination; one wavefront per distinct node adds its contributions in ascending contribution number (2 e for h_e, 2 e + 1 for t_e) in
+ * float64 and writes the row once.  Edges with an endpoint outside [0, N) contribute nothing. */
+size_t cb_linkp_bwd_workspace_bytes(int64_t P, int64_t Nn);
+int cb_linkp_loss_bwd_f32(const float* emb, int64_t ld, int64_t N, int64_t D, const int32_t* pos, int64_t P, const int32_t* neg, int64_t Nn,
+                          const float* scores, const float* g, float* demb, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
