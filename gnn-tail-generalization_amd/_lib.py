@@ -28,7 +28,15 @@ class CsrView(ctypes.Structure):
                 ('ws', _P), ('ws_bytes', _SZ)]
 
 
+class TrunkStore(ctypes.Structure):
+    """cb_trunk_store of include/coldbrew_hip.h: the trunk's store (ReLU, mask words, residual mix, dropout, activation output) as one argument.
+    Built by trunk.store_args, which also keeps the tensors behind the pointers alive for the call."""
+    _fields_ = [('mix_src', _P), ('ld_mix', _I64), ('mix_index', _P), ('c_act', ctypes.c_float), ('c_mix', ctypes.c_float), ('drop_p', ctypes.c_float),
+                ('seed', ctypes.c_uint64), ('seed_dev', _P), ('row0', _I64), ('relu_bits', _P), ('bits_relu_only', _I32), ('out_act', _P), ('ld_act', _I64)]
+
+
 _G = ctypes.POINTER(CsrView)
+_S = ctypes.POINTER(TrunkStore)
 
 # name -> (restype, argtypes); mirrors include/coldbrew_hip.h one to one
 SIGNATURES = {
@@ -66,8 +74,7 @@ SIGNATURES = {
                                             ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _SZ, _P]),
     'cb_gemm_tn_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
     'cb_gemm_tn_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
-    'cb_spmm_csr_fused_f32': (ctypes.c_int, [_G, _P, _P, _I32, _I64, _I64, _P, _P, _P, _I64, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64,
-                                             _P, _I32, _P, _I64, _P, _I64, _P]),
+    'cb_spmm_csr_fused_f32': (ctypes.c_int, [_G, _P, _P, _I32, _I64, _I64, _P, _P, _P, _I64, _S, _P, _I64, _P]),
     'cb_trunk_layer_bwd_f32': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _I64, _I64, ctypes.c_float, ctypes.c_uint64,
                                               _P, _I64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_uint64, ctypes.c_float, _P, _P, _P, _SZ, _P]),
     'cb_gemm_nn_bf16out_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, ctypes.c_int, _P, _SZ, _P]),
@@ -86,21 +93,16 @@ SIGNATURES = {
                                               ctypes.c_float, _I64, _P, _P, _P, _SZ, _P]),
     'cb_expand_rows_f32': (ctypes.c_int, [_P, _P, _I64, _I64, ctypes.c_float, _P, _P]),
     'cb_gemm_nn_store_rows_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64]),
-    'cb_gemm_nn_store_rows_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, ctypes.c_float,
-                                                 ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, ctypes.c_int, _P, _I64, _P, _SZ, _P]),
-    'cb_trunk_store_rows_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P,
-                                               ctypes.c_int, _P, _P, _P]),
+    'cb_gemm_nn_store_rows_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _P, _S, _P, _SZ, _P]),
+    'cb_trunk_store_rows_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _S, _P, _P]),
     'cb_agg_gemm_image_bytes': (_SZ, [_I64, _I64]),
     'cb_agg_gemm_image_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_int, _P, _SZ, _P]),
     'cb_spmm_gemm_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_fused_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
-                                              _P, _P, _P, _I64, _P, _I64, _P]),
+    'cb_spmm_gemm_fused_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _S, _P, _I64, _I32, _P, _P, _P, _I64, _P, _I64, _P]),
     'cb_agg_gemm_head_image_bytes': (_SZ, [_I64, _I64]),
     'cb_agg_gemm_head_image_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_int, _P, _SZ, _P]),
-    'cb_spmm_gemm_fused_head_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _I32,
-                                                   _P, _P, _I64, _P, _I64, _P]),
-    'cb_spmm_gemm_store_rows_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _P,
-                                                   _I64, _P, _I32, _P, _I64, _P, _I64, _P]),
+    'cb_spmm_gemm_fused_head_f32': (ctypes.c_int, [_G, _P, _I64, _P, _I64, _I64, _P, _P, _S, _P, _I64, _I32, _P, _P, _I64, _P, _I64, _P]),
+    'cb_spmm_gemm_store_rows_f32': (ctypes.c_int, [_G, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P, _S, _P, _I64, _P]),
     'cb_spmm_csr_weighted_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, ctypes.c_int, _P, _I64, _P]),
     'cb_spmm_edge_dot_f32': (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P]),
     'cb_gemm_nn_indrop_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64]),

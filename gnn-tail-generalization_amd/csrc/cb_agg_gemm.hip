@@ -40,30 +40,15 @@ struct GemmTail {
   int64_t ld_add;
   float* out;              // [rows, ld_out]
   int64_t ld_out;
-  // SR kernels only (described below): the store's factor and dropout
-  float c_act;
-  uint32_t thresh;
-  float keep_scale;
-  uint64_t seed;
-  const uint64_t* seed_dev;
-  int64_t row0;
+  TrunkStore st;
   int* err;                // device-visible error word (cb_error.hip): a tile hand-over that timed out is recorded here, never silent
   // NARROW kernels only (the output Linear as the tail of the last layer's aggregation, GCN.py:133-138): out[m][n] = acc + bias[n], n < n_out <= 64
   const float* bias;       // [n_out] or null (SR kernels: [256] or null)
   int n_out;
   // SR kernels only (rows-only forward, trunk.py _layer_on_rows: the trunk's store on a SUBSET of the node rows as the tail — the expression of
   // cb_gemm_nn_store_rows_f32, cb_gemm_core.h nn_epilogue EPI == 2): with gm = row_ids[m],
-  //   act = relu(rowscale[m] * acc + bias) (-> out_act);  out = dropout_{seed, row0 + gm}(c_act * act + c_mix * mix_src[mix_index[m] | gm])
-  //   mask words bits_out[gm][4] (bits_relu_only: act > 0 alone); thresh / keep_scale / seed / seed_dev / row0 / c_act above
+  //   act = relu(rowscale[m] * acc + bias) (-> st.out_act);  out = the store's value at node row gm, mask words st.bits[gm][4]
   const int64_t* row_ids;
-  const float* mix_src;     // or null
-  int64_t ld_mix;
-  const int64_t* mix_index; // or null
-  float c_mix;
-  unsigned long long* bits_out;   // [all node rows][4] or null
-  int bits_relu_only;
-  float* out_act;           // [rows, ld_act] or null
-  int64_t ld_act;
 };
 
 // (declared in cb_tile_gemm.h)
@@ -278,7 +263,7 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
   f32x16 acc[2][2];
   tile_times_image<kNS, kTLD>(tile, gt.image, w, lane, acc);
   ag_signal(freed, lane);      // the tile has been read for the last time
-  if (gt.bits_out && use > 0) ag_wait(mw_done, use, gt.err);      // the words of this buffer's previous tile have left
+  if (gt.st.bits && use > 0) ag_wait(mw_done, use, gt.err);      // the words of this buffer's previous tile have left
   const int r0 = t * kTM;
   const int n = 64 * w + (lane & 15) * 4;
   float bv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -303,7 +288,7 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
         const bool live = m < n_rows;
         float o[4] = {v.x, v.y, v.z, v.w}, mk[4] = {1.f, 1.f, 1.f, 1.f};
         int64_t gm = 0;
-        if (live) {      // the arithmetic of nn_epilogue's EPI == 2 branch (cb_gemm_core.h), term by term
+        if (live) {      // nn_epilogue's expression (cb_gemm_core.h), then the store's steps (cb_trunk_store.h)
           gm = gt.row_ids[m];
           const float rs = gt.rowscale ? gt.rowscale[m] : 1.f;
           const float ad[4] = {0.f, 0.f, 0.f, 0.f};
@@ -312,13 +297,13 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
             o[e] = o[e] * rs + ad[e] + bv[e];
             o[e] = fmaxf(o[e], 0.f);
           }
-          if (gt.thresh) keep4(seed_eff, ((gt.row0 + gm) * kND + n) >> 2, gt.thresh, gt.keep_scale, mk);
+          store_keep4(gt.st, seed_eff, gm, kND, n, mk);
         }
-        if (gt.bits_out) {
+        if (gt.st.bits) {
           // ballot e: bits 16 k .. 16 k + 15 = row (lane >> 4 == k) of this pass, columns 64 w .. 64 w + 63 -> bits 16 w .. of word e
           unsigned long long bal[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) bal[e] = __ballot(live && o[e] > 0.f && (gt.bits_relu_only || mk[e] != 0.f));
+          for (int e = 0; e < 4; ++e) bal[e] = __ballot(live && store_passes_grad(gt.st, o[e], mk[e]));
           if (lane < 16) {
             const int k = lane >> 2, e = lane & 3;
             unsigned long long be = bal[0];
@@ -329,23 +314,15 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
           }
         }
         if (live) {
-          if (gt.out_act) store_stream<4>(gt.out_act + m * gt.ld_act + n, o);
-          float x[4] = {o[0], o[1], o[2], o[3]};
-          if (gt.mix_src) {
-            const int64_t mr = gt.mix_index ? gt.mix_index[m] : gm;
-            const float4 qv = *reinterpret_cast<const float4*>(gt.mix_src + mr * gt.ld_mix + n);
-            x[0] = mix2(gt.c_act, o[0], gt.c_mix, qv.x); x[1] = mix2(gt.c_act, o[1], gt.c_mix, qv.y);
-            x[2] = mix2(gt.c_act, o[2], gt.c_mix, qv.z); x[3] = mix2(gt.c_act, o[3], gt.c_mix, qv.w);
-          }
-          if (gt.thresh) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] *= mk[e];
-          }
+          if (gt.st.out_act) store_stream<4>(gt.st.out_act + m * gt.st.ld_act + n, o);
+          float qv[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
+          if (gt.st.mix_src) gather<4>(qv, gt.st.mix_src + store_mix_row(gt.st, m, gm) * gt.st.ld_mix + n);
+          store_value(gt.st, o, qv, mk, x);
           store_stream<4>(gt.out + m * gt.ld_out + n, x);
         }
       }
     }
-  if (gt.bits_out) {
+  if (gt.st.bits) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wavefront's pieces are in LDS
     int prev = 0;
     if (lane == 0) prev = __hip_atomic_fetch_add(mw_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -356,7 +333,7 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
       if (m < n_rows) {
         const uint4* src = reinterpret_cast<const uint4*>(words + lane * 16);
         const uint4 w01 = src[0], w23 = src[1];
-        uint4* dst = reinterpret_cast<uint4*>(gt.bits_out + gt.row_ids[m] * 4);
+        uint4* dst = reinterpret_cast<uint4*>(gt.st.bits + gt.row_ids[m] * 4);
         dst[0] = w01;
         dst[1] = w23;
       }
@@ -379,7 +356,7 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
   const bool gathers = wv < kNG;
   const int w = gathers ? wv : wv - kNG;
   const int n_it = ((int)blockIdx.x < n_tiles) ? (n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-  const uint64_t seed_eff = SR ? (gt.seed_dev ? gt.seed + *gt.seed_dev : gt.seed) : 0ull;
+  const uint64_t seed_eff = SR ? store_seed(gt.st) : 0ull;
   if (threadIdx.x < 2) ready[threadIdx.x] = freed[threadIdx.x] = mw_cnt[threadIdx.x] = mw_done[threadIdx.x] = 0;
   __syncthreads();
   if (gathers) {
@@ -550,24 +527,20 @@ extern "C" int cb_spmm_gemm_f32(const cb_csr_view* g, const float* h, int64_t ld
 // of H's rows — g_out = dropout(c_act * relu(g_rowscale * (H @ B) + bias) + c_mix * mix_src[mix_index[m] | row_ids[m]]), out_act = the ReLU output,
 // relu_bits[row_ids[m]] = its mask words (cb_gemm_nn_store_rows_f32: the same values bit for bit).
 extern "C" int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* col_scale, float* out, int64_t ld_out,
-                                           const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src,
-                                           int64_t ld_mix, const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                           const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act,
-                                           int64_t ld_act, float* g_out, int64_t ld_gout, void* stream) {
+                                           const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const cb_trunk_store* store,
+                                           float* g_out, int64_t ld_gout, void* stream) {
+  const char* who = "cb_spmm_gemm_store_rows_f32";
   cb_csr_view v;
-  const int rc = agg_gemm_common_checks("cb_spmm_gemm_store_rows_f32", g, v, d, h, ld_h, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
+  const int rc = agg_gemm_common_checks(who, g, v, d, h, ld_h, image, nullptr, 0, g_out, ld_gout, nullptr, 0);
   if (rc != CB_OK || v.n_rows == 0) return rc;
-  CB_CHECK_ARG(out && aligned16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids && (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0 && ld_mix >= kND)) &&
-                   (!out_act || (aligned16(out_act) && ld_act % 4 == 0 && ld_act >= kND)) && (!relu_bits || aligned16(relu_bits)),
-               CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: null pointer or misaligned rows");
-  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_spmm_gemm_store_rows_f32: dropout p / row offset out of range");
+  CB_CHECK_ARG(out && aligned16(out) && ld_out % 4 == 0 && ld_out >= d && col_scale && row_ids, CB_E_INVALID, "%s: null pointer or misaligned rows", who);
+  const int rcs = check_trunk_store(who, store, kND);
+  if (rcs != CB_OK) return rcs;
+  CB_CHECK_ARG(aligned16(store->relu_bits), CB_E_INVALID, "%s: relu_bits must be 16-byte aligned (the mask words leave as 16-byte vectors)", who);
   Epilogue ep{nullptr, nullptr, 0, nullptr, 0, v.col_flags};
   ep.col_scale = col_scale;
   GemmTail gt{(const uint4*)image, g_rowscale, nullptr, 0, g_out, ld_gout};
-  gt.c_act = c_act; gt.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u; gt.keep_scale = 1.f / (1.f - drop_p);
-  gt.seed = seed; gt.seed_dev = seed_dev; gt.row0 = row0; gt.bias = bias;
-  gt.row_ids = row_ids; gt.mix_src = mix_src; gt.ld_mix = ld_mix; gt.mix_index = mix_index; gt.c_mix = c_mix;
-  gt.bits_out = (unsigned long long*)relu_bits; gt.bits_relu_only = bits_relu_only; gt.out_act = out_act; gt.ld_act = ld_act;
+  gt.bias = bias; gt.row_ids = row_ids; gt.st = make_trunk_store(*store);
   return launch_agg_gemm<false, false>(v, h, ld_h, ep, out, ld_out, (hipStream_t)stream, FusedEpi{}, gt);
 }
 
@@ -577,24 +550,21 @@ extern "C" int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h,
 // undefined; may be NULL when the plan has no hub rows).  10 GB less written per launch at the headline size.
 // n_out > 0: the narrow tail — g_out = logits [N, ld_gout >= n_out]; the common checks see a stand-in leading dimension.
 static int spmm_gemm_fused_impl(const char* who, const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
-                                const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
-                                int64_t ld_next, int32_t skip_next, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add,
-                                float* g_out, int64_t ld_gout, void* stream, const float* head_bias = nullptr, int n_out = 0) {
+                                const float* row_scale, const float* bias, const cb_trunk_store* store, float* out_next, int64_t ld_next, int32_t skip_next,
+                                const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream,
+                                const float* head_bias = nullptr, int n_out = 0) {
   cb_csr_view v;
   const int rc = agg_gemm_common_checks(who, g, v, d, h, ld_h, image, g_addend, ld_add, g_out, n_out > 0 ? kND : ld_gout, acc_init, ld_init);
   if (rc != CB_OK || v.n_rows == 0) return rc;
-  CB_CHECK_ARG((out_next || (skip_next && v.n_hubs == 0)) && aligned16(out_next) && ld_next % 4 == 0 && ld_next >= d &&
-                   (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0)) && (!out_act || (aligned16(out_act) && ld_act % 4 == 0 && ld_act >= d)),
-               CB_E_INVALID, "%s: 16-byte aligned rows required", who);
-  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "%s: dropout p out of range", who);
+  CB_CHECK_ARG((out_next || (skip_next && v.n_hubs == 0)) && aligned16(out_next) && ld_next % 4 == 0 && ld_next >= d, CB_E_INVALID,
+               "%s: 16-byte aligned rows required", who);
+  const int rcs = check_trunk_store(who, store, d);
+  if (rcs != CB_OK) return rcs;
+  CB_CHECK_ARG(!store->mix_index, CB_E_INVALID, "%s: the mix is taken at the node row (no mix_index)", who);
   Epilogue ep{row_scale, bias, 1, acc_init, ld_init, v.col_flags};
   FusedEpi fe{};
-  fe.mix_src = mix_src; fe.ld_mix = ld_mix; fe.c_act = c_act; fe.c_mix = c_mix;
-  fe.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
-  fe.keep_scale = 1.f / (1.f - drop_p);
-  fe.seed = seed; fe.seed_dev = seed_dev; fe.row0 = row0; fe.bits = (unsigned long long*)relu_bits; fe.bits_relu_only = bits_relu_only;
-  fe.out_act = out_act; fe.ld_act = ld_act; fe.out_next = out_next; fe.ld_next = ld_next; fe.d = (int)d;
+  fe.st = make_trunk_store(*store);
+  fe.out_next = out_next; fe.ld_next = ld_next; fe.d = (int)d;
   fe.skip_next = skip_next != 0;
   GemmTail gt{(const uint4*)image, g_rowscale, g_addend, ld_add, g_out, ld_gout};
   gt.bias = head_bias; gt.n_out = n_out;
@@ -603,14 +573,11 @@ static int spmm_gemm_fused_impl(const char* who, const cb_csr_view* g, const flo
 }
 
 extern "C" int cb_spmm_gemm_fused_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
-                                      const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                      const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
-                                      int64_t ld_next, int32_t skip_next,
-                                      const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout,
-                                      void* stream) {
-  return spmm_gemm_fused_impl("cb_spmm_gemm_fused_f32", g, acc_init, ld_init, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed,
-                              seed_dev, row0, relu_bits, bits_relu_only, out_act, ld_act, out_next, ld_next, skip_next, image, g_rowscale, g_addend, ld_add,
-                              g_out, ld_gout, stream);
+                                      const float* row_scale, const float* bias, const cb_trunk_store* store, float* out_next, int64_t ld_next,
+                                      int32_t skip_next, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out,
+                                      int64_t ld_gout, void* stream) {
+  return spmm_gemm_fused_impl("cb_spmm_gemm_fused_f32", g, acc_init, ld_init, h, ld_h, d, row_scale, bias, store, out_next, ld_next, skip_next, image, g_rowscale,
+                              g_addend, ld_add, g_out, ld_gout, stream);
 }
 
 // ---- the output Linear as the tail of the LAST layer's aggregation (round 5; GCN.py:133-138: Linear(dropout(X_L)) on the rows the store just made) ----
@@ -634,16 +601,14 @@ extern "C" int cb_agg_gemm_head_image_f32(const float* W, int64_t ld, int64_t K,
 // Fused trunk store of the LAST layer (as cb_spmm_gemm_fused_f32) + logits = out_next @ B + head_bias, B = the 256 x C matrix behind head_image.
 // skip_next: the last layer's activations are not written at all (hub rows excepted), only the logits leave.
 extern "C" int cb_spmm_gemm_fused_head_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
-                                           const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                           const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next,
-                                           int64_t ld_next, int32_t skip_next, const void* head_image, const float* head_bias, int64_t C, float* logits,
-                                           int64_t ld_logits, void* stream) {
+                                           const float* row_scale, const float* bias, const cb_trunk_store* store, float* out_next, int64_t ld_next,
+                                           int32_t skip_next, const void* head_image, const float* head_bias, int64_t C, float* logits, int64_t ld_logits,
+                                           void* stream) {
   const char* who = "cb_spmm_gemm_fused_head_f32";
   const bool empty = g && g->n_rows == 0;
   CB_CHECK_ARG(C >= 1 && C <= 32 * kNTn && (empty || (logits && ld_logits >= C)), CB_E_INVALID, "%s: 1 <= C <= 64 logits per row expected", who);
   // (the common checks want a 256-wide 16-byte aligned tail output: the narrow tail has its own rule — any ld >= C, float4 stores where ld % 4 == 0)
   CB_CHECK_ARG(empty || aligned16(logits), CB_E_INVALID, "%s: logits must be 16-byte aligned", who);
-  return spmm_gemm_fused_impl(who, g, acc_init, ld_init, h, ld_h, d, row_scale, bias, mix_src, ld_mix, c_act, c_mix, drop_p, seed, seed_dev, row0, relu_bits,
-                              bits_relu_only, out_act, ld_act, out_next, ld_next, skip_next, head_image, nullptr, nullptr, 0, logits, ld_logits, stream,
-                              head_bias, (int)C);
+  return spmm_gemm_fused_impl(who, g, acc_init, ld_init, h, ld_h, d, row_scale, bias, store, out_next, ld_next, skip_next, head_image, nullptr, nullptr, 0, logits,
+                              ld_logits, stream, head_bias, (int)C);
 }

@@ -24,6 +24,7 @@
 #include "cb_limb_core.h"
 #include "cb_philox.h"
 #include "cb_tile_gemm.h"
+#include "cb_trunk_store.h"
 
 namespace cb {
 
@@ -139,13 +140,8 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
       if (m < fa.M) {      // (wave-uniform)
         store_stream4(fa.x0 + m * fa.ld_x0 + 4 * lane, o);
         if (fa.bits) {
-          unsigned long long mine = 0ull;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const unsigned long long wq = __ballot(o[k] > 0.f);
-            if (lane == k) mine = wq;
-          }
-          if (lane < 4) fa.bits[m * 4 + lane] = mine;
+          const bool pos[4] = {o[0] > 0.f, o[1] > 0.f, o[2] > 0.f, o[3] > 0.f};
+          write_row_mask_words(fa.bits + m * 4, lane, pos);
         }
         if (fa.x0_drop) store_stream4(fa.x0_drop + m * fa.ld_drop + 4 * lane, xd);
       }

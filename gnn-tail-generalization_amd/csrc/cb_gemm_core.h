@@ -3,6 +3,7 @@
 #pragma once
 #include "cb_common.h"
 #include "cb_philox.h"
+#include "cb_trunk_store.h"
 
 namespace cb {
 
@@ -40,17 +41,11 @@ struct GemmEpilogue {
   DropSpec adrop;                   // ADROP kernels only: dropout of the A operand (thresh = 0: off)
   unsigned long long* relu_bits_out;   // 256-column tiles only: [M][4] mask words of (C > 0) after the ReLU (word q, bit L <-> column 4 L + q:
                                     // the layout of the aggregation's fused store) — the trunk's input stage reads them instead of C itself
-  // EPI == 2 kernels only (N == 256): the trunk's fused store on the rows of a SUBSET of the node rows (cb_trunk_store_rows_f32's pass in this
-  // epilogue): act = relu(rowscale * acc + addend + bias) -> out_act (optional); C = dropout(c_act * act + c_mix * mix_src[mix_index[m] | row_ids[m]]);
-  // relu_bits_out is indexed by the NODE row row_ids[m]; the dropout mask (thresh, keep_scale, seed, seed_dev, row0 above) is drawn there too
+  // EPI == 2 kernels only (N == 256): the trunk's store (cb_trunk_store.h) on the rows of a SUBSET of the node rows (cb_trunk_store_rows_f32's pass in
+  // this epilogue): act = relu(rowscale * acc + addend + bias) -> st.out_act (optional); C = the store's value; the mask words st.bits and the dropout mask
+  // are taken at the NODE row row_ids[m] (none of the EPI == 1 fields above is read)
   const int64_t* row_ids;
-  const float* mix_src;
-  int64_t ld_mix;
-  const int64_t* mix_index;
-  float c_act, c_mix;
-  int bits_relu_only;
-  float* out_act;
-  int64_t ld_act;
+  TrunkStore st;
 };
 
 template <int WM, int WN, int BKT = BK, int WTN = 2>
@@ -311,28 +306,15 @@ __device__ __forceinline__ void nn_epilogue(f32x16 (&acc)[2][WTN], float* __rest
         } else if constexpr (EPI == 2) {   // launch contract: N == 256 (TPR == 64: a wavefront holds one whole row), vector stores, ep.relu set
           const int64_t gm = ep.row_ids[m];
           float mk[4] = {1.f, 1.f, 1.f, 1.f};
-          if (ep.thresh) keep4(ep.seed_dev ? ep.seed + *ep.seed_dev : ep.seed, ((ep.row0 + gm) * N + n) >> 2, ep.thresh, ep.keep_scale, mk);
-          if (ep.relu_bits_out) {
-            unsigned long long mine = 0ull;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const unsigned long long wq = __ballot(o[q] > 0.f && (ep.bits_relu_only || mk[q] != 0.f));
-              if ((t & 63) == q) mine = wq;
-            }
-            if ((t & 63) < 4) ep.relu_bits_out[gm * 4 + (t & 63)] = mine;
+          store_keep4(ep.st, gm, N, n, mk);
+          if (ep.st.bits) store_mask_words(ep.st, ep.st.bits + gm * 4, t & 63, o, mk);
+          if (ep.st.out_act) store4(ep.st.out_act + m * ep.st.ld_act + n, o[0], o[1], o[2], o[3], 0);
+          float qv[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
+          if (ep.st.mix_src) {
+            const float4 q4 = *reinterpret_cast<const float4*>(ep.st.mix_src + store_mix_row(ep.st, m, gm) * ep.st.ld_mix + n);
+            qv[0] = q4.x; qv[1] = q4.y; qv[2] = q4.z; qv[3] = q4.w;
           }
-          if (ep.out_act) store4(ep.out_act + m * ep.ld_act + n, o[0], o[1], o[2], o[3], 0);
-          float x[4] = {o[0], o[1], o[2], o[3]};
-          if (ep.mix_src) {
-            const int64_t mr = ep.mix_index ? ep.mix_index[m] : gm;
-            const float4 qv = *reinterpret_cast<const float4*>(ep.mix_src + mr * ep.ld_mix + n);
-            x[0] = mix2(ep.c_act, o[0], ep.c_mix, qv.x); x[1] = mix2(ep.c_act, o[1], ep.c_mix, qv.y);
-            x[2] = mix2(ep.c_act, o[2], ep.c_mix, qv.z); x[3] = mix2(ep.c_act, o[3], ep.c_mix, qv.w);
-          }
-          if (ep.thresh) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) x[q] *= mk[q];
-          }
+          store_value(ep.st, o, qv, mk, x);
           store4(C + m * ldc + n, x[0], x[1], x[2], x[3], 0);
         } else {
           float* cp = C + m * ldc + n;
@@ -344,13 +326,8 @@ __device__ __forceinline__ void nn_epilogue(f32x16 (&acc)[2][WTN], float* __rest
           }
           if constexpr (TPR == 64) {   // a wavefront holds one whole 256-column row: four ballots are its mask words
             if (ep.relu_bits_out) {
-              unsigned long long mine = 0ull;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const unsigned long long wq = __ballot(o[q] > 0.f);
-                if ((t & 63) == q) mine = wq;
-              }
-              if ((t & 63) < 4) ep.relu_bits_out[m * 4 + (t & 63)] = mine;
+              const bool pos[4] = {o[0] > 0.f, o[1] > 0.f, o[2] > 0.f, o[3] > 0.f};
+              write_row_mask_words(ep.relu_bits_out + m * 4, t & 63, pos);
             }
           }
           if constexpr (EPI == 1) {   // launch contract: N % 4 == 0, 16-byte aligned out2 rows

@@ -228,31 +228,26 @@ extern "C" int cb_spmm_csr_prop_f32(const cb_csr_view* g, const float* h, int64_
 // bf16 rows when the halo rows crossed the links as bf16).  row_ids: over a CSR whose rows are a SUBSET of the node rows (rows-only forward, trunk.py) —
 // row r of the CSR / of row_scale / of out_act / out_next is node row row_ids[r] (ascending); mix_src, relu_bits and the dropout mask are taken at the node row.
 extern "C" int cb_spmm_csr_fused_f32(const cb_csr_view* g, const int32_t* row_ids, const void* h, int32_t h_bf16, int64_t ld_h, int64_t d,
-                                     const float* row_scale, const float* bias, const float* acc_init, int64_t ld_init, const float* mix_src,
-                                     int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                                     uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                                     void* stream) {
+                                     const float* row_scale, const float* bias, const float* acc_init, int64_t ld_init, const cb_trunk_store* store,
+                                     float* out_next, int64_t ld_next, void* stream) {
   const char* who = "cb_spmm_csr_fused_f32";
   CB_CHECK_ARG(d > 0 && d % 256 == 0, CB_E_INVALID, "%s: d must be a positive multiple of 256", who);
   cb_csr_view v;
   const int rc = check_csr_view(who, g, d, v);
   if (rc != CB_OK || v.n_rows == 0) return rc;
   CB_CHECK_ARG(h && out_next, CB_E_INVALID, "%s: null pointer", who);
-  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, CB_E_INVALID, "%s: dropout p out of range", who);
+  const int rcs = check_trunk_store(who, store, d);
+  if (rcs != CB_OK) return rcs;
+  CB_CHECK_ARG(!store->mix_index, CB_E_INVALID, "%s: the mix is taken at the node row (no mix_index)", who);
   CB_CHECK_ARG(!row_ids || (!acc_init && !h_bf16), CB_E_INVALID, "%s: a row subset needs fp32 rows and no running sums", who);
-  const bool al = ((uintptr_t)h % (h_bf16 ? 8 : 16) == 0) && aligned16(out_next) && ld_h % 4 == 0 && ld_next % 4 == 0 &&
-                  (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0)) &&
-                  (!out_act || (aligned16(out_act) && ld_act % 4 == 0));
+  const bool al = ((uintptr_t)h % (h_bf16 ? 8 : 16) == 0) && aligned16(out_next) && ld_h % 4 == 0 && ld_next % 4 == 0;
   CB_CHECK_ARG(al && ld_h >= d && ld_next >= d, CB_E_INVALID, "%s: 16-byte aligned rows required", who);
   CB_CHECK_ARG(!acc_init || (aligned16(acc_init) && ld_init % 4 == 0 && ld_init >= d), CB_E_INVALID,
                "%s: acc_init must be 16-byte aligned rows of at least d floats", who);
   Epilogue ep{row_scale, bias, 1, acc_init, ld_init, v.col_flags};
   FusedEpi fe{};
-  fe.mix_src = mix_src; fe.ld_mix = ld_mix; fe.c_act = c_act; fe.c_mix = c_mix;
-  fe.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
-  fe.keep_scale = 1.f / (1.f - drop_p);
-  fe.seed = seed; fe.seed_dev = seed_dev; fe.row0 = row0; fe.bits = (unsigned long long*)relu_bits; fe.bits_relu_only = bits_relu_only;
-  fe.out_act = out_act; fe.ld_act = ld_act; fe.out_next = out_next; fe.ld_next = ld_next; fe.d = (int)d; fe.row_ids = row_ids;
+  fe.st = make_trunk_store(*store);
+  fe.out_next = out_next; fe.ld_next = ld_next; fe.d = (int)d; fe.row_ids = row_ids;
   if (h_bf16) return launch_spmm<4, true, bf16_t>(v, (const bf16_t*)h, ld_h, d, ep, out_next, ld_next, (hipStream_t)stream, fe);
   return launch_spmm<4, true, float>(v, (const float*)h, ld_h, d, ep, out_next, ld_next, (hipStream_t)stream, fe);
 }
@@ -277,11 +272,10 @@ extern "C" int cb_spmm_csr_store_bwd_f32(const cb_csr_view* g, const float* h, i
                CB_E_INVALID, "%s: 16-byte aligned rows required", who);
   Epilogue ep{row_scale, nullptr, 0, nullptr, 0, v.col_flags};
   FusedEpi fe{};
-  fe.bwd = 1; fe.bwd_rowscale = bwd_rowscale; fe.c_act = c_act;
-  fe.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
-  fe.keep_scale = 1.f / (1.f - drop_p);
-  fe.seed = seed; fe.seed_dev = seed_dev; fe.row0 = row0; fe.bits = (unsigned long long*)relu_bits;
-  fe.out_act = out_g; fe.ld_act = ld_g; fe.out_next = out_gr; fe.ld_next = ld_gr; fe.d = (int)d;
+  fe.bwd = 1; fe.bwd_rowscale = bwd_rowscale; fe.st.c_act = c_act;
+  set_store_dropout(fe.st, drop_p);
+  fe.st.seed = seed; fe.st.seed_dev = seed_dev; fe.st.row0 = row0; fe.st.bits = (unsigned long long*)relu_bits;
+  fe.st.out_act = out_g; fe.st.ld_act = ld_g; fe.out_next = out_gr; fe.ld_next = ld_gr; fe.d = (int)d;
   return launch_spmm<4, true, float>(v, h, ld_h, d, ep, out_gr, ld_gr, (hipStream_t)stream, fe);
 }
 
@@ -352,11 +346,10 @@ extern "C" int cb_spmm_csr_store_bwd_mix_f32(const cb_csr_view* g, const float* 
                "%s: column-sum workspace missing/too small", who);
   Epilogue ep{row_scale, nullptr, 0, nullptr, 0, v.col_flags};
   FusedEpi fe{};
-  fe.bwd = 1; fe.bwd_rowscale = bwd_rowscale; fe.c_act = c_act;
-  fe.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u;
-  fe.keep_scale = 1.f / (1.f - drop_p);
-  fe.seed = seed; fe.seed_dev = seed_dev; fe.row0 = row0; fe.bits = (unsigned long long*)relu_bits;
-  fe.out_act = out_m; fe.ld_act = ld_m; fe.out_next = out_gr; fe.ld_next = ld_gr; fe.d = (int)d;
+  fe.bwd = 1; fe.bwd_rowscale = bwd_rowscale; fe.st.c_act = c_act;
+  set_store_dropout(fe.st, drop_p);
+  fe.st.seed = seed; fe.st.seed_dev = seed_dev; fe.st.row0 = row0; fe.st.bits = (unsigned long long*)relu_bits;
+  fe.st.out_act = out_m; fe.st.ld_act = ld_m; fe.out_next = out_gr; fe.ld_next = ld_gr; fe.d = (int)d;
   fe.mx_n = n_mix; fe.mx_c = c_mix;
   for (int q = 0; q < n_mix; ++q) {
     CB_CHECK_ARG(mix_g[q] && mix_pos[q] && aligned16(mix_g[q]), CB_E_INVALID, "%s: null or misaligned mix operand %d", who, q);

@@ -4,6 +4,7 @@
 #pragma once
 #include "cb_common.h"
 #include "cb_philox.h"
+#include "cb_trunk_store.h"
 
 namespace cb {
 
@@ -154,25 +155,12 @@ __device__ __forceinline__ void write_row_lp(float* __restrict__ out_row, const 
   }
 }
 
-// Extended epilogue of the fused residual trunk (GCN.py:127-133 folded into the aggregation's store):
-//   act    = relu(row_scale * acc + bias)                      -> ReLU mask bits and/or the activation itself
-//   x_next = dropout_{seed}((1-alpha) * act + alpha * mix_src[row])   -> the next stage's input
+// Extended epilogue of the fused residual trunk (GCN.py:127-133 folded into the aggregation's store): the trunk's store (cb_trunk_store.h) applied to
+//   y = row_scale * acc + bias,   x_next -> out_next (the next stage's input)
 // Only for VEC = 4 full tiles (d % 256 == 0): lane l owns columns 4l..4l+3 of its 256-wide tile, the mask
 // word k of a (row, tile) holds the ballot of component k over the 64 lanes.
 struct FusedEpi {
-  const float* mix_src;   // [N, ld_mix] or null (no mix)
-  int64_t ld_mix;
-  float c_act, c_mix;     // (1 - alpha), alpha
-  uint32_t thresh;        // dropout threshold (0 = keep everything)
-  float keep_scale;       // 1 / (1 - p)
-  uint64_t seed;
-  const uint64_t* seed_dev;  // hipGraph mode: per-step seed part in device memory (added to `seed`), or null
-  int64_t row0;           // global index of local row 0 (node-sharded runs draw the unsharded mask)
-  unsigned long long* bits;  // [N][d/256][4] or null
-  int bits_relu_only;     // mask words hold (act > 0) alone, not (act > 0 AND kept by this store's dropout): the 'Residual' trunk, whose backward
-                          // also sends the NEXT layer's mix gradient through this ReLU (under another dropout mask)
-  float* out_act;         // [N, ld_act] or null
-  int64_t ld_act;
+  TrunkStore st;          // (no mix_index: the mix is taken at the node row)
   float* out_next;        // [N, ld_next]
   int64_t ld_next;
   int d;
@@ -202,31 +190,32 @@ struct FusedEpi {
 // row ahead by the caller; cs: the wavefront's running column sums of c_act * keep * g under the mask word.
 __device__ __forceinline__ void fused_store_bwd_mix(const FusedEpi& fe, int64_t row, int c0, const float (&acc)[4], float scale, float (&x)[4],
                                                     const float (&xm)[2][4], const int (&xp)[2], float (&cs)[4]) {
-  const uint64_t sd = fe.seed_dev ? *fe.seed_dev : 0ull;
-  const int64_t quad = ((fe.row0 + row) * fe.d + c0) >> 2;
+  const TrunkStore& st = fe.st;
+  const uint64_t sd = st.seed_dev ? *st.seed_dev : 0ull;
+  const int64_t quad = ((st.row0 + row) * fe.d + c0) >> 2;
   float m[4] = {1.f, 1.f, 1.f, 1.f}, mm[4] = {0.f, 0.f, 0.f, 0.f};
-  if (fe.thresh) keep4(fe.seed + sd, quad, fe.thresh, fe.keep_scale, m);
+  if (st.thresh) keep4(st.seed + sd, quad, st.thresh, st.keep_scale, m);
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     if (q < fe.mx_n && xp[q] >= 0) {      // (wave-uniform)
       float mq[4] = {1.f, 1.f, 1.f, 1.f};
-      if (fe.thresh) keep4(fe.mx_seed[q] + sd, quad, fe.thresh, fe.keep_scale, mq);
+      if (st.thresh) keep4(fe.mx_seed[q] + sd, quad, st.thresh, st.keep_scale, mq);
 #pragma unroll
       for (int i = 0; i < 4; ++i) mm[i] += fe.mx_c * (xm[q][i] * mq[i]);
     }
   }
-  const unsigned long long* bw = fe.bits + (row * (fe.d >> 8) + (c0 >> 8)) * 4;
+  const unsigned long long* bw = st.bits + (row * (fe.d >> 8) + (c0 >> 8)) * 4;
   const float rs = fe.bwd_rowscale ? fe.bwd_rowscale[row] : 1.f;
   const int lane = lane_id();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float gm = scale_add(acc[i], scale, 0.f) * m[i];
     mm[i] += fe.mx_c * gm;
-    const float t = ((bw[i] >> lane) & 1ull) ? fe.c_act * gm : 0.f;
+    const float t = ((bw[i] >> lane) & 1ull) ? st.c_act * gm : 0.f;
     cs[i] += t;
     x[i] = t * rs;                       // (cb_trunk_layer_bwd_f32's expressions, in its order)
   }
-  store_stream<4>(fe.out_act + row * fe.ld_act + c0, mm);
+  store_stream<4>(st.out_act + row * st.ld_act + c0, mm);
   store_stream<4>(fe.out_next + row * fe.ld_next + c0, x);
 }
 
@@ -234,46 +223,31 @@ __device__ __forceinline__ void fused_store_bwd_mix(const FusedEpi& fe, int64_t 
 // grow: the node row of `row` (== row unless fe.row_ids)
 __device__ __forceinline__ void fused_store(const FusedEpi& fe, int64_t row, int c0, const float (&acc)[4], float scale,
                                             const float (&b)[4], const float (&rmix)[4], float (&x)[4], int64_t grow) {
+  const TrunkStore& st = fe.st;
   float a[4], m[4] = {1.f, 1.f, 1.f, 1.f};
   if (fe.bwd) {
     float g4[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) g4[i] = scale_add(acc[i], scale, b[i]);      // (b = 0: what the plain store writes)
-    if (fe.out_act) store_stream<4>(fe.out_act + row * fe.ld_act + c0, g4);
-    if (fe.thresh) keep4(fe.seed_dev ? fe.seed + *fe.seed_dev : fe.seed, ((fe.row0 + grow) * fe.d + c0) >> 2, fe.thresh, fe.keep_scale, m);
-    const unsigned long long* bw = fe.bits + (grow * (fe.d >> 8) + (c0 >> 8)) * 4;
+    if (st.out_act) store_stream<4>(st.out_act + row * st.ld_act + c0, g4);
+    store_keep4(st, grow, fe.d, c0, m);
+    const unsigned long long* bw = st.bits + (grow * (fe.d >> 8) + (c0 >> 8)) * 4;
     const float rs = fe.bwd_rowscale ? fe.bwd_rowscale[grow] : 1.f;
     const int lane = lane_id();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float gm = g4[i] * m[i];
-      x[i] = ((bw[i] >> lane) & 1ull) ? (fe.c_act * gm) * rs : 0.f;      // (cb_trunk_layer_bwd_f32's expressions, in its order)
+      x[i] = ((bw[i] >> lane) & 1ull) ? (st.c_act * gm) * rs : 0.f;      // (cb_trunk_layer_bwd_f32's expressions, in its order)
     }
     store_stream<4>(fe.out_next + row * fe.ld_next + c0, x);
     return;
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) a[i] = fmaxf(scale_add(acc[i], scale, b[i]), 0.f);
-  if (fe.thresh) keep4(fe.seed_dev ? fe.seed + *fe.seed_dev : fe.seed, ((fe.row0 + grow) * fe.d + c0) >> 2, fe.thresh, fe.keep_scale, m);
-  if (fe.bits) {
-    // mask word k of (row, tile), bit l: the element (column 4 l + k) passes gradient to the pre-activation — ReLU positive AND kept
-    // by the dropout.  The backward kernels that also regenerate the keep-mask are unaffected (masking twice is masking once).
-    const int lane = lane_id();
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned long long w = __ballot(a[k] > 0.f && (fe.bits_relu_only || m[k] != 0.f));
-      if (lane == k) mine = w;
-    }
-    if (lane < 4) fe.bits[(grow * (fe.d >> 8) + (c0 >> 8)) * 4 + lane] = mine;
-  }
-  if (fe.out_act) store_stream<4>(fe.out_act + row * fe.ld_act + c0, a);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = fe.mix_src ? mix2(fe.c_act, a[i], fe.c_mix, rmix[i]) : a[i];
-  if (fe.thresh) {      // kept as a statement of its own: the same rounding sequence as cb_axpby_f32 followed by cb_dropout_f32
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] *= m[i];
-  }
+  store_keep4(st, grow, fe.d, c0, m);
+  if (st.bits) store_mask_words(st, st.bits + (grow * (fe.d >> 8) + (c0 >> 8)) * 4, lane_id(), a, m);
+  if (st.out_act) store_stream<4>(st.out_act + row * st.ld_act + c0, a);
+  store_value(st, a, rmix, m, x);
   if (!fe.skip_next) store_stream<4>(fe.out_next + row * fe.ld_next + c0, x);
 }
 
@@ -339,9 +313,9 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
   float rmix[4] = {0.f, 0.f, 0.f, 0.f};   // FUSED: mix_src row of local row `cur`, fetched one row ahead
   auto gid_of = [&](int i) -> int64_t { return fe.row_ids ? (int64_t)bcast_lane(my_gid_v, i) : (int64_t)(r0 + i); };
   if constexpr (FUSED) {
-    if (fe.mix_src) {
+    if (fe.st.mix_src) {
       float t[VEC];
-      gather_stream<VEC>(t, fe.mix_src + gid_of(rlo) * fe.ld_mix + c0);
+      gather_stream<VEC>(t, fe.st.mix_src + gid_of(rlo) * fe.st.ld_mix + c0);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) rmix[i] = t[i];
     }
@@ -396,9 +370,9 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
         fused_store(fe, (int64_t)(r0 + cur), c0, a4, s, b4, rmix, x4, gid_of(cur));
       }
       if constexpr (TLD > 0) *reinterpret_cast<float4*>(tile_lane + cur * TLD) = make_float4(x4[0], x4[1], x4[2], x4[3]);
-      if (fe.mix_src && cur + 1 < nr) {
+      if (fe.st.mix_src && cur + 1 < nr) {
         float t[VEC];
-        gather_stream<VEC>(t, fe.mix_src + gid_of(cur + 1) * fe.ld_mix + c0);
+        gather_stream<VEC>(t, fe.st.mix_src + gid_of(cur + 1) * fe.st.ld_mix + c0);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) rmix[i] = t[i];
       }
@@ -715,9 +689,9 @@ __global__ void __launch_bounds__(256) k_spmm_hub_finish(int d, int n_hubs, cons
 #pragma unroll
     for (int k = 0; k < 4; ++k) { a4[k] = acc[k % VEC]; b4[k] = bvec[k % VEC]; }
     const int64_t grow = fe.row_ids ? (int64_t)fe.row_ids[row] : (int64_t)row;
-    if (fe.mix_src) {
+    if (fe.st.mix_src) {
       float t[VEC];
-      gather_stream<VEC>(t, fe.mix_src + grow * fe.ld_mix + c0);
+      gather_stream<VEC>(t, fe.st.mix_src + grow * fe.st.ld_mix + c0);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) rmix[k] = t[k];
     }

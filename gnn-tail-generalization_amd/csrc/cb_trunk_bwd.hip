@@ -3,6 +3,7 @@
 #include "cb_philox.h"
 #include "cb_reduce.h"
 #include "cb_rowpass.h"
+#include "cb_trunk_store.h"
 
 namespace cb {
 
@@ -283,40 +284,25 @@ __global__ void __launch_bounds__(kBlock) k_trunk_input_bwd_multi(const float* _
 //   act = relu(y[r]);  out[r] = dropout_seed((c_act * act + c_mix * mix_src[mix_index[r]]));  mask words at the GLOBAL row row_index[r].
 // y / out: compact [n_rows, d]; relu_bits: the full array; mix_src (may be null): its row mix_index[r] (mix_index null: row_index[r], i.e. the full
 // array).  One wavefront per row, lane l = columns 4l .. 4l+3 of each tile.
-__global__ void __launch_bounds__(kBlock) k_trunk_store_rows(const float* __restrict__ y, const int64_t* __restrict__ ridx, int64_t n_rows, int d,
-                                                             const float* __restrict__ mix_src, int64_t ld_mix, const int64_t* __restrict__ midx, float c_act,
-                                                             float c_mix, uint32_t thresh,
-                                                             float keep_scale, uint64_t seed, const uint64_t* __restrict__ seed_dev, int64_t row0,
-                                                             unsigned long long* __restrict__ bits, int relu_only, float* __restrict__ out,
-                                                             float* __restrict__ out_act) {
-  if (seed_dev) seed += *seed_dev;
+__global__ void __launch_bounds__(kBlock) k_trunk_store_rows(const float* __restrict__ y, const int64_t* __restrict__ ridx, int64_t n_rows, int d, TrunkStore st,
+                                                             float* __restrict__ out) {
+  const uint64_t seed = store_seed(st);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tiles = d >> 8;
   for (int64_t r = (int64_t)blockIdx.x * (kBlock / kWave) + w; r < n_rows; r += (int64_t)gridDim.x * (kBlock / kWave)) {
-    const int64_t rr = ridx[r], mr = midx ? midx[r] : rr;
+    const int64_t rr = ridx[r], mr = store_mix_row(st, r, rr);
     for (int tile = 0; tile < tiles; ++tile) {
       const int c = tile * 256 + lane * 4;
       const float4 y4 = *reinterpret_cast<const float4*>(y + r * d + c);
-      float a[4] = {fmaxf(y4.x, 0.f), fmaxf(y4.y, 0.f), fmaxf(y4.z, 0.f), fmaxf(y4.w, 0.f)}, m[4] = {1.f, 1.f, 1.f, 1.f};
-      if (thresh) keep4(seed, ((row0 + rr) * d + c) >> 2, thresh, keep_scale, m);
-      if (bits) {
-        unsigned long long mine = 0ull;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const unsigned long long wq = __ballot(a[k] > 0.f && (relu_only || m[k] != 0.f));
-          if (lane == k) mine = wq;
-        }
-        if (lane < 4) bits[(rr * tiles + tile) * 4 + lane] = mine;
+      const float a[4] = {fmaxf(y4.x, 0.f), fmaxf(y4.y, 0.f), fmaxf(y4.z, 0.f), fmaxf(y4.w, 0.f)};
+      float m[4] = {1.f, 1.f, 1.f, 1.f}, q[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
+      store_keep4(st, seed, rr, d, c, m);
+      if (st.bits) store_mask_words(st, st.bits + (rr * tiles + tile) * 4, lane, a, m);
+      if (st.out_act) *reinterpret_cast<float4*>(st.out_act + r * st.ld_act + c) = make_float4(a[0], a[1], a[2], a[3]);
+      if (st.mix_src) {
+        const float4 q4 = *reinterpret_cast<const float4*>(st.mix_src + mr * st.ld_mix + c);
+        q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
       }
-      if (out_act) *reinterpret_cast<float4*>(out_act + r * d + c) = make_float4(a[0], a[1], a[2], a[3]);
-      float x[4] = {a[0], a[1], a[2], a[3]};
-      if (mix_src) {
-        const float4 q = *reinterpret_cast<const float4*>(mix_src + mr * ld_mix + c);
-        x[0] = mix2(c_act, a[0], c_mix, q.x); x[1] = mix2(c_act, a[1], c_mix, q.y); x[2] = mix2(c_act, a[2], c_mix, q.z); x[3] = mix2(c_act, a[3], c_mix, q.w);
-      }
-      if (thresh) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] *= m[k];
-      }
+      store_value(st, a, q, m, x);
       *reinterpret_cast<float4*>(out + r * d + c) = make_float4(x[0], x[1], x[2], x[3]);
     }
   }
@@ -512,19 +498,15 @@ extern "C" int cb_trunk_input_bwd_multi_cs_f32(const float* g, uint64_t seed, in
                                     stream, n_cs, cs_src, cs_bits, cs_c, colsum2, ws2, ws2_bytes);
 }
 
-extern "C" int cb_trunk_store_rows_f32(const float* y, const int64_t* row_index, int64_t n_rows, int64_t d, const float* mix_src, int64_t ld_mix,
-                                       const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits,
-                                       int bits_relu_only, float* out, float* out_act, void* stream) {
-  CB_CHECK_ARG(n_rows >= 0 && d > 0 && d % 256 == 0 && d < (1 << 20), CB_E_INVALID, "cb_trunk_store_rows_f32: d must be a multiple of 256");
+extern "C" int cb_trunk_store_rows_f32(const float* y, const int64_t* row_index, int64_t n_rows, int64_t d, const cb_trunk_store* store, float* out, void* stream) {
+  const char* who = "cb_trunk_store_rows_f32";
+  CB_CHECK_ARG(n_rows >= 0 && d > 0 && d % 256 == 0 && d < (1 << 20), CB_E_INVALID, "%s: d must be a multiple of 256", who);
   if (n_rows == 0) return CB_OK;
-  CB_CHECK_ARG(y && row_index && out && aligned16(y) && aligned16(out) && (!out_act || aligned16(out_act)) && (!mix_src || (aligned16(mix_src) && ld_mix % 4 == 0 && ld_mix >= d)) &&
-                   (!relu_bits || (uintptr_t)relu_bits % 8 == 0),
-               CB_E_INVALID, "cb_trunk_store_rows_f32: null or misaligned pointer");
-  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_trunk_store_rows_f32: dropout p / row offset out of range");
+  CB_CHECK_ARG(y && row_index && out && aligned16(y) && aligned16(out), CB_E_INVALID, "%s: null or misaligned pointer", who);
+  const int rcs = check_trunk_store(who, store, d);
+  if (rcs != CB_OK) return rcs;
   const int nb = grid_for(n_rows * kWave);      // one wavefront per row
-  const DropParams dp = drop_params(drop_p);
-  hipLaunchKernelGGL(k_trunk_store_rows, dim3((unsigned)nb), dim3(kBlock), 0, (hipStream_t)stream, y, row_index, n_rows, (int)d, mix_src, ld_mix, mix_index, c_act, c_mix,
-                     dp.thresh, dp.keep_scale, seed, seed_dev, row0, (unsigned long long*)relu_bits, bits_relu_only, out, out_act);
+  hipLaunchKernelGGL(k_trunk_store_rows, dim3((unsigned)nb), dim3(kBlock), 0, (hipStream_t)stream, y, row_index, n_rows, (int)d, make_trunk_store(*store), out);
   CB_LAUNCH_CHECK();
   return CB_OK;
 }

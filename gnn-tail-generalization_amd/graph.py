@@ -596,7 +596,6 @@ class CSRGraph:
         store on the node rows row_ids (int64 [N]) of this CSR's rows — act = relu(rowscale * (H @ B) + bias), out = dropout(c_act * act + c_mix *
         mix[mix_index | row_ids]), mask words in bits (the full [n_nodes, 1, 4] array, rows row_ids written) — with B the 256 x 256 matrix behind
         `image` (weight_image): the values of spmm(col_scale=...) followed by gemm.mm_nn_store_rows, bit for bit."""
-        import ctypes
         from . import ops
         lib = _lib.load()
         _lib.require_device(h, col_scale, image, rowscale, bias, row_ids, mix, mix_index, bits)
@@ -622,10 +621,9 @@ class CSRGraph:
             ev0.record()
         with torch.cuda.device(dev):
             _lib.check(lib.cb_spmm_gemm_store_rows_f32(view, _lib.ptr(h), h.stride(0), d, _lib.ptr(col_scale.contiguous()), _lib.ptr(out), d, _lib.ptr(image),
-                                                       _lib.ptr(rowscale), _lib.ptr(bias), _lib.ptr(row_ids), _lib.ptr(mix),
-                                                       mix.stride(0) if mix is not None else 0, _lib.ptr(mix_index), float(c_act), float(c_mix), float(p),
-                                                       ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0), _lib.ptr(bits), int(bool(relu_only)),
-                                                       _lib.ptr(act), 256, _lib.ptr(g_out), 256, _lib.stream_ptr()),
+                                                       _lib.ptr(rowscale), _lib.ptr(bias), _lib.ptr(row_ids),
+                                                       ops.store_args(mix, mix_index, c_act, c_mix, p, seed, row0, bits, relu_only, act),
+                                                       _lib.ptr(g_out), 256, _lib.stream_ptr()),
                        'cb_spmm_gemm_store_rows_f32')
         if prof is not None:
             ev1.record()

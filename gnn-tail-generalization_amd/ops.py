@@ -72,6 +72,18 @@ def seed_dev_ptr():
     return _lib.ptr(_graph_seed) if _graph_seed is not None else None
 
 
+def store_args(mix, mix_index, c_act, c_mix, p, seed, row0, bits, relu_only, act):
+    """The trunk's store as the one argument the entries take (cb_trunk_store, include/coldbrew_hip.h): mix (+ mix_index: its row per stored row, where
+    it is a compact matrix), the mix factors, the dropout (p, seed, the graph-replay seed word, row0 = global index of node row 0), the mask words `bits`
+    (relu_only: ReLU mask alone) and the activation output `act`; tensors may be None.  The struct holds on to the tensors, so they live as long as it."""
+    st = _lib.TrunkStore(mix.data_ptr() if mix is not None else None, mix.stride(0) if mix is not None else 0,
+                         mix_index.data_ptr() if mix_index is not None else None, float(c_act), float(c_mix), float(p), int(seed),
+                         _graph_seed.data_ptr() if _graph_seed is not None else None, int(row0), bits.data_ptr() if bits is not None else None,
+                         int(bool(relu_only)), act.data_ptr() if act is not None else None, act.stride(0) if act is not None else 0)
+    st._keep = (mix, mix_index, bits, act, _graph_seed)
+    return st
+
+
 def _dropout_raw(x, p, seed, offset=0):
     lib = _lib.load()
     x = _c(x)

@@ -189,9 +189,8 @@ def _fused_gemm_launch(graph, z, bias, x0, c_act, c_mix, p, seed, image, g_rowsc
         g_addend = g_addend.contiguous()
     with torch.cuda.device(dev):
         _lib.check(fn(g._view(d, use_flags=True), _lib.ptr(acc), acc.stride(0) if acc is not None else 0,
-                      _lib.ptr(z), z.stride(0), d, _lib.ptr(graph.norm_in), _lib.ptr(bias), _lib.ptr(x0),
-                      x0.stride(0) if x0 is not None else 0, float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed),
-                      ops.seed_dev_ptr(), int(getattr(graph, 'row_offset', 0)), _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(act), d,
+                      _lib.ptr(z), z.stride(0), d, _lib.ptr(graph.norm_in), _lib.ptr(bias),
+                      ops.store_args(x0, None, c_act, c_mix, p, seed, getattr(graph, 'row_offset', 0), bits, relu_only, act),
                       _lib.ptr(out_next), d, int(not want_bits), _lib.ptr(image),
                       *((_lib.ptr(head[0]), int(head[1])) if head is not None
                         else (_lib.ptr(g_rowscale), _lib.ptr(g_addend), g_addend.stride(0) if g_addend is not None else 0)),
@@ -260,8 +259,7 @@ def _fused_launch(lib, graph, g, z, acc, bias, x0, c_act, c_mix, p, seed, want_a
         _lib.check(lib.cb_spmm_csr_fused_f32(g._view(d, use_flags=True, elem=z.element_size()), _lib.ptr(row_ids), _lib.ptr(z), int(bf16), z.stride(0), d,
                                              _lib.ptr(graph.norm_in if row_scale is None else row_scale), _lib.ptr(bias), _lib.ptr(acc),
                                              d if acc is not None else 0,
-                                             _lib.ptr(x0), x0.stride(0) if x0 is not None else 0, float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed),
-                                             ops.seed_dev_ptr(), int(getattr(graph, 'row_offset', 0)), _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(act), d,
+                                             ops.store_args(x0, None, c_act, c_mix, p, seed, getattr(graph, 'row_offset', 0), bits, relu_only, act),
                                              _lib.ptr(out_next), d, _lib.stream_ptr()), 'cb_spmm_csr_fused_f32')
     if prof is not None:
         ev1.record()
@@ -489,10 +487,9 @@ def _store_rows(y, idx, mix, c_act, c_mix, p, seed, row0, bits, relu_only, mix_i
     out = torch.empty_like(y)
     act = torch.empty_like(y) if want_act else None
     with torch.cuda.device(y.device):
-        _lib.check(lib.cb_trunk_store_rows_f32(_lib.ptr(y), _lib.ptr(idx), y.shape[0], y.shape[1], _lib.ptr(mix), mix.stride(0) if mix is not None else 0,
-                                               _lib.ptr(mix_index), float(c_act), float(c_mix), float(p), ctypes.c_uint64(seed), ops.seed_dev_ptr(), int(row0),
-                                               _lib.ptr(bits), int(bool(relu_only)), _lib.ptr(out), _lib.ptr(act), _lib.stream_ptr()),
-                   'cb_trunk_store_rows_f32')
+        _lib.check(lib.cb_trunk_store_rows_f32(_lib.ptr(y), _lib.ptr(idx), y.shape[0], y.shape[1],
+                                               ops.store_args(mix, mix_index, c_act, c_mix, p, seed, row0, bits, relu_only, act), _lib.ptr(out),
+                                               _lib.stream_ptr()), 'cb_trunk_store_rows_f32')
     return out, act
 
 

@@ -265,26 +265,43 @@ int cb_gemm_tn_f32(const float* A, int64_t lda, const float* G, int64_t ldg, con
 
 /* ------------------------------------------------------------------------------------
  * Fused residual trunk (type_trick with 'Initial', no bare norm: the default configs of
- * Pubmed / ogbn-arxiv / the synthetic power-law benchmark).  Folds GCN.py:127-133 of layer l
- * and GCN.py:110 of layer l+1 into the aggregation's store:
- *     act      = relu(row_scale[v] * sum_j h[col[j]] + bias)                       (GCN.py:238-253,128)
- *     out_next = dropout_{seed,p}( c_act * act + c_mix * mix_src[v] )              (res_tricks.py:23, GCN.py:110/133)
- * relu_bits [N][d/256][4] uint64 receives the backward mask of the store (word k, bit l = column 256*tile + 4*l + k): set where
- * the element passes gradient to the pre-activation, i.e. act > 0 AND the dropout keeps it (p = 0: the ReLU mask); bits_relu_only != 0: act > 0
- * alone (the 'Residual' connection, res_tricks.py:7-14: layer l+1's mix sends a second gradient through this ReLU under ANOTHER dropout mask —
- * the backward kernels regenerate the keep masks anyway); out_act (nullable) the activation itself (the mix source of the next 'Residual' layer).  d must be a multiple of 256; rows 16-byte aligned.  row0 = global index
- * of local row 0 (dropout mask of the unsharded tensor).  mix_src NULL: no mix; drop_p 0: no dropout.
+ * Pubmed / ogbn-arxiv / the synthetic power-law benchmark).
+ *
+ * The trunk's STORE — GCN.py:127-133 of layer l and GCN.py:110 of layer l+1, applied to a pre-activation y wherever a kernel has it in registers:
+ *     act  = relu(y)                                                               (GCN.py:128)
+ *     next = dropout_{seed,p}( c_act * act + c_mix * mix_src[mix row] )            (res_tricks.py:7-23, GCN.py:110/133)
+ * One argument of every entry that applies it: a HOST struct, passed by pointer and read during the call only (nothing retains it); the pointers
+ * inside are device pointers.  `next` (and what else the entry writes) is the entry's own argument.
+ * mix_src [., ld_mix] (NULL: no mix, next = dropout(act)): read at the node row; mix_index (NULL: none; int64, one entry per stored row; the entries
+ * over a SUBSET of the node rows only — cb_*_store_rows_f32): mix_src is a compact matrix, read at row mix_index[r].
+ * drop_p in [0, 1) (0: no dropout).  The keep-mask is cb_dropout_f32's draw for (seed, seed_dev, flat index (row0 + node row) * d + column): row0 =
+ * global index of node row 0 (the dropout mask of the unsharded tensor), seed_dev as in cb_dropout_f32.
+ * relu_bits [node rows][d/256][4] uint64 (NULL: not written) receives the backward mask of the store (word k, bit l = column 256*tile + 4*l + k): set
+ * where the element passes gradient to the pre-activation, i.e. act > 0 AND the dropout keeps it (p = 0: the ReLU mask); bits_relu_only != 0: act > 0
+ * alone (the 'Residual' connection, res_tricks.py:7-14: layer l+1's mix sends a second gradient through this ReLU under ANOTHER dropout mask — the
+ * backward kernels regenerate the keep masks anyway).
+ * out_act [., ld_act] (NULL: not written): the activation itself (the mix source of the next 'Residual' layer), at the row `next` is written at.
+ * d must be a multiple of 256; mix_src / out_act rows 16-byte aligned with a leading dimension that is a multiple of 4 and >= d; relu_bits 8-byte
+ * aligned.  An entry that has no kernel for an option returns CB_E_INVALID.  96 bytes.
+ * ---------------------------------------------------------------------------------- */
+typedef struct cb_trunk_store {
+  const float* mix_src; int64_t ld_mix; const int64_t* mix_index;
+  float c_act, c_mix, drop_p;
+  uint64_t seed; const uint64_t* seed_dev; int64_t row0;
+  uint64_t* relu_bits; int32_t bits_relu_only;
+  float* out_act; int64_t ld_act;
+} cb_trunk_store;
+
+/* The store folded into the aggregation's store:  y = row_scale[v] * sum_j h[col[j]] + bias  (GCN.py:238-253); out_next = the store's `next`.
  * h_bf16 / acc_init ([n_rows, ld_init], 16-byte aligned rows; NULL: none) as in cb_spmm_csr_f32: bf16-stored source rows, and the fused store as
  * the LAST pass of a node-sharded aggregation on top of the running sums.
  * row_ids (int32 [n_rows], ascending; NULL: none; fp32 rows, no acc_init): the CSR's rows are a SUBSET of the node rows — row r of rowptr / row_scale /
  * out_act / out_next is node row row_ids[r]; mix_src, relu_bits ([all node rows][d/256][4]) and the dropout mask are taken at the node row.  The
  * rows-only training forward (trunk.py): a GCNConv + store (GCN.py:205-256,127-133) evaluated only on the rows the layers above read.
- * ---------------------------------------------------------------------------------- */
+ * No mix_index: the mix is taken at the node row. */
 int cb_spmm_csr_fused_f32(const cb_csr_view* g, const int32_t* row_ids, const void* h, int32_t h_bf16, int64_t ld_h, int64_t d,
-                          const float* row_scale, const float* bias, const float* acc_init, int64_t ld_init, const float* mix_src,
-                          int64_t ld_mix, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
-                          uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act, float* out_next, int64_t ld_next,
-                          void* stream);
+                          const float* row_scale, const float* bias, const float* acc_init, int64_t ld_init, const cb_trunk_store* store,
+                          float* out_next, int64_t ld_next, void* stream);
 
 /* Backward of that epilogue in one pass over contiguous [rows, d]:
  *     gm = dropout_bwd(g);  gx0 = (accumulate ? gx0 : 0) + c_mix * gm  (gx0 NULL: skipped);
@@ -472,12 +489,12 @@ int cb_spmm_gemm_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t
                      const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream);
 /* skip_next != 0: a forward that no backward follows (evaluation / metrics passes, GCN.py:100-140 under no_grad): the stored activations have
  * no reader — the next layer's Z leaves this kernel — so the rows the persistent kernel finishes are NOT written to out_next (the hub rows
- * pass through it, its other contents are undefined afterwards; NULL is accepted when n_hubs == 0).  g_out as above. */
+ * pass through it, its other contents are undefined afterwards; NULL is accepted when n_hubs == 0).  g_out as above.  store: cb_trunk_store, as
+ * cb_spmm_csr_fused_f32 applies it on all node rows (no mix_index). */
 int cb_spmm_gemm_fused_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
-                           const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix,
-                           float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only,
-                           float* out_act, int64_t ld_act, float* out_next, int64_t ld_next, int32_t skip_next, const void* image,
-                           const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out, int64_t ld_gout, void* stream);
+                           const float* row_scale, const float* bias, const cb_trunk_store* store, float* out_next, int64_t ld_next,
+                           int32_t skip_next, const void* image, const float* g_rowscale, const float* g_addend, int64_t ld_add, float* g_out,
+                           int64_t ld_gout, void* stream);
 /* The output Linear as the tail of the LAST layer's aggregation (round 5): GCN.py:133-138 `layers_MLP[-1](F.dropout(x))` reads exactly the rows
  * the last trunk store has just made — logits = out_next @ W_out^T + b_out leave the aggregation kernel (C <= 64 classes; the four multiplying
  * wavefronts of a block take the four 32 x 32 blocks of a tile's 64 x 64 output), the separate head GEMM and its re-read of the [N, 256]
@@ -487,10 +504,9 @@ int cb_spmm_gemm_fused_f32(const cb_csr_view* g, const float* acc_init, int64_t 
 size_t cb_agg_gemm_head_image_bytes(int64_t K, int64_t C);
 int cb_agg_gemm_head_image_f32(const float* W, int64_t ld, int64_t K, int64_t C, int transpose, void* image, size_t image_bytes, void* stream);
 int cb_spmm_gemm_fused_head_f32(const cb_csr_view* g, const float* acc_init, int64_t ld_init, const float* h, int64_t ld_h, int64_t d,
-                                const float* row_scale, const float* bias, const float* mix_src, int64_t ld_mix, float c_act, float c_mix,
-                                float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only,
-                                float* out_act, int64_t ld_act, float* out_next, int64_t ld_next, int32_t skip_next, const void* head_image,
-                                const float* head_bias, int64_t C, float* logits, int64_t ld_logits, void* stream);
+                                const float* row_scale, const float* bias, const cb_trunk_store* store, float* out_next, int64_t ld_next,
+                                int32_t skip_next, const void* head_image, const float* head_bias, int64_t C, float* logits, int64_t ld_logits,
+                                void* stream);
 /* Fault injection for the failure path above (tests): one wavefront waits with a short spin bound for a hand-over that never comes;
  * cb_device_status() must then report CB_E_DEVICE. */
 int cb_agg_gemm_handover_selftest(void* stream);
@@ -567,12 +583,11 @@ int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const uint64_t* x
  *     act   = relu(g_rowscale[m] * (H @ B)[m] + bias)                      -> out_act [N, ld_act] if given
  *     g_out = dropout_{seed, node row}(c_act * act + c_mix * mix_src[mix_index[m] | row_ids[m]])
  *     relu_bits[row_ids[m]][0..3] = the mask words of act > 0 (AND kept by the dropout unless bits_relu_only), as cb_gemm_nn_store_rows_f32
- * row_ids (int64 [N]): the node row of each CSR row; the dropout mask is drawn at (row0 + row_ids[m]).  d must be 256, fp32 rows, 16-byte aligned;
+ * store: cb_trunk_store (relu_bits 16-byte aligned here: the words leave as 16-byte vectors).  row_ids (int64 [N]): the node row of each CSR row; the
+ * dropout mask is drawn at (row0 + row_ids[m]).  d must be 256, fp32 rows, 16-byte aligned;
  * image: cb_agg_gemm_image_f32 of W.  A tile hand-over that times out is recorded in the device error word (cb_device_status). */
 int cb_spmm_gemm_store_rows_f32(const cb_csr_view* g, const float* h, int64_t ld_h, int64_t d, const float* col_scale, float* out, int64_t ld_out,
-                                const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const float* mix_src,
-                                int64_t ld_mix, const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed,
-                                const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int32_t bits_relu_only, float* out_act, int64_t ld_act,
+                                const void* image, const float* g_rowscale, const float* bias, const int64_t* row_ids, const cb_trunk_store* store,
                                 float* g_out, int64_t ld_gout, void* stream);
 
 /* One label-propagation step, elementwise passes folded into the aggregation's store (Label_propagation_model/outcome_correlation.py:137-143
@@ -616,16 +631,12 @@ int cb_gather_rows_bf16_f32(const float* src, int64_t ld, const int64_t* idx, in
  * of the row-sparse backward that produces it is compact; fill = NaN: the logits (GCN.py:138) of a rows-only training forward, evaluated on the loss
  * rows of trainer_node_classification.py:390-391 only — a reader of any other row gets NaN, not a plausible number (trunk.py). */
 int cb_expand_rows_f32(const float* src, const int32_t* pos, int64_t n_rows, int64_t d, float fill, float* out, void* stream);
-/* The trunk's fused store — ReLU, mask words, residual mix, dropout (GCN.py:127-133, res_tricks.py:7-23) — on a SUBSET of the rows, applied to the
- * output of a dense transform instead of inside an aggregation: y / out are compact [n_rows, d] matrices of the rows row_index[0 .. n_rows) (ascending
- * global ids), relu_bits ([N][d/256][4], may be NULL) is the full array, the dropout mask is drawn at the global row; mix_src (may be NULL) is read at row
- * mix_index[r] (mix_index NULL: at row_index[r], i.e. mix_src is a full array too).
- *   act = relu(y[r]) (-> out_act[r] if given: the next 'Residual' layer's mix source);  out[r] = dropout((c_act * act + c_mix * mix_src[mix_index[r]]));
- *   bits as cb_spmm_csr_fused_f32 writes them.
+/* The trunk's store (cb_trunk_store) on a SUBSET of the rows, applied to the output of a dense transform instead of inside an aggregation: y / out
+ * (and out_act) are compact [n_rows, .] matrices of the rows row_index[0 .. n_rows) (ascending global ids), relu_bits is the full array, the dropout
+ * mask is drawn at the global row; mix_src is read at row mix_index[r] (mix_index NULL: at row_index[r], i.e. mix_src is a full array too).
+ *   act = relu(y[r]) (-> out_act[r]);  out[r] = dropout((c_act * act + c_mix * mix_src[mix_index[r]]));  bits as cb_spmm_csr_fused_f32 writes them.
  * The rows-only forward of the training step (trunk.py): the last GCNConv (GCN.py:205-256) evaluated on the loss rows of trainer…:390-391. */
-int cb_trunk_store_rows_f32(const float* y, const int64_t* row_index, int64_t n_rows, int64_t d, const float* mix_src, int64_t ld_mix,
-                            const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int bits_relu_only,
-                            float* out, float* out_act, void* stream);
+int cb_trunk_store_rows_f32(const float* y, const int64_t* row_index, int64_t n_rows, int64_t d, const cb_trunk_store* store, float* out, void* stream);
 /* The same store as the EPILOGUE of the dense transform in front of it:
  *   act = relu(rowscale * (A @ B) + addend + bias) (-> out_act if given);  C = dropout(c_act * act + c_mix * mix_src[mix_index[m] | row_index[m]])
  * with A, C, out_act, rowscale, addend compact over the rows row_index[0 .. M) — a GCNConv evaluated sum-first on a subset of the rows (GCN.py:213-256
@@ -634,9 +645,7 @@ int cb_trunk_store_rows_f32(const float* y, const int64_t* row_index, int64_t n_
 int cb_gemm_nn_store_rows_supported(const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, int64_t M, int64_t N, int64_t K);
 int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                               const float* rowscale, const float* addend, int64_t ld_add, const float* bias, const int64_t* row_index,
-                              const float* mix_src, int64_t ld_mix, const int64_t* mix_index, float c_act, float c_mix, float drop_p, uint64_t seed,
-                              const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, int bits_relu_only, float* out_act, int64_t ld_act, void* ws,
-                              size_t ws_bytes, void* stream);
+                              const cb_trunk_store* store, void* ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------
  * Student MLPs (MLP_model/__init__.py:1-156; cb_mlp.hip).  HBM-bound row kernels and losses; the Linear layers are cb_gemm_*.
