@@ -179,6 +179,12 @@ SIGNATURES = {
     'cb_linkp_mrr_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P]),
     'cb_linkp_bwd_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_linkp_loss_bwd_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    # CN / AA pair scores and rank counts (cb_heur.hip): views bound as plain pointers, as for the samplers above
+    'cb_heur_aa_weights_f64': (ctypes.c_int, [_P, _P, _P]),
+    'cb_heur_pair_scores_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
+    'cb_heur_pair_scores_width_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P]),
+    'cb_rank_counts_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_rank_counts_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

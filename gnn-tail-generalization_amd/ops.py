@@ -20,6 +20,9 @@ The teacher's edge-wise term (trainer_node_classification.py:417-438, 507-563; u
   LinkSampler       positive / negative edge samples on the device CSR (binary search in a row; counter-based draws)
   linkp_loss_eva    BCE-with-logits of the DistMult scores + MRR over index pairs; gradient as one [N, D] matrix, no atomics
   cal_MRR           the MRR of held scores
+Link-prediction baselines and tie-safe metrics (Link_prediction_baseline/heuristics.py:51-62, 107-129; Link_prediction_model/utils.py:43-59):
+  pair_scores       CN / AA of index pairs by sorted-row intersection on the by-src CSR (CN exact, AA in float64 rounded once)
+  rank_counts       per positive, the negatives above it and equal to it; hits_at_k / auc derive from the two integers
 """
 import ctypes
 import os
@@ -1423,3 +1426,170 @@ def cal_MRR(pos_score, neg_score):
         _lib.check(lib.cb_linkp_mrr_f32(_lib.ptr(ps), ps.numel(), _lib.ptr(ns) if ns.numel() else None, ns.numel(), _lib.ptr(mrr), _lib.stream_ptr()),
                    'cb_linkp_mrr_f32')
     return mrr.reshape(())
+
+
+# ---------------------------------------------------------------------------------------------
+# link-prediction baselines CN / AA and the counts behind Hits@K / AUC: Link_prediction_baseline/heuristics.py:51-62, 107-129;
+# Link_prediction_model/utils.py:43-59  (cb_heur.hip)
+# ---------------------------------------------------------------------------------------------
+HEUR_KINDS = ('CN', 'AA')
+CN_EXACT_BELOW = float(2 ** 24)      # a CN score is an integer held in fp32
+
+_heur_pending = {}      # device -> [int32 [1] count of out-of-range pairs, fp32 [1] largest CN score] since the last pair_scores_check()
+
+
+def _heur_pairs(t):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 2 or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError('pair_scores: pairs must be an int32 / int64 [2, P] tensor')
+    _lib.require_device(t)
+    return t
+
+
+def _out_view(graph):
+    v = _lib.CsrView(graph.rowptr_t.data_ptr(), graph.col_t.data_ptr(), 0, graph.N, graph.E, 1, 0, 0, None, None, None, 0)
+    v._keep = (graph.rowptr_t, graph.col_t)
+    return v
+
+
+def aa_weights(graph):
+    """float64 [N]: 1 / log(in-degree with multiplicity), 0 where the in-degree is <= 1 (heuristics.py:119-120).  Built once per graph and kept on it."""
+    w = getattr(graph, '_heur_aa_w', None)
+    if w is None:
+        lib = _lib.load()
+        w = torch.empty(graph.N, dtype=torch.float64, device=graph.device)
+        with torch.cuda.device(graph.device):
+            _lib.check(lib.cb_heur_aa_weights_f64(ctypes.byref(_linkp_view(graph)), _lib.ptr(w), _lib.stream_ptr()), 'cb_heur_aa_weights_f64')
+        graph._heur_aa_w = w
+    return w
+
+
+def pair_scores(graph, pairs, kind='CN', weight=None, return_status=False, group=None):
+    """fp32 [P]: the common-neighbour ('CN') or Adamic-Adar ('AA') score of every pair (pairs[0, i], pairs[1, i]) on the graph as given —
+    `CN` / `AA` of Link_prediction_baseline/heuristics.py:107-129 with A[s, k] the multiplicity of the edge s -> k: CN = sum_k A[s, k] A[d, k]
+    exactly (an integer in fp32; pair_scores_check() raises if one reached 2^24), AA = sum_k A[s, k] A[d, k] / log(c_k) summed in float64 and rounded
+    once, c_k the in-degree of k with multiplicity, terms with c_k <= 1 dropped.  No special case for s == d, self loops or pairs that are edges.
+    `weight` (float64 [N], kind 'AA' only) replaces 1 / log(c): resource allocation is weight = 1 / c.  pairs: int32 or int64 [2, P] on the graph's
+    device; P = 0 returns an empty tensor without a launch.  A pair with an endpoint outside [0, N) is never used as an index: its score is NaN and
+    it counts in the status word, which pair_scores_check() reads where the caller reads the scores anyway (return_status: also hand back the int32
+    [1] status of this call).  group: 16 or 64 lanes per pair (default: the library's choice); the results do not hinge on it."""
+    from .graph import CSRGraph
+    if kind == 'PPR':
+        raise NotImplementedError("pair_scores: 'PPR' is not built (the reference's PPR needs the fast_pagerank package, which is absent)")
+    if kind not in HEUR_KINDS:
+        raise ValueError(f"pair_scores: kind must be 'CN' or 'AA', got {kind!r}")
+    if type(graph) is not CSRGraph or graph.n_cols != graph.N or graph.row_offset != 0 or getattr(graph, 'rowptr_t', None) is None:
+        raise ValueError('pair_scores needs a whole square graph.CSRGraph (segmented and node-sharded graphs are out of scope)')
+    if weight is not None and kind == 'CN':
+        raise ValueError("pair_scores: `weight` belongs to kind='AA' (CN counts common neighbours unweighted)")
+    if group not in (None, 16, 64):
+        raise ValueError('pair_scores: group is 16 or 64')
+    pairs = _heur_pairs(pairs)
+    if pairs.device != graph.device:
+        raise ValueError('pair_scores: pairs live on another device than the graph')
+    if weight is not None:
+        _lib.require_device(weight)
+        if weight.dtype != torch.float64 or weight.dim() != 1 or weight.numel() != graph.N or weight.device != graph.device:
+            raise ValueError(f'pair_scores: weight must be a float64 vector of {graph.N} nodes on the device of the graph')
+        weight = _c(weight)
+    P = int(pairs.shape[1])
+    dev = graph.device
+    score = torch.empty(P, dtype=torch.float32, device=dev)
+    if P == 0:
+        return (score, torch.zeros(1, dtype=torch.int32, device=dev)) if return_status else score
+    lib = _lib.load()
+    w = None if kind == 'CN' else (aa_weights(graph) if weight is None else weight)
+    p32 = _c(pairs.to(torch.int32))
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        if group is None:
+            rc = lib.cb_heur_pair_scores_f32(ctypes.byref(_out_view(graph)), _lib.ptr(w), _lib.ptr(p32), P, _lib.ptr(score), _lib.ptr(status), _lib.stream_ptr())
+        else:
+            rc = lib.cb_heur_pair_scores_width_f32(ctypes.byref(_out_view(graph)), _lib.ptr(w), _lib.ptr(p32), P, group, _lib.ptr(score), _lib.ptr(status),
+                                                   _lib.stream_ptr())
+        _lib.check(rc, 'cb_heur_pair_scores_f32')
+    pend = _heur_pending.get(dev)
+    if pend is None:
+        pend = _heur_pending[dev] = [torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)]
+    pend[0] += status
+    if kind == 'CN':
+        pend[1] = torch.fmax(pend[1], torch.nan_to_num(score, nan=0.0).max().reshape(1))
+    return (score, status) if return_status else score
+
+
+def pair_scores_check():
+    """Reads the status words of the pair_scores() calls since the last check (a host synchronisation: call it where the scores are read anyway),
+    clears them, and raises RuntimeError if a pair had an endpoint outside the graph (its score is NaN) or OverflowError if a CN score reached 2^24
+    (fp32 no longer holds every integer there)."""
+    bad, top = 0, 0.0
+    for pend in _heur_pending.values():
+        bad += int(pend[0].item())
+        top = max(top, float(pend[1].item()))
+        pend[0].zero_()
+        pend[1].zero_()
+    if bad:
+        raise RuntimeError(f'pair_scores: {bad} pair(s) with an endpoint outside [0, N) (their scores are NaN)')
+    if top >= CN_EXACT_BELOW:
+        raise OverflowError(f'pair_scores: a CN score reached {top:.0f} >= 2^24, beyond which fp32 does not hold every integer')
+
+
+def rank_counts(pos, neg, return_status=False):
+    """(gt, eq) int32 [P]: gt[i] = #{j : neg[j] > pos[i]}, eq[i] = #{j : neg[j] == pos[i]} over all negatives; -0.0 equals +0.0, +-inf compare as
+    numbers.  A NaN on either side never compares: the int32 [1] status (return_status) counts them and every gt / eq is then -1; hits_at_k() and
+    auc() raise on it.  Nn = 0 gives zeros."""
+    _lib.require_device(pos, neg)
+    if not torch.is_tensor(pos) or not torch.is_tensor(neg) or pos.dtype != torch.float32 or neg.dtype != torch.float32 or pos.device != neg.device:
+        raise ValueError('rank_counts expects float32 scores on one device')
+    lib = _lib.load()
+    ps, ns = _c(pos.detach().reshape(-1)), _c(neg.detach().reshape(-1))
+    P, Nn, dev = ps.numel(), ns.numel(), ps.device
+    gt = torch.empty(P, dtype=torch.int32, device=dev)
+    eq = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = lib.cb_rank_counts_workspace_bytes(P, Nn)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_rank_counts_f32(_lib.ptr(ps) if P else None, P, _lib.ptr(ns) if Nn else None, Nn, _lib.ptr(gt) if P else None,
+                                          _lib.ptr(eq) if P else None, _lib.ptr(status), _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_rank_counts_f32')
+    return (gt, eq, status) if return_status else (gt, eq)
+
+
+def hits_from_counts(gt, eq, ks):
+    """{'Hits@K': mean(gt + eq < K)} in float64 from the integer counts: the OGB rule `pos > K-th largest negative` stated on counts (a tie with the
+    K-th largest negative is no hit), 1.0 when there are fewer than K negatives, as OGB gives."""
+    if gt.numel() == 0:
+        raise ValueError('Hits@K is a mean over the positives: at least one is required')
+    worse = gt.to(torch.int64) + eq.to(torch.int64)
+    return {f'Hits@{int(k)}': float((worse < int(k)).to(torch.float64).mean().item()) for k in ks}
+
+
+def auc_from_counts(gt, eq, n_neg):
+    """sum_i (Nn - gt_i - eq_i + eq_i / 2) / (P Nn): the Mann-Whitney form of the AUC, equal to roc_auc_score under ties.  The numerator is summed as
+    the integer sum_i 2 (Nn - gt_i - eq_i) + eq_i and divided once."""
+    P, Nn = int(gt.numel()), int(n_neg)
+    if P == 0 or Nn == 0:
+        raise ValueError('the AUC needs at least one positive and one negative')
+    g, e = gt.to(torch.int64), eq.to(torch.int64)
+    return int((2 * (Nn - g - e) + e).sum().item()) / (2 * P * Nn)
+
+
+def _checked_counts(pos, neg, who):
+    gt, eq, status = rank_counts(pos, neg, return_status=True)
+    n = int(status.item())
+    if n:
+        raise ValueError(f'{who}: {n} NaN score(s): a NaN has no rank')
+    return gt, eq
+
+
+def hits_at_k(pos, neg, ks=(20, 50, 100)):
+    """{'Hits@K': share of the positives with fewer than K negatives at or above them} (Link_prediction_model/utils.py:43-52 with the OGB evaluator's
+    rule); well defined under ties, unlike cal_MRR, which counts ties for the positive."""
+    gt, eq = _checked_counts(pos, neg, 'hits_at_k')
+    return hits_from_counts(gt, eq, ks)
+
+
+def auc(pos, neg):
+    """The AUC of positives against negatives (Link_prediction_model/utils.py:54-59 `roc_auc_score`), ties counting one half."""
+    if pos.numel() == 0 or neg.numel() == 0:
+        raise ValueError('the AUC needs at least one positive and one negative')
+    gt, eq = _checked_counts(pos, neg, 'auc')
+    return auc_from_counts(gt, eq, neg.numel())

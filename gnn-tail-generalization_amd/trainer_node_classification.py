@@ -670,6 +670,25 @@ class trainer:
         self.link_sampler().check()
         return float(mrr.item())
 
+    def evaluate_linkp_heuristic(self, kind, mode):
+        """{'Hits@20', 'Hits@50', 'Hits@100', 'AUC'} of the baseline `kind` ('CN' or 'AA'; Link_prediction_baseline/heuristics.py:107-129) on a
+        fresh `mode` sample: the numbers a learned scorer's are held against.  Every positive is ranked against all sampled negatives, ties as
+        Link_prediction_model/utils.py:43-59 counts them.  The graph is scored as given (the sampled positives are edges of it)."""
+        if mode not in ('train', 'test'):
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
+        if kind not in ops.HEUR_KINDS:
+            raise NotImplementedError(f"kind must be 'CN' or 'AA', got {kind!r} ('PPR' needs the fast_pagerank package)")
+        if getattr(self, 'teacherGNN', None) is None:      # the cached device graph hangs on the model
+            self.setup_teacherGNN()
+        pos, neg = self.gen_pn_edge_index(mode)
+        g = self.graph()
+        ps, ns = ops.pair_scores(g, pos, kind), ops.pair_scores(g, neg, kind)
+        self.link_sampler().check()
+        ops.pair_scores_check()
+        out = ops.hits_at_k(ps, ns, (20, 50, 100))
+        out['AUC'] = ops.auc(ps, ns)
+        return out
+
     def train_teacherGNN_linkp(self):
         """train_teacherGNN with the edge-wise term in the objective: the same record layout ([loss_train (log), acc_train, acc_test, linkp_train,
         linkp_test (+ head / tail / iso)], one column per epoch), rows 3 and 4 now real.  Eager steps only (no --hip_graph, no --resume).

@@ -834,6 +834,44 @@ size_t cb_linkp_bwd_workspace_bytes(int64_t P, int64_t Nn);
 int cb_linkp_loss_bwd_f32(const float* emb, int64_t ld, int64_t N, int64_t D, const int32_t* pos, int64_t P, const int32_t* neg, int64_t Nn,
                           const float* scores, const float* g, float* demb, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * The link-prediction baselines CN / AA (Link_prediction_baseline/heuristics.py:107-129 `CN`, `AA`; Link_prediction_model/layer.py:6-17
+ * `Heuristics.get_score`; base_options.py:112 `--encoder CN | AA | PPR`) and the counts behind Hits@K / AUC
+ * (Link_prediction_model/utils.py:43-59; Link_prediction_baseline/heuristics.py:51-62); cb_heur.hip.  The reference evaluates
+ * `A[src].multiply(A_[dst])` with scipy on the host in batches of 100 000 pairs; on the CSR it is a sorted-row intersection.
+ * A = csr_matrix((1, (ei[0], ei[1]))): A[s, k] = the multiplicity of the edge s -> k, row s = the OUT-row of s = row s of the by-src CSR
+ * (rowptr_t / col_t of cb_csr_from_coo_i64; ascending columns, duplicates stored).  CN(s, d) = sum_k A[s, k] A[d, k];
+ * AA(s, d) = sum_k A[s, k] A[d, k] w[k].  No special case for s == d, self loops, or (s, d) being an edge.
+ * The views are read for rowptr / col / n_rows / n_edges only (square, plain column ids: col_flags == 0).
+ * The float results involve no atomic; no host synchronisation; two calls with the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+#define CB_HEUR_GROUP 16 /* lanes that share one pair in cb_heur_pair_scores_f32 (four pairs per wavefront) */
+
+/* w [N] float64: 1 / log(in-degree), 0 where in-degree <= 1 (heuristics.py:119-120: `1 / np.log(A.sum(axis=0))`, the inf of a column sum
+ * of 1 zeroed).  g_in: the by-dst view (rowptr read only): in-degree with multiplicity = rowptr[k + 1] - rowptr[k]. */
+int cb_heur_aa_weights_f64(const cb_csr_view* g_in, double* w, void* stream);
+
+/* score [P] fp32 (heuristics.py:113, 126).  g_out: the by-src view.  pairs int32 [2, P]: row 0 = s, row 1 = d.
+ * w == NULL: CN, accumulated in int64, converted once (exact below 2^24).
+ * w != NULL ([N] float64): the sum of the multiplicity products times w[k] in float64, rounded to fp32 once.
+ * status [1] (zeroed by the call): the number of pairs with an endpoint outside [0, N).  Such a pair is never used as an index; its score
+ * is NaN (one integer atomic per such pair, order-independent).  P == 0 launches nothing. */
+int cb_heur_pair_scores_f32(const cb_csr_view* g_out, const double* w, const int32_t* pairs, int64_t P, float* score, int32_t* status,
+                            void* stream);
+/* The same with the group width chosen by the caller: group = 16 or 64 lanes per pair.  CN does not depend on it; the weighted sum is taken
+ * in another order (float64, rounded once).  For measuring the choice of CB_HEUR_GROUP and for testing that results do not hinge on it. */
+int cb_heur_pair_scores_width_f32(const cb_csr_view* g_out, const double* w, const int32_t* pairs, int64_t P, int32_t group, float* score,
+                                  int32_t* status, void* stream);
+
+/* gt [P], eq [P] int32: gt[i] = #{j : neg[j] > pos[i]}, eq[i] = #{j : neg[j] == pos[i]} over ALL Nn negatives (Nn < 2^31, P < 2^31):
+ * Hits@K = mean(gt + eq < K) and AUC = sum_i (Nn - gt_i - eq_i + eq_i / 2) / (P Nn) derive from them and are well defined under ties
+ * (Link_prediction_model/utils.py:43-59).  The negatives are sorted once (order-preserving float -> uint32 key: -0.0 == +0.0, -inf first,
+ * +inf last; cb_sort.hip on 32 bits), then two binary searches per positive.  status [1] (zeroed by the call): the number of NaNs in pos
+ * and neg; if it is not 0, every gt / eq is -1 (a NaN never compares as a number).  Nn == 0 gives zeros and needs no workspace. */
+size_t cb_rank_counts_workspace_bytes(int64_t P, int64_t Nn);
+int cb_rank_counts_f32(const float* pos, int64_t P, const float* neg, int64_t Nn, int32_t* gt, int32_t* eq, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
