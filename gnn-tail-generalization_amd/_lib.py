@@ -185,6 +185,16 @@ SIGNATURES = {
     'cb_heur_pair_scores_width_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P]),
     'cb_rank_counts_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_rank_counts_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    # the link predictors and ranking losses on index pairs (cb_linkpred.hip)
+    'cb_pair_gemm_nn_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64]),
+    'cb_pair_gemm_nn_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, ctypes.c_int, ctypes.c_float,
+                                           ctypes.c_uint64, _P, _I64, _P, _P]),
+    'cb_pair_dot_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _P, _P]),
+    'cb_pair_scatter_workspace_bytes': (_SZ, [_I64]),
+    'cb_pair_scatter_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    'cb_rank_loss_workspace_bytes': (_SZ, []),
+    'cb_rank_loss_fwd_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'cb_rank_loss_bwd_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

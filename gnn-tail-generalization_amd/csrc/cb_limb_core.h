@@ -120,6 +120,63 @@ struct RowOperand {
   }
 };
 
+// ---- "row" operand that is the Hadamard product of two GATHERED rows: value[r][k] = h[u_r][k] * h[v_r][k] (the link predictors' x_i * x_j,
+// Link_prediction_model/layer.py:100) — the gathered matrices and their product are never written.  Same LDS image and fragment reads as
+// RowOperand<R>.  `base` of load() is &h[0][k0] (uniform); the lane adds node * ld in 64 bits (N = 10^8 rows of 256 floats overflow 32).  A row whose
+// pair has an endpoint outside [0, N) addresses node 0 and stages zeros (the kernel overwrites its row of C).  Each product is rounded to
+// fp32 once, as a value of its own, before the split (mul_rounded): the limbs are those of the materialised h[u] * h[v].  The second row's quads live
+// in the operand, so the K loop must run at register prefetch depth 1.
+template <int R>
+struct PairRowOperand {
+  static constexpr int PLANE = R * 32, BYTES = 3 * PLANE, NV = R / 64;
+  static_assert(NV >= 1, "tile rows");
+  int32_t nu[NV], nv[NV];      // the two nodes of tile row t/4 + 64 j; nu < 0: the row stages zeros (outside the matrix, or an unusable pair)
+  uint32_t woff;
+  static constexpr bool HAS_SC = false;
+  float sc[1];
+  float4 fv[NV];               // the second row's quads of the loaded step
+  // usable pair of tile row `row` (pairs = &pairs[0][tile row 0], S = its row length, rows_left = S - tile row 0, N = number of nodes);
+  // in: the row lies inside the matrix
+  static __device__ __forceinline__ bool pair_of(const int32_t* __restrict__ pairs, int64_t S, int64_t rows_left, int64_t N, int row, int& u, int& v, bool& in) {
+    in = row < rows_left;
+    u = in ? pairs[row] : 0;
+    v = in ? pairs[S + row] : 0;
+    return in && u >= 0 && u < N && v >= 0 && v < N;
+  }
+  __device__ __forceinline__ void init(const int32_t* __restrict__ pairs, int64_t S, int64_t rows_left, int64_t N, int t) {
+    const int row = t >> 2, kq = t & 3;
+    woff = row * 32 + (((kq >> 1) ^ ((row >> 3) & 1)) << 4) + ((kq & 1) << 3);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      int u, v;
+      bool in;
+      const bool ok = pair_of(pairs, S, rows_left, N, row + 64 * j, u, v, in);
+      nu[j] = ok ? u : -1;
+      nv[j] = ok ? v : 0;
+    }
+  }
+  template <int J>
+  __device__ __forceinline__ void load(float4 (&f)[NV], const float* __restrict__ base, int64_t ld, int64_t k_left, const float*, int t) {
+    const int kq4 = (t & 3) * 4 < k_left ? (t & 3) * 4 : 0;
+    f[J] = *reinterpret_cast<const float4*>(base + ((int64_t)(nu[J] < 0 ? 0 : nu[J]) * ld + kq4));
+    fv[J] = *reinterpret_cast<const float4*>(base + ((int64_t)nv[J] * ld + kq4));
+  }
+  template <int J>
+  __device__ __forceinline__ void stage(const float4 (&f)[NV], char* __restrict__ S, int64_t k_left, int t) const {
+    const bool live = nu[J] >= 0 && (t & 3) * 4 < k_left;
+    const float a[4] = {f[J].x, f[J].y, f[J].z, f[J].w}, b[4] = {fv[J].x, fv[J].y, fv[J].z, fv[J].w};
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = live ? mul_rounded(a[i], b[i]) : 0.f;
+    uint2 pl[3];
+    split4(v, pl);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(S + p * PLANE + woff + J * (64 * 32)) = pl[p];
+  }
+  static __device__ __forceinline__ uint32_t frag_addr(int r0, int lane) { return RowOperand<R>::frag_addr(r0, lane); }
+  static __device__ __forceinline__ bf16x8 frag(const char* __restrict__ S, uint32_t addr, int plane) { return RowOperand<R>::frag(S, addr, plane); }
+};
+
 // ---- "col" operand: global [k][cols] (cols contiguous) -> LDS planes [16 k][C cols] ------------------
 template <int C, bool SCALED, bool DROP = false, int NT = 256>      // NT: threads of the block that stage the operand
 struct ColOperand {

@@ -23,6 +23,10 @@ The teacher's edge-wise term (trainer_node_classification.py:417-438, 507-563; u
 Link-prediction baselines and tie-safe metrics (Link_prediction_baseline/heuristics.py:51-62, 107-129; Link_prediction_model/utils.py:43-59):
   pair_scores       CN / AA of index pairs by sorted-row intersection on the by-src CSR (CN exact, AA in float64 rounded once)
   rank_counts       per positive, the negatives above it and equal to it; hits_at_k / auc derive from the two integers
+Link predictors and ranking losses (Link_prediction_model/layer.py:85-106, 182-191; loss.py:4-30; model.py:152-158):
+  pair_dot          <h[u], h[v]> per index pair (DotPredictor); gradient through the sorted inverted index, no atomics
+  pair_linear       act((h[u] * h[v]) @ W^T + b) (+ dropout): MLPPredictor's first layer, its A operand formed while the GEMM stages it
+  rank_loss         auc / adaptive_auc / log_rank / ce / info_nce over pos [P] and neg [P, k], every term in float64, rounded once
 """
 import ctypes
 import os
@@ -1593,3 +1597,256 @@ def auc(pos, neg):
         raise ValueError('the AUC needs at least one positive and one negative')
     gt, eq = _checked_counts(pos, neg, 'auc')
     return auc_from_counts(gt, eq, neg.numel())
+
+
+# ---------------------------------------------------------------------------------------------
+# link predictors and ranking losses: Link_prediction_model/layer.py:85-106, 182-191; loss.py:4-30; model.py:152-158  (cb_linkpred.hip)
+# ---------------------------------------------------------------------------------------------
+RANK_KINDS = {'auc_loss': 0, 'adaptive_auc_loss': 1, 'log_rank_loss': 2, 'ce_loss': 3, 'info_nce_loss': 4}
+
+_pair_pending = {}      # device -> int32 [1] count of unusable pairs since the last pair_check()
+
+
+def _pair_args(who, h, pairs):
+    _lib.require_device(h, pairs)
+    if not torch.is_tensor(h) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[0] < 1 or h.shape[1] < 1:
+        raise ValueError(f'{who} expects a float32 [N, D] embedding matrix')
+    if not torch.is_tensor(pairs) or pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{who}: pairs must be an int32 / int64 [2, S] tensor')
+    if pairs.device != h.device:
+        raise ValueError(f'{who}: pairs live on another device than the embeddings')
+    return _c(pairs.to(torch.int32))
+
+
+def _pair_rows(h):
+    """h with contiguous rows (a column slice of a wider matrix stays where it is: the kernels take its leading dimension)."""
+    return h if h.stride(1) == 1 and h.stride(0) >= h.shape[1] else h.contiguous()
+
+
+def _pair_note(status):
+    pend = _pair_pending.get(status.device)
+    if pend is None:
+        pend = _pair_pending[status.device] = torch.zeros(1, dtype=torch.int32, device=status.device)
+    pend += status
+
+
+def pair_check():
+    """Reads the status words of the pair_dot() / pair_linear() calls since the last check (a host synchronisation: call it where the loss is read
+    anyway), clears them, and raises RuntimeError if a pair had an endpoint outside [0, N) — the -1 of a failed LinkSampler slot.  Its score, and
+    any loss taken over it, is NaN.  Also reachable as pair_dot.check, pair_linear.check and rank_loss.check."""
+    bad = 0
+    for pend in _pair_pending.values():
+        bad += int(pend.item())
+        pend.zero_()
+    if bad:
+        raise RuntimeError(f'link predictor: {bad} pair(s) with an endpoint outside [0, N) (their scores are NaN)')
+
+
+def _pair_scatter_raw(h, pairs, coef, out=None):
+    """dH [N, D] = sum_e (coef_e * h[v_e] into row u_e, coef_e * h[u_e] into row v_e); coef [S] (a scalar per pair) or [S, D] (a row per pair).
+    h: rows contiguous (any leading dimension); pairs: int32 [2, S], contiguous; out: optional [N, D] destination with contiguous rows."""
+    lib = _lib.load()
+    N, D = h.shape
+    S = pairs.shape[1]
+    coef = _pair_rows(coef) if coef.dim() == 2 else _c(coef)
+    ldcoef = 0 if coef.dim() == 1 else (coef.stride(0) if S > 1 else D)
+    dh = torch.empty((N, D), dtype=torch.float32, device=h.device) if out is None else out
+    if tuple(dh.shape) != (N, D) or dh.dtype != torch.float32 or dh.stride(1) != 1 or dh.stride(0) < D or dh.device != h.device:
+        raise ValueError(f'pair scatter: out must be a float32 [{N}, {D}] matrix with contiguous rows on the device of h')
+    wsb = lib.cb_pair_scatter_workspace_bytes(S)
+    ws = _ws(wsb, h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(lib.cb_pair_scatter_f32(_lib.ptr(h), h.stride(0), N, D, _lib.ptr(pairs), S, _lib.ptr(coef), ldcoef, _lib.ptr(dh), dh.stride(0) if N > 1 else D, _lib.ptr(ws), wsb,
+                                           _lib.stream_ptr()), 'cb_pair_scatter_f32')
+    return dh
+
+
+class _PairDotFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, pairs):
+        lib = _lib.load()
+        e = _pair_rows(h)
+        N, D = e.shape
+        S = pairs.shape[1]
+        scores = torch.empty(S, dtype=torch.float32, device=e.device)
+        status = torch.empty(1, dtype=torch.int32, device=e.device)
+        with torch.cuda.device(e.device):
+            _lib.check(lib.cb_pair_dot_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(pairs), S, _lib.ptr(scores), _lib.ptr(status), _lib.stream_ptr()),
+                       'cb_pair_dot_f32')
+        ctx.save_for_backward(e, pairs)
+        ctx.mark_non_differentiable(status)
+        return scores, status
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        e, pairs = ctx.saved_tensors
+        return _pair_scatter_raw(e, pairs, g.detach().to(torch.float32)), None
+
+
+def pair_dot(h, pairs, return_status=False):
+    """fp32 [S]: <h[pairs[0, e]], h[pairs[1, e]]> — `DotPredictor.forward(h[u], h[v])` (layer.py:189-191) without the two gathered [S, D] matrices.
+    h: the full [N, D] float32 embedding matrix (rows may be strided); pairs: int32 / int64 [2, S] on its device.  The gradient arrives as one
+    [N, D] matrix built through a sorted inverted index: no atomics, bit-identical from call to call, untouched rows exactly zero.  A pair with an
+    endpoint outside [0, N) is never used as an index: its score is NaN, it contributes no gradient, and pair_dot.check() raises where the
+    caller reads the loss (return_status: also hand back the int32 [1] count of this call)."""
+    pairs = _pair_args('pair_dot', h, pairs)
+    scores, status = _PairDotFn.apply(h, pairs)
+    _pair_note(status)
+    return (scores, status) if return_status else scores
+
+
+def pair_linear_supported(h, weight):
+    """The fused first layer exists for this shape (cb_pair_gemm_nn_supported): in and out widths multiples of 4, 16-byte aligned rows."""
+    lib = _lib.load()
+    e, b = _pair_rows(h), weight.t().contiguous()
+    K, Nout = b.shape
+    return e.shape[1] == K and bool(lib.cb_pair_gemm_nn_supported(_lib.ptr(e), e.stride(0), _lib.ptr(b), Nout, Nout, K))
+
+
+def _pair_product(h, pairs):
+    """h[u] * h[v] materialised; the row of an unusable pair is zero (its endpoints are never used as indices: they are replaced by node 0 first)."""
+    N = h.shape[0]
+    ok = ((pairs >= 0) & (pairs < N)).all(0)
+    u, v = torch.where(ok, pairs[0], 0).long(), torch.where(ok, pairs[1], 0).long()
+    return (h[u] * h[v]) * ok[:, None].to(h.dtype)
+
+
+def _pair_linear_raw(e, pairs, b, bias, relu, p, seed, row0):
+    """(y, dropout_p(y) | None, status) of cb_pair_gemm_nn_f32: y = act((e[u] * e[v]) @ b + bias), b [K, Nout] contiguous."""
+    lib = _lib.load()
+    N, K = e.shape
+    S, Nout = pairs.shape[1], b.shape[1]
+    dev = e.device
+    y = torch.empty((S, Nout), dtype=torch.float32, device=dev)
+    yd = torch.empty((S, Nout), dtype=torch.float32, device=dev) if p > 0.0 else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_pair_gemm_nn_f32(_lib.ptr(e), e.stride(0), N, _lib.ptr(pairs), S, _lib.ptr(b), Nout, _lib.ptr(y), Nout, _lib.ptr(yd), Nout,
+                                           Nout, K, _lib.ptr(bias), int(bool(relu)), float(p), ctypes.c_uint64(seed), seed_dev_ptr(), int(row0),
+                                           _lib.ptr(status), _lib.stream_ptr()), 'cb_pair_gemm_nn_f32')
+    return y, yd, status
+
+
+class _PairLinearFn(torch.autograd.Function):
+    """Y = act((h[u] * h[v]) @ W^T + b), nn.Linear's weight layout [out, in]; returns dropout_p(Y) when p > 0."""
+
+    @staticmethod
+    def forward(ctx, h, pairs, weight, bias, relu, p, seed, row0, fused):
+        from . import gemm
+        lib = _lib.load()
+        e = _pair_rows(h)
+        N, K = e.shape
+        S, Nout = pairs.shape[1], weight.shape[0]
+        b = weight.t().contiguous()
+        can = S > 0 and bool(lib.cb_pair_gemm_nn_supported(_lib.ptr(e), e.stride(0), _lib.ptr(b), Nout, Nout, K))
+        if fused and not can:
+            raise _lib.HipExtensionError('pair_linear: the fused form does not exist for this shape (pair_linear_supported)')
+        if can and fused is not False:
+            y, yd, status = _pair_linear_raw(e, pairs, b, bias, relu, p, seed, row0)
+        else:      # the shape is outside the fused form: the same operators one after the other
+            x = _pair_product(e, pairs)
+            y = gemm.mm_nn(x, b, bias=bias, relu=relu)
+            ok = (pairs >= 0).all(0) & (pairs < N).all(0)
+            y = torch.where(ok[:, None], y, torch.full_like(y, float('nan')))
+            status = (~ok).sum().to(torch.int32).reshape(1)
+            yd = _dropout_raw(y, p, seed, row0 * Nout) if p > 0.0 else None
+        ctx.relu, ctx.p, ctx.seed, ctx.row0, ctx.has_bias = bool(relu), float(p), int(seed), int(row0), bias is not None
+        ctx.save_for_backward(e, pairs, weight, y if relu else None)
+        ctx.mark_non_differentiable(status)
+        return (yd if p > 0.0 else y), status
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        from . import gemm
+        e, pairs, weight, y = ctx.saved_tensors
+        Nout = weight.shape[0]
+        g = _c(g)
+        if ctx.p > 0.0:
+            g = _dropout_raw(g, ctx.p, ctx.seed, ctx.row0 * Nout)
+        need_b = ctx.has_bias and ctx.needs_input_grad[3]
+        if ctx.relu or need_b:
+            gm, db = act_bwd(g, y if ctx.relu else None, None, want_out=ctx.relu, want_colsum=need_b)
+            if gm is None:
+                gm = g
+        else:
+            gm, db = g, None
+        dh = _pair_scatter_raw(e, pairs, gemm.mm_nn(gm, weight)) if ctx.needs_input_grad[0] else None      # dX = gm @ W, scattered with row coefficients
+        dw = gemm.mm_tn(gm, _pair_product(e, pairs)) if ctx.needs_input_grad[2] else None                  # the product matrix exists here only
+        return dh, None, dw, db, None, None, None, None, None
+
+
+def pair_linear(h, pairs, weight, bias=None, relu=False, p=0.0, seed=None, row0=0, return_status=False, fused=None):
+    """act((h[u] * h[v]) @ weight^T + bias), then F.dropout(p) when p > 0: the first Linear of `MLPPredictor.forward(h[u], h[v])` (layer.py:99-104)
+    on index pairs.  The product is formed while the three-limb GEMM stages its A operand (cb_pair_gemm_nn_f32): neither gathered matrix nor the
+    product is written in the forward, and the output has the bits of gemm.mm_nn(h[u] * h[v], weight.t(), bias, relu) — with p > 0 those of
+    gemm.mm_nn_drop2 for (seed, row0).  Backward: act_bwd, dX = gm @ W on mm_nn, dH through the sorted inverted index with row coefficients (no
+    atomics), dW = gm^T @ (h[u] * h[v]) on mm_tn over a product matrix materialised there.  Where the fused form does not exist for the shape
+    (pair_linear_supported) the same operators run one after the other; fused=False asks for that.  Unusable pairs: as pair_dot."""
+    pairs = _pair_args('pair_linear', h, pairs)
+    _lib.require_device(weight, bias)
+    if weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[1] != h.shape[1]:
+        raise ValueError(f'pair_linear: weight must be a float32 [out, {h.shape[1]}] matrix')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('pair_linear: 0 <= p < 1 required')
+    if p > 0.0 and seed is None:
+        seed = next_seed()
+    y, status = _PairLinearFn.apply(h, pairs, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
+    _pair_note(status)
+    return (y, status) if return_status else y
+
+
+class _RankLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kind, pos, neg, k, weight):
+        lib = _lib.load()
+        P, dev = pos.numel(), pos.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        wsb = lib.cb_rank_loss_workspace_bytes()
+        ws = _ws(wsb, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_rank_loss_fwd_f32(kind, _lib.ptr(pos), P, _lib.ptr(neg), k, _lib.ptr(weight), _lib.ptr(loss), _lib.ptr(ws), wsb,
+                                                _lib.stream_ptr()), 'cb_rank_loss_fwd_f32')
+        ctx.kind, ctx.k = kind, k
+        ctx.save_for_backward(pos, neg, weight)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        pos, neg, weight = ctx.saved_tensors
+        P, dev = pos.numel(), pos.device
+        g = g.detach().reshape(1).to(torch.float32).contiguous()
+        dpos, dneg = torch.empty_like(pos), torch.empty_like(neg)
+        with torch.cuda.device(dev):
+            _lib.check(lib.cb_rank_loss_bwd_f32(ctx.kind, _lib.ptr(pos), P, _lib.ptr(neg), ctx.k, _lib.ptr(weight), _lib.ptr(g), _lib.ptr(dpos),
+                                                _lib.ptr(dneg), _lib.stream_ptr()), 'cb_rank_loss_bwd_f32')
+        return None, dpos, dneg, None, None
+
+
+def rank_loss(kind, pos, neg, num_neg=None, weight=None):
+    """The pairwise losses of Link_prediction_model/loss.py as a 0-dim tensor with an autograd node: kind is 'auc_loss', 'adaptive_auc_loss'
+    (weight [P]), 'log_rank_loss', 'ce_loss' or 'info_nce_loss'; pos holds P >= 1 scores and neg P * num_neg, read as [P, num_neg] exactly as
+    loss.py reshapes them (num_neg None: len(neg) / len(pos), which must divide).  Every term is evaluated in float64 from the fp32 scores by the
+    reference's formula as written, its + 1e-15 included, summed in float64 in one fixed order and rounded once; the gradients are float64 sums
+    rounded once, from the upstream scalar on the device — no host synchronisation.  The reference evaluates in fp32: on saturated scores its
+    1 - sigmoid(s) cancels and its exp(s) overflows above s = 88; this is the float64 value of the same formula."""
+    if kind not in RANK_KINDS:
+        raise ValueError(f'rank_loss: kind must be one of {sorted(RANK_KINDS)}, got {kind!r}')
+    _lib.require_device(pos, neg, weight)
+    if not torch.is_tensor(pos) or not torch.is_tensor(neg) or pos.dtype != torch.float32 or neg.dtype != torch.float32 or pos.device != neg.device:
+        raise ValueError('rank_loss expects float32 scores on one device')
+    P, Nn = pos.numel(), neg.numel()
+    k = Nn // P if (num_neg is None and P) else int(num_neg or 0)
+    if P < 1 or k < 1 or P * k != Nn:
+        raise ValueError(f'rank_loss: {Nn} negatives do not reshape to [{P}, {k}] (at least one positive and one negative per positive are required)')
+    if kind == 'adaptive_auc_loss':
+        if weight is None or weight.dtype != torch.float32 or weight.numel() != P or weight.device != pos.device:
+            raise ValueError(f'rank_loss: adaptive_auc_loss needs a float32 weight of {P} elements on the device of the scores')
+        weight = _c(weight.detach().reshape(-1))
+    else:
+        weight = None
+    return _RankLossFn.apply(RANK_KINDS[kind], _c(pos.reshape(-1)), _c(neg.reshape(-1)), k, weight)
+
+
+pair_dot.check = pair_linear.check = rank_loss.check = pair_check

@@ -712,6 +712,90 @@ class trainer:
             wzRec(results_arr2D[row], f'{name}@{tag}', want_save_npy=1, npy_dir=npy_dir)
         return results_arr2D
 
+    # -- the link predictors and ranking losses of Link_prediction_model (layer.py, loss.py; BaseModel.train / test, model.py:121-169, 187-266) ----
+    # The teacher GNN is the encoder; the decoder is `--predictor DOT | MLP`, the objective `--loss_func` over `--batch_size` sampled positives and
+    # `--num_neg` negatives each.  Next to the *_linkp entry points above, which keep their BCE on the raw dot product.
+    def setup_teacherGNN_linkpred(self):
+        """Teacher, predictor and one fused Adam over both parameter sets (model.py:82-88).  DOT has no parameters; MLP is
+        MLPPredictor(dim_commonEmb, mlp_hidden_channels, 1, mlp_num_layers, dropout): the reference's create_predictor_layer uses one width for
+        both, here the input width is the teacher's embedding width."""
+        from .Link_prediction_model import MLPPredictor, create_predictor_layer
+        a = self.args
+        self.setup_teacherGNN()
+        if a.predictor.upper() == 'MLP':
+            self.predictor = MLPPredictor(a.dim_commonEmb, a.mlp_hidden_channels, 1, a.mlp_num_layers, a.dropout).to(self.device)
+        else:
+            self.predictor = create_predictor_layer(a.mlp_hidden_channels, a.mlp_num_layers, a.dropout, a.predictor).to(self.device)
+        self.optimizer = self.optfun(list(self.teacherGNN.parameters()) + list(self.predictor.parameters()), lr=a.lr, weight_decay=self.weight_decay)
+
+    def gen_linkpred_edge_index(self, mode):
+        """(pos [2, P], neg [2, P * num_neg]): P = --batch_size positives of `mode` and --num_neg negatives for each, read as [P, num_neg] by the
+        losses.  The sampler fills negatives two columns at a time, so P * num_neg must be even."""
+        a = self.args
+        P, k = int(a.batch_size), int(a.num_neg)
+        if P < 1 or k < 1 or (P * k) % 2:
+            raise ValueError(f'link prediction needs batch_size >= 1, num_neg >= 1 and an even batch_size * num_neg (got {P} * {k}): '
+                             'the negative sampler writes (u, v) and (v, u) side by side')
+        s = self.link_sampler()
+        return s.positives(mode, P), s.negatives(mode, P * k)
+
+    def training_loss_linkpred(self):
+        """Forward + objective of BaseModel.train's step (model.py:147-157): a full teacher forward (res.commonEmb is read on sampled rows, so no
+        loss_rows / rows_only promise), predictor.score_pairs on the sampled pairs, calculate_loss(--loss_func).  Returns the 0-dim loss."""
+        from .Link_prediction_model import calculate_loss
+        res = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index)
+        pos, neg = self.gen_linkpred_edge_index('train')
+        h = res.commonEmb
+        return calculate_loss(self.args.loss_func, self.predictor.score_pairs(h, pos), self.predictor.score_pairs(h, neg), int(self.args.num_neg))
+
+    def run_trainSet_linkpred(self):
+        a = self.args
+        self.teacherGNN.train()
+        self.predictor.train()
+        loss = self.training_loss_linkpred()
+        self.optimizer.zero_grad()
+        loss.backward()
+        if a.grad_clip_norm >= 0:      # (model.py:160-162)
+            torch.nn.utils.clip_grad_norm_(self.teacherGNN.parameters(), a.grad_clip_norm)
+            if list(self.predictor.parameters()):      # (DOT has none)
+                torch.nn.utils.clip_grad_norm_(self.predictor.parameters(), a.grad_clip_norm)
+        self.optimizer.step()
+        value = self._checked(loss.item())
+        self.link_sampler().check()      # the loss has just been read: a failed negative slot, or a pair outside the graph, raises here
+        ops.pair_check()
+        return value
+
+    def evaluate_linkpred(self, mode='test'):
+        """{'Hits@20', 'Hits@50', 'Hits@100', 'AUC'} of the eval-mode predictor on a fresh `mode` sample (model.py:187-266 with `hits`; every positive
+        is ranked against all sampled negatives, ties as ops.rank_counts counts them)."""
+        if mode not in ('train', 'test'):
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
+        self.teacherGNN.eval()
+        self.predictor.eval()
+        with torch.no_grad():
+            h = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index).commonEmb
+            pos, neg = self.gen_linkpred_edge_index(mode)
+            ps, ns = self.predictor.score_pairs(h, pos).reshape(-1), self.predictor.score_pairs(h, neg).reshape(-1)
+        self.link_sampler().check()
+        ops.pair_check()
+        out = ops.hits_at_k(ps, ns, (20, 50, 100))
+        out['AUC'] = ops.auc(ps, ns)
+        return out
+
+    def train_teacherGNN_linkpred(self):
+        """--epochs steps of run_trainSet_linkpred, then evaluate_linkpred('test').  Eager steps only (no --hip_graph, no --resume).  Returns
+        (losses [epochs], metrics of the last evaluation)."""
+        self.setup_teacherGNN_linkpred()
+        losses = []
+        for epoch in range(self.epochs):
+            self.epoch = epoch
+            losses.append(self.run_trainSet_linkpred())
+            if epoch % 20 == 0:
+                print(f'Ep{epoch:03d}, {self.args.loss_func} = {losses[-1]:.5f}')
+        metrics = self.evaluate_linkpred('test')
+        save_model(self.teacherGNN, join(self.modeldir, 'teacherGNN'))
+        return np.array(losses), metrics
+
     @staticmethod
     def _checked(value):
         """The loss has just been read (host synchronisation): a device-side error recorded by a kernel of this step — a tile hand-over

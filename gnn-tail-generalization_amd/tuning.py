@@ -71,6 +71,11 @@ class Tuning:
     # cap on the column slabs a row block's sweep is split into.  0: the rule of the top-K sweep (about four blocks per CU)
     ncloss_max_splits: int = 0
 
+    # ---- link predictors (Link_prediction_model.layer, ops.pair_linear / pair_dot, cb_linkpred.hip) --------------------------------------------
+    # predictor.score_pairs(h, pairs) scores the index pairs in place (True) or gathers h[u], h[v] and runs predictor.forward on them (False): the
+    # same numbers either way (bit for bit for the MLP without dropout).  S = 262 144 pairs, D = 256, profiles/linkpred.md
+    score_pairs_fused: bool = True
+
     # ---- adjacency power on the device (ops.spgemm_csr / ops.SparsePower.from_adjacency, cb_spgemm.hip) -------------------------------------
     # products one chunk of the sparse x sparse product expands at most (a single row with more gets a chunk of its own).  A MEMORY bound, not a
     # measured break-even: 24 B of workspace per product, 1.5 GiB at 2^26, about 2 GB with the chunk's compact result beside it; the result's

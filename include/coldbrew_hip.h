@@ -872,6 +872,62 @@ size_t cb_rank_counts_workspace_bytes(int64_t P, int64_t Nn);
 int cb_rank_counts_f32(const float* pos, int64_t P, const float* neg, int64_t Nn, int32_t* gt, int32_t* eq, int32_t* status, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * The decoder of the link-prediction experiment on index pairs (Link_prediction_model/layer.py:85-106 `MLPPredictor`, :182-191 `DotPredictor`;
+ * loss.py:4-30; model.py:108-119, 152-158); cb_linkpred.hip.  h [N, K] fp32 (ld >= K): the encoder's embeddings; pairs int32 [2, S]: row 0 = u,
+ * row 1 = v.  Where the reference gathers h[u] and h[v] into two [S, K] matrices and multiplies them, these entries read the rows in place.
+ * A pair with an endpoint outside [0, N) (a failed sampler slot holds -1) is never used as an index; status [1] (zeroed by the call) counts such
+ * pairs (one integer atomic each, on that path only).  No float atomics; no host synchronisation; two calls with the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+
+/* C [S, Nout] = act((h[u] * h[v]) @ B + bias), B [K, Nout]; the A operand is formed while the three-limb NN kernel stages it.  Every product
+ * h[u][k] * h[v][k] is rounded to fp32 once and then split, and the K loop, the epilogue and the tile order are those of cb_gemm_nn_f32
+ * (tiles of 256 x 64 for Nout <= 64 and 128 x 128 otherwise; an output element's K order does not depend on the tile): C has the bits
+ * cb_gemm_nn_f32 gives on the materialised product.  drop_p > 0: C2 = dropout_p(C) with the keep-mask of cb_dropout_f32(C, ..., seed, seed_dev,
+ * offset = row0 * Nout), the bits cb_gemm_nn_drop2_f32 writes — from the GEMM's own epilogue when Nout > 64 and C, C2 allow float4 stores
+ * (16-byte aligned, ldc % 4 == 0, ldc2 % 4 == 0), else from cb_dropout_f32 after it, which needs ldc == ldc2 == Nout (checked before anything
+ * is launched); drop_p == 0: C2 is not read.  The whole row of an unusable pair is NaN in C and in C2, in either form.
+ * Exists where the three-limb NN kernel does (cb_pair_gemm_nn_supported: K % 4 == 0, Nout % 4 == 0, ld % 4 == 0, ldb % 4 == 0, h and B 16-byte
+ * aligned); elsewhere the caller composes the gather, the product and cb_gemm_nn_f32. */
+int cb_pair_gemm_nn_supported(const float* h, int64_t ld, const float* B, int64_t ldb, int64_t Nout, int64_t K);
+int cb_pair_gemm_nn_f32(const float* h, int64_t ld, int64_t N, const int32_t* pairs, int64_t S, const float* B, int64_t ldb, float* C, int64_t ldc,
+                        float* C2, int64_t ldc2, int64_t Nout, int64_t K, const float* bias, int relu, float drop_p, uint64_t seed,
+                        const uint64_t* seed_dev, int64_t row0, int32_t* status, void* stream);
+
+/* scores [S]: <h[u_e], h[v_e]> in fp32 (one wavefront per pair, fixed-shape reduction; float4 loads when D % 4 == 0, ld % 4 == 0 and h is
+ * 16-byte aligned).  NaN for an unusable pair. */
+int cb_pair_dot_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* pairs, int64_t S, float* scores, int32_t* status, void* stream);
+
+/* dh [N, D] (ldd >= D) = sum_e (c_e * h[v_e] into row u_e, c_e * h[u_e] into row v_e): the gradient of either predictor with respect to h.
+ * ldcoef == 0: coef [S], a scalar per pair (the dot predictor's ds); ldcoef >= D: coef [S, ldcoef], a row per pair multiplied elementwise (the
+ * MLP predictor's dX).  The 2 S contributions are sorted by destination; one wavefront per distinct node adds its contributions in ascending
+ * contribution number (2 e for u_e, 2 e + 1 for v_e) in float64 and writes the row once; rows no pair touches are zero.  Unusable pairs
+ * contribute nothing. */
+size_t cb_pair_scatter_workspace_bytes(int64_t S);
+int cb_pair_scatter_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* pairs, int64_t S, const float* coef, int64_t ldcoef,
+                        float* dh, int64_t ldd, void* ws, size_t ws_bytes, void* stream);
+
+/* The pairwise losses of Link_prediction_model/loss.py over pos [P] and neg [P * k] read as [P, k] (P >= 1, k >= 1):
+ *     CB_RANK_AUC           sum_ij (1 - (pos_i - neg_ij))^2
+ *     CB_RANK_ADAPTIVE_AUC  sum_ij weight_i (1 - (pos_i - neg_ij))^2                                    weight [P]
+ *     CB_RANK_LOG_RANK      mean_ij -log(sigmoid(pos_i - neg_ij) + 1e-15)
+ *     CB_RANK_CE            mean_i -log(sigmoid(pos_i) + 1e-15) + mean_ij -log(1 - sigmoid(neg_ij) + 1e-15)
+ *     CB_RANK_INFO_NCE      mean_i -log(exp(pos_i) / (exp(pos_i) + sum_j exp(neg_ij)) + 1e-15)
+ * Every term is evaluated in float64 from the fp32 scores by the formula as written (sigmoid(x) = 1 / (1 + exp(-x))), summed in float64 in one
+ * fixed order (thread-strided partial sums, a halving tree per block, one over the at most 256 blocks) and rounded to fp32 once.  The reference
+ * evaluates in fp32, where 1 - sigmoid(s) cancels and exp(s) overflows above s = 88; this is the float64 value.
+ * Backward: g is a DEVICE pointer to the upstream scalar; dpos [P] and dneg [P * k], each element a float64 sum rounded once. */
+#define CB_RANK_AUC 0
+#define CB_RANK_ADAPTIVE_AUC 1
+#define CB_RANK_LOG_RANK 2
+#define CB_RANK_CE 3
+#define CB_RANK_INFO_NCE 4
+size_t cb_rank_loss_workspace_bytes(void);
+int cb_rank_loss_fwd_f32(int32_t kind, const float* pos, int64_t P, const float* neg, int64_t k, const float* weight, float* loss, void* ws,
+                         size_t ws_bytes, void* stream);
+int cb_rank_loss_bwd_f32(int32_t kind, const float* pos, int64_t P, const float* neg, int64_t k, const float* weight, const float* g, float* dpos,
+                         float* dneg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
