@@ -1,0 +1,246 @@
+// One layer of the link-prediction encoders (Link_prediction_model/layer.py:8-35: SAGEConv / GraphConv / GCNConv(normalize=False)) in one kernel:
+//     agg[v] = row_scale[v] * sum_{j in row v} col_scale[col[j]] * h[col[j]]                      (the aggregation, rows of 256 fp32)
+//     out[v] = epi( [agg[v] | self[v]] @ B + bias )                                               (B: 512 x 256, or 256 x 256 without `self`)
+// Forward (by-dst CSR, h = self = X, B = [W_n^T ; W_s^T]) and backward (by-src CSR, h = self = G, B = [W_n ; W_s], agg also stored: the weight
+// gradient reads it) are the same launch.  What it spares against aggregation -> GEMM: the write and the read of the aggregated matrix and the
+// second read of X, i.e. the `[agg | x]` operand never exists in memory.
+//
+// Shape of a block: 8 wavefronts, one 64-row tile, three phases kept apart by ONE block barrier (no hand-over through counters, no persistent
+// loop, no spin, no atomics, nothing to report in the device error word):
+//   1. all eight wavefronts copy their 8 rows of `self` into columns 256..511 of the LDS tile and reduce their share of the tile's rows into columns
+//      0..255 — stream_rows of cb_spmm_core.h, the walk and the sums of cb_spmm_csr_f32 (rows cut among the wavefronts at equal edge counts as in
+//      cb_agg_gemm.hip; hub rows are reduced by the hub kernels BEFORE this launch and read back from `agg_out`);
+//   2. __syncthreads();
+//   3. wavefronts 0..3 multiply the 64 x 512 tile by the image (tile_times_image of cb_tile_gemm.h: three bf16 limbs, the six limb products of
+//      cb_gemm_nn_f32 in its order, K steps 0..31 in order into the same accumulators) and store through their private C strips.
+// The arithmetic is therefore cb_spmm_csr_f32's followed by cb_gemm_nn_f32's on the materialised [agg | self], bit for bit.
+//
+// LDS: ONE 64 x 516-float tile (132 096 B) + four C strips (8 704 B) = 140 800 B of the CU's 160 KiB, one block per CU.  The alternative — a 64 x 260
+// tile re-filled with the self rows after K step 15, 75 KB, two blocks per CU — was not taken: it puts a global-load latency and two more barriers in
+// the middle of the K loop of every tile and needs tile_times_image to resume on live accumulators from an image offset (a change to a header three
+// other kernels share).  Occupancy of the gather phase comes from the block instead: eight wavefronts (two per SIMD, twelve gathers in flight each)
+// reduce the tile, the figure the aggregation + GEMM kernel settled on; the four that multiply afterwards have 256 registers each, which the K
+// loop's two-step prefetch ring needs anyway.  Without `self` (GCN) the tile is 64 x 260 and two blocks share a CU.  The choice between the two tile
+// forms was made from the guides' LDS / occupancy arithmetic, not from a measurement of both; the layer against the two-kernel form is measured
+// (tools/bench_sage.py, profiles/sage.md).
+#include "cb_common.h"
+#include "cb_limb_core.h"
+#include "cb_philox.h"
+#include "cb_spmm_core.h"
+#include "cb_tile_gemm.h"
+
+namespace cb {
+
+constexpr int kSG = 8;                 // wavefronts of a block (all gather; 0..3 multiply)
+constexpr int kSU = 12;                // gathers in flight per wavefront
+constexpr int kTLD2 = 2 * kKD + 4;     // floats per row of the [agg | self] tile (516 * 4 = 16 mod 256 bytes, as kTLD)
+
+struct SageArgs {
+  const int* rowptr;
+  const int* col;
+  int n_rows, hub_T;
+  const float* h;
+  int64_t ld_h;
+  const float* self;
+  int64_t ld_self;
+  const float* col_scale;
+  const float* row_scale;
+  const uint4* image;
+  const float* bias;
+  int relu;
+  uint32_t thresh;       // 0: no dropout
+  float keep_scale;
+  uint64_t seed;
+  const uint64_t* seed_dev;
+  int64_t row0;
+  float* agg;            // hub rows' way into the tile; WAGG: receives every aggregated row
+  int64_t ld_agg;
+  float* out;
+  int64_t ld_out;
+};
+
+template <bool HAS_SELF, bool CS, bool WAGG, int GP>
+__global__ void __launch_bounds__(64 * kSG) k_sage_layer(SageArgs a) {
+  constexpr int TLD = HAS_SELF ? kTLD2 : kTLD;
+  constexpr int NSTEPS = HAS_SELF ? 2 * kNS : kNS;
+  __shared__ __attribute__((aligned(16))) float tile[kTM * TLD];
+  __shared__ __attribute__((aligned(16))) float cstrip[4][8 * kCLD];
+  const int lane = lane_id(), wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int r0 = (int)blockIdx.x * kTM;
+  const int nrt = min(kTM, a.n_rows - r0);
+  const int c0 = lane * 4;
+  float* tile_lane = tile + c0;
+
+  // ---- phase 1a: the self rows (8 per wavefront; rows past the matrix are zero) ----
+  if constexpr (HAS_SELF) {
+    float4 sv[kTM / kSG];
+#pragma unroll
+    for (int i = 0; i < kTM / kSG; ++i) {
+      const int row = wv * (kTM / kSG) + i;
+      sv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row < nrt) sv[i] = *reinterpret_cast<const float4*>(a.self + (int64_t)(r0 + row) * a.ld_self + c0);
+    }
+#pragma unroll
+    for (int i = 0; i < kTM / kSG; ++i) *reinterpret_cast<float4*>(tile_lane + (wv * (kTM / kSG) + i) * TLD + kKD) = sv[i];
+  }
+
+  // ---- phase 1b: the aggregation of this wavefront's rows (cb_agg_gemm.hip's cut of the tile at equal edge counts) ----
+  {
+    const int my_ptr = __builtin_nontemporal_load(a.rowptr + r0 + min(lane, nrt));
+    const int ptr_hi = a.rowptr[r0 + nrt];
+    float my_scale = 1.f;
+    if (a.row_scale && lane < nrt) my_scale = __builtin_nontemporal_load(a.row_scale + r0 + lane);
+    int nxt = __shfl_down(my_ptr, 1);
+    if (lane == kWave - 1) nxt = ptr_hi;
+    const unsigned long long hubmask = __ballot(lane < nrt && (nxt - my_ptr) > a.hub_T);
+    const int e0 = bcast_lane(my_ptr, 0), e1 = ptr_hi;
+    const int64_t span = (int64_t)e1 - e0;
+    const int ta = e0 + (int)(span * wv / kSG), tb = e0 + (int)(span * (wv + 1) / kSG);
+    const int ra = wv == 0 ? 0 : (int)__popcll(__ballot(lane < nrt && my_ptr < ta));
+    const int rb = wv == kSG - 1 ? nrt : (int)__popcll(__ballot(lane < nrt && my_ptr < tb));
+    const float bvec[4] = {0.f, 0.f, 0.f, 0.f};
+    Epilogue ep{};
+    ep.row_scale = a.row_scale;
+    ep.col_scale = a.col_scale;
+    const FusedEpi fe{};
+    const float* h_lane = a.h + c0;
+    float* out_lane = WAGG ? a.agg + c0 : nullptr;
+    int r = ra;
+    while (r < rb) {      // maximal hub-free runs of [ra, rb)
+      const unsigned long long m = (hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
+      const int nh = m ? r + (__ffsll((long long)m) - 1) : rb;
+      if (nh > r)
+        stream_rows<4, kSU, true, false, false, float, GP, TLD, true, CS, false, !WAGG>(r, nh, nrt, my_ptr, my_scale, r0, a.col, h_lane, a.ld_h, out_lane, a.ld_agg,
+                                                                                         true, 0, bvec, fe, c0, nullptr, 0, ep, tile_lane, ptr_hi);
+      if (nh < rb)        // hub row nh: finished by the hub kernels, which ran before this launch
+        *reinterpret_cast<float4*>(tile_lane + nh * TLD) = *reinterpret_cast<const float4*>(a.agg + (int64_t)(r0 + nh) * a.ld_agg + c0);
+      r = nh + 1;
+    }
+    if (wv == kSG - 1) {
+      for (int i = nrt; i < kTM; ++i) *reinterpret_cast<float4*>(tile_lane + i * TLD) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: [agg | self] @ B on the matrix cores, epilogue, store ----
+  if (wv < 4) {
+    f32x16 acc[2][2];
+    tile_times_image<NSTEPS, TLD, 2>(tile, a.image, wv, lane, acc);
+    const int nl = 64 * wv + (lane & 15) * 4;
+    float bv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (a.bias) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bv[e] = a.bias[nl + e];
+    }
+    const uint64_t seed_eff = a.seed_dev ? a.seed + *a.seed_dev : a.seed;
+    acc_rows_through_strip(acc, cstrip[wv], wv, lane, [&](int mt, int n, const float4& v) {
+      if (mt >= nrt) return;
+      const int64_t m = r0 + mt;
+      float o[4] = {v.x, v.y, v.z, v.w};
+      const float rs = 1.f, ad = 0.f;      // (cb_gemm_core.h nn_epilogue's expression: o * rowscale + addend + bias, then the ReLU)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = o[e] * rs + ad + bv[e];
+        if (a.relu) o[e] = fmaxf(o[e], 0.f);
+      }
+      if (a.thresh) {                      // cb_dropout_f32's keep-mask for (seed, flat index (row0 + m) * 256 + n)
+        float mk[4];
+        keep4(seed_eff, ((a.row0 + m) * kND + n) >> 2, a.thresh, a.keep_scale, mk);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = o[e] * mk[e];
+      }
+      store_stream<4>(a.out + m * a.ld_out + n, o);
+    });
+  }
+}
+
+template <bool HAS_SELF, bool CS, bool WAGG>
+static void launch_sage_gp(int gp, dim3 grid, hipStream_t st, const SageArgs& a) {
+  if (gp) hipLaunchKernelGGL((k_sage_layer<HAS_SELF, CS, WAGG, 2>), grid, dim3(64 * kSG), 0, st, a);
+  else hipLaunchKernelGGL((k_sage_layer<HAS_SELF, CS, WAGG, 0>), grid, dim3(64 * kSG), 0, st, a);
+}
+
+template <bool HAS_SELF>
+static void launch_sage(bool cs, bool wagg, int gp, dim3 grid, hipStream_t st, const SageArgs& a) {
+  if (cs) { if (wagg) launch_sage_gp<HAS_SELF, true, true>(gp, grid, st, a); else launch_sage_gp<HAS_SELF, true, false>(gp, grid, st, a); }
+  else { if (wagg) launch_sage_gp<HAS_SELF, false, true>(gp, grid, st, a); else launch_sage_gp<HAS_SELF, false, false>(gp, grid, st, a); }
+}
+
+static inline bool sage_rows_ok(const float* p, int64_t ld) { return aligned16(p) && ld % 4 == 0 && ld >= kKD; }
+
+}  // namespace cb
+
+using namespace cb;
+
+extern "C" size_t cb_sage_image_bytes(int has_self) { return (size_t)(has_self ? 2 : 1) * kNS * kNT * 3 * 64 * sizeof(uint4); }
+
+extern "C" int cb_sage_image_f32(const float* W_n, int64_t ld_n, const float* W_s, int64_t ld_s, int transpose, void* image, size_t image_bytes, void* stream) {
+  CB_CHECK_ARG(W_n && image && ld_n >= kKD && (!W_s || ld_s >= kKD), CB_E_INVALID, "cb_sage_image_f32: null pointer / bad leading dimension (256 x 256 blocks)");
+  CB_CHECK_ARG(image_bytes >= cb_sage_image_bytes(W_s != nullptr) && aligned16(image), CB_E_WORKSPACE, "cb_sage_image_f32: image buffer too small or misaligned");
+  // B[k][n] = W[k][n] (transpose = 0) or W[n][k] (transpose = 1), W_n's block on top of W_s's: K steps 0..15 and 16..31 of the image
+  const float* W[2] = {W_n, W_s};
+  const int64_t ld[2] = {ld_n, ld_s};
+  for (int b = 0; b < (W_s ? 2 : 1); ++b) {
+    const int64_t sk = transpose ? 1 : ld[b], sn = transpose ? ld[b] : 1;
+    hipLaunchKernelGGL(k_weight_image, dim3(kNS * kNT * 64 / 256), dim3(256), 0, (hipStream_t)stream, W[b], sk, sn, (uint4*)image + (size_t)b * kNS * kNT * 3 * 64, kNS);
+    CB_LAUNCH_CHECK();
+  }
+  return CB_OK;
+}
+
+extern "C" int cb_sage_layer_supported(int64_t d_in, int64_t d_out, int32_t h_bf16, const void* h, int64_t ld_h, const float* self, int64_t ld_self,
+                                       const float* agg_out, int64_t ld_agg, const float* out, int64_t ld_out) {
+  if (d_in != kKD || d_out != kND || h_bf16 || !h || !out) return 0;
+  if (!sage_rows_ok((const float*)h, ld_h) || !sage_rows_ok(out, ld_out)) return 0;
+  if (self && !sage_rows_ok(self, ld_self)) return 0;
+  if (agg_out && !sage_rows_ok(agg_out, ld_agg)) return 0;
+  return 1;
+}
+
+extern "C" int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t ld_h, const float* self, int64_t ld_self, const float* col_scale,
+                                 const float* row_scale, const void* image, const float* bias, int relu, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                 int64_t row0, float* agg_out, int64_t ld_agg, int32_t agg_hubs_only, float* out, int64_t ld_out, void* stream) {
+  const char* who = "cb_sage_layer_f32";
+  cb_csr_view v;
+  const int rc = check_csr_view(who, g, kKD, v);
+  if (rc != CB_OK || v.n_rows == 0) return rc;
+  CB_CHECK_ARG(v.n_rows < INT32_MAX - kTM, CB_E_RANGE, "%s: size exceeds the int32 contract", who);
+  CB_CHECK_ARG(h && image && out && aligned16(image), CB_E_INVALID, "%s: null pointer or misaligned image", who);
+  CB_CHECK_ARG(cb_sage_layer_supported(kKD, kND, 0, h, ld_h, self, ld_self, agg_out, ld_agg, out, ld_out), CB_E_INVALID,
+               "%s: 16-byte aligned fp32 rows of at least 256 floats (ld %% 4 == 0) required; ask cb_sage_layer_supported first", who);
+  CB_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && row0 >= 0 && (drop_p == 0.f || relu), CB_E_INVALID, "%s: dropout follows the ReLU, 0 <= p < 1", who);
+  CB_CHECK_ARG(agg_out || (v.n_hubs == 0 && !agg_hubs_only), CB_E_INVALID, "%s: a plan with hub rows needs agg_out (the hub rows' way into the tile)", who);
+  hipStream_t st = (hipStream_t)stream;
+  const bool cs = col_scale != nullptr, wagg = agg_out && !agg_hubs_only;
+  if (v.n_hubs > 0) {      // hub rows first: the layer kernel reads their finished rows back (cb_spmm_csr_f32's hub kernels, its sums)
+    Epilogue ep{};
+    ep.row_scale = row_scale;
+    ep.col_scale = col_scale;
+    ep.col_flags = v.col_flags;
+    float* partial = (float*)v.ws;
+    const int64_t ld_p = kKD;
+    const dim3 gridc((unsigned)((v.n_chunks + 3) / 4), 1), blk(256);
+#define CB_SAGE_HUB(GP_, CS_)                                                                                                                       \
+  hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, GP_, CS_>), gridc, blk, 0, st, v.rowptr, v.col, h, ld_h, kKD, v.hub_threshold, v.n_hubs, v.n_chunks, \
+                     v.hub_rows, v.hub_chunk_ptr, partial, ld_p, ep)
+    if (cs) { if (v.col_flags) CB_SAGE_HUB(2, true); else CB_SAGE_HUB(0, true); }
+    else { if (v.col_flags) CB_SAGE_HUB(2, false); else CB_SAGE_HUB(0, false); }
+#undef CB_SAGE_HUB
+    CB_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_spmm_hub_finish<4, false>), dim3((unsigned)((v.n_hubs + 3) / 4), 1), blk, 0, st, kKD, v.n_hubs, v.hub_rows, v.hub_chunk_ptr, partial,
+                       ld_p, agg_out, ld_agg, ep, FusedEpi{});
+    CB_LAUNCH_CHECK();
+  }
+  SageArgs a{};
+  a.rowptr = v.rowptr; a.col = v.col; a.n_rows = (int)v.n_rows; a.hub_T = v.hub_threshold;
+  a.h = h; a.ld_h = ld_h; a.self = self; a.ld_self = ld_self; a.col_scale = col_scale; a.row_scale = row_scale;
+  a.image = (const uint4*)image; a.bias = bias; a.relu = relu;
+  a.thresh = drop_p > 0.f ? dropout_threshold(drop_p) : 0u; a.keep_scale = 1.f / (1.f - drop_p);
+  a.seed = seed; a.seed_dev = seed_dev; a.row0 = row0;
+  a.agg = agg_out; a.ld_agg = ld_agg; a.out = out; a.ld_out = ld_out;
+  const dim3 grid((unsigned)((v.n_rows + kTM - 1) / kTM));
+  if (self) launch_sage<true>(cs, wagg, v.col_flags, grid, st, a);
+  else launch_sage<false>(cs, wagg, v.col_flags, grid, st, a);
+  CB_LAUNCH_CHECK();
+  return CB_OK;
+}

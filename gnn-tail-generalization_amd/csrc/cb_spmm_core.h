@@ -283,7 +283,9 @@ __device__ __forceinline__ void gather_pol(float (&v)[VEC], const HT* __restrict
 // TLD > 0 (cb_agg_gemm.hip): every finished row is also written to an LDS tile — tile_lane = this lane's 4 columns of the
 // wavefront's local row 0, TLD floats per tile row.
 // P65 (64-row blocks, cb_agg_gemm.hip): lane i holds rowptr[r0 + i] for i < 64 and ptr_hi = rowptr[r0 + 64].
-template <int VEC, int U, bool FULL, bool FUSED, bool ACC, typename HT, int GP = 0, int TLD = 0, bool P65 = false, bool CS = false, bool MIXB = false>
+// TILE_ONLY (cb_sage.hip, TLD > 0): the finished row goes to the LDS tile alone — nothing is written through out_lane (may be null).
+template <int VEC, int U, bool FULL, bool FUSED, bool ACC, typename HT, int GP = 0, int TLD = 0, bool P65 = false, bool CS = false, bool MIXB = false,
+          bool TILE_ONLY = false>
 __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr_v, float my_scale, int r0, const int* __restrict__ col,
                                             const HT* __restrict__ h_lane, int64_t ld_h, float* __restrict__ out_lane,
                                             int64_t ld_out, bool active_in, int relu, const float (&bvec)[VEC], const FusedEpi& fe,
@@ -294,6 +296,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
   // MIXB (FusedEpi): my_xp0 / my_xp1: lane i holds the position of local row i in the compact operands; cs_acc: the wavefront's 4 running column sums
   static_assert(!MIXB || (FUSED && VEC == 4 && FULL && !ACC && TLD == 0 && !P65), "folded mix gradients: the fused d % 256 == 0 kernel on all node rows");
   static_assert(TLD == 0 || (VEC == 4 && FULL), "on-chip row tile: d == 256, float4 lanes");
+  static_assert(!TILE_ONLY || (TLD > 0 && !FUSED && !ACC), "tile-only rows: the plain aggregation into an on-chip tile");
   static_assert(!CS || (!FUSED && !ACC && sizeof(HT) == 4), "source-row factor: plain fp32 aggregation only");
   struct PtrAt {      // rowptr of local row i (wave-uniform i)
     int v, hi;
@@ -389,7 +392,15 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
       }
       if (!lp_done) {
         float rv[VEC];
-        write_row<VEC>(out_lane + (int64_t)(r0 + cur) * ld_out, acc, s, bvec, relu, rv);
+        if constexpr (TILE_ONLY) {      // write_row's value, not stored
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float t = scale_add(acc[i], s, bvec[i]);
+            rv[i] = relu ? fmaxf(t, 0.f) : t;
+          }
+        } else {
+          write_row<VEC>(out_lane + (int64_t)(r0 + cur) * ld_out, acc, s, bvec, relu, rv);
+        }
         if constexpr (TLD > 0) *reinterpret_cast<float4*>(tile_lane + cur * TLD) = make_float4(rv[0], rv[1], rv[2], rv[3]);
       }
     }

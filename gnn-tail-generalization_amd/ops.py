@@ -27,7 +27,11 @@ Link predictors and ranking losses (Link_prediction_model/layer.py:85-106, 182-1
   pair_dot          <h[u], h[v]> per index pair (DotPredictor); gradient through the sorted inverted index, no atomics
   pair_linear       act((h[u] * h[v]) @ W^T + b) (+ dropout): MLPPredictor's first layer, its A operand formed while the GEMM stages it
   rank_loss         auc / adaptive_auc / log_rank / ce / info_nce over pos [P] and neg [P, k], every term in float64, rounded once
+Encoders of the link-prediction experiment (Link_prediction_model/layer.py:19-75; model.py:290-304):
+  sage_layer        act((s * (A X)) W_n^T + X W_s^T + b): one SAGEConv / GraphConv / GCNConv(normalize=False) layer with the ReLU and dropout after it; one
+                    kernel per direction at 256 -> 256 (aggregation into an on-chip tile, the GEMM from there), the composed kernels elsewhere
 """
+import collections
 import ctypes
 import os
 
@@ -1850,3 +1854,156 @@ def rank_loss(kind, pos, neg, num_neg=None, weight=None):
 
 
 pair_dot.check = pair_linear.check = rank_loss.check = pair_check
+
+
+# ---------------------------------------------------------------------------------------------
+# one layer of the link-prediction encoders (Link_prediction_model/layer.py:8-35; csrc/cb_sage.hip)
+# ---------------------------------------------------------------------------------------------
+SAGE_MODES = ('SAGE', 'WSAGE', 'GCN')
+sage_paths = collections.deque(maxlen=256)      # ('fwd' | 'bwd', 'fused' | 'composed') per layer launch, newest last (tests, tools/bench_sage.py)
+
+
+def inv_indeg(graph):
+    """1 / in-degree as float32 [N], 0 where a node has no in-edge (its mean is 0, not NaN); made once per graph."""
+    s = getattr(graph, '_inv_indeg', None)
+    if s is None:
+        deg = (graph.rowptr[1:] - graph.rowptr[:-1]).to(torch.float32)
+        s = graph._inv_indeg = torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg)).contiguous()
+    return s
+
+
+def _sage_image(W_n, W_s, transpose):
+    lib = _lib.load()
+    nb = lib.cb_sage_image_bytes(int(W_s is not None))
+    img = torch.empty(nb, dtype=torch.uint8, device=W_n.device)
+    with torch.cuda.device(W_n.device):
+        _lib.check(lib.cb_sage_image_f32(_lib.ptr(W_n), W_n.stride(0), _lib.ptr(W_s), W_s.stride(0) if W_s is not None else 0, int(bool(transpose)),
+                                         _lib.ptr(img), nb, _lib.stream_ptr()), 'cb_sage_image_f32')
+    return img
+
+
+def _sage_supported(h, d_out, has_self, agg, out):
+    lib = _lib.load()
+    return bool(lib.cb_sage_layer_supported(h.shape[1], d_out, int(h.dtype == torch.bfloat16), _lib.ptr(h), h.stride(0), _lib.ptr(h if has_self else None),
+                                            h.stride(0), _lib.ptr(agg), agg.stride(0) if agg is not None else 0, _lib.ptr(out), out.stride(0)))
+
+
+def sage_layer_raw(graph, h, W_n, W_s=None, bias=None, scale=None, relu=False, p=0.0, seed=0, backward=False, want_agg=False, fused=None, out=None, row0=0):
+    """(out, agg or None, path): one encoder layer without autograd.  forward (backward=False): by-dst CSR, agg = scale * (A h) by row,
+    out = epi([agg | h] @ [W_n^T ; W_s^T] + bias).  backward=True: by-src CSR, agg = A^T (scale * h) by source row, out = [agg | h] @ [W_n ; W_s].
+    W_s None: no self block.  fused (None: tuning.T.sage_fused): the one-kernel layer where cb_sage_layer_supported allows, else — and for
+    fused=False — the composed path: graph.spmm, the materialised [agg | h], one cb_gemm_nn_f32 with K = 2 d, ops.dropout's kernel.  The two give the
+    same bits.  out: optional [N, d_out] float32 destination with contiguous rows."""
+    from . import gemm
+    from .graph import CSRGraph
+    from .tuning import T
+    lib = _lib.load()
+    _lib.require_device(h, W_n, W_s, bias, scale, out)
+    if not isinstance(graph, CSRGraph) or graph.n_cols != graph.N or (backward and graph.rowptr_t is None):
+        raise ValueError('sage_layer: the whole square graph on this device (a CSRGraph with both orientations) is required; node-sharded and segmented '
+                         'graphs are not built for the encoders')
+    if h.dim() != 2 or h.shape[0] != graph.N or (h.shape[1] > 1 and h.stride(1) != 1):
+        raise ValueError(f'sage_layer: rows [{graph.N}, d] with contiguous elements expected, got {tuple(h.shape)}')
+    if p and not relu:
+        raise ValueError('sage_layer: dropout follows the ReLU (layer.py:29-35)')
+    N, d = h.shape
+    has_self = W_s is not None
+    d_out = W_n.shape[1] if backward else W_n.shape[0]
+    if tuple(W_n.shape) != ((d, d_out) if backward else (d_out, d)) or (has_self and W_s.shape != W_n.shape) or W_n.dtype != torch.float32:
+        raise ValueError(f'sage_layer: weights [out, in] float32 expected, got {tuple(W_n.shape)} for rows of {d}')
+    W_n = _c(W_n)
+    W_s = _c(W_s) if has_self else None
+    if out is None:
+        out = torch.empty((N, d_out), dtype=torch.float32, device=h.device)
+    elif tuple(out.shape) != (N, d_out) or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise ValueError(f'sage_layer: out must be a float32 [{N}, {d_out}] matrix with contiguous rows')
+    want_fused = T.sage_fused if fused is None else bool(fused)
+    if want_fused and N > 0 and _sage_supported(h, d_out, has_self, None, out):
+        plan = graph._plan_t if backward else graph._plan
+        agg, hubs_only = None, 0
+        if want_agg or plan.n_hubs > 0:      # (hub rows reach the kernel's tile through memory: an [N, 256] allocation of which only those rows are written)
+            agg, hubs_only = torch.empty((N, 256), dtype=torch.float32, device=h.device), int(not want_agg)
+        img = _sage_image(W_n, W_s, transpose=not backward)
+        view = graph._view(256, backward, use_flags=True)
+        with torch.cuda.device(h.device):
+            _lib.check(lib.cb_sage_layer_f32(ctypes.byref(view), _lib.ptr(h), h.stride(0), _lib.ptr(h if has_self else None), h.stride(0),
+                                             _lib.ptr(scale if backward else None), _lib.ptr(None if backward else scale), _lib.ptr(img), _lib.ptr(bias),
+                                             int(bool(relu)), float(p), ctypes.c_uint64(int(seed)), seed_dev_ptr(), int(row0), _lib.ptr(agg),
+                                             256 if agg is not None else 0, hubs_only, _lib.ptr(out), out.stride(0), _lib.stream_ptr()), 'cb_sage_layer_f32')
+        sage_paths.append(('bwd' if backward else 'fwd', 'fused'))
+        return out, (agg if want_agg else None), 'fused'
+    K = 2 * d if has_self else d
+    cat = torch.empty((N, K), dtype=torch.float32, device=h.device)
+    aggv = cat[:, :d]
+    if backward and scale is not None and d % 256:      # (the source-row factor exists at d % 256 == 0: elsewhere a row-scaled copy of h is gathered)
+        graph.spmm(act_bwd(h, None, scale)[0], transpose=True, out=aggv)
+    else:
+        graph.spmm(h, transpose=backward, row_scale=None if backward else scale, col_scale=scale if backward else None, out=aggv)
+    if has_self:
+        cat[:, d:].copy_(h)
+        B = torch.cat([W_n, W_s]) if backward else torch.cat([W_n.t(), W_s.t()])
+    else:
+        B = W_n if backward else W_n.t()
+    if p:
+        y = gemm.mm_nn(cat, B.contiguous(), bias=bias, relu=relu)
+        out.copy_(_dropout_raw(y, p, seed, offset=int(row0) * d_out))
+    else:
+        gemm.mm_nn(cat, B.contiguous(), bias=bias, relu=relu, out=out)
+    sage_paths.append(('bwd' if backward else 'fwd', 'composed'))
+    return out, (aggv if want_agg else None), 'composed'
+
+
+class _SageLayerFn(torch.autograd.Function):
+    """Y = epi((s * (A X)) W_n^T + X W_s^T + b).  With G = dY * 1[Y > 0] / (1 - p) (the stored activation is the mask: dropout(relu(y)) > 0 exactly where the
+    ReLU passed and the mask kept; G = dY on a layer without ReLU) and R = A^T (s * G):  dX = R W_n + G W_s,  dW_n = R^T X,  dW_s = G^T X,  db = colsum(G).
+    The forward stores neither the aggregated matrix nor mask words."""
+
+    @staticmethod
+    def forward(ctx, graph, x, W_n, W_s, bias, mode, relu, p, seed, fused):
+        scale = inv_indeg(graph) if mode == 'SAGE' else None
+        y, _, _ = sage_layer_raw(graph, x, W_n, W_s, bias, scale, relu, p, seed, False, False, fused)
+        ctx.graph, ctx.scale, ctx.relu, ctx.p, ctx.fused, ctx.has_bias = graph, scale, relu, p, fused, bias is not None
+        ctx.save_for_backward(x, W_n, W_s, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import gemm
+        x, W_n, W_s, y = ctx.saved_tensors
+        need_b = ctx.has_bias and ctx.needs_input_grad[4]
+        dy = _c(dy)
+        keep = 1.0 / (1.0 - ctx.p) if ctx.p else 1.0
+        if ctx.relu:
+            rs = torch.full((dy.shape[0],), keep, dtype=torch.float32, device=dy.device) if ctx.p else None
+            G, db = act_bwd(dy, y, rs, want_out=True, want_colsum=need_b)
+            if db is not None and ctx.p:
+                db = db * keep
+        else:
+            G, db = dy, (act_bwd(dy, None, None, want_out=False, want_colsum=True)[1] if need_b else None)
+        dx, R, _ = sage_layer_raw(ctx.graph, G, W_n, W_s, None, ctx.scale, False, 0.0, 0, True, True, ctx.fused)
+        dWn = gemm.mm_tn(R, x) if ctx.needs_input_grad[2] else None
+        dWs = gemm.mm_tn(G, x) if (W_s is not None and ctx.needs_input_grad[3]) else None
+        return None, (dx if ctx.needs_input_grad[1] else None), dWn, dWs, db, None, None, None, None, None
+
+
+def sage_layer(graph, x, W_n, W_s=None, bias=None, mode='SAGE', relu=False, p=0.0, seed=None, fused=None):
+    """One layer of the SAGE / WSAGE / GCN encoders with its autograd: act((s * (A X)) W_n^T + X W_s^T + b), A X the sum over the in-neighbours as the
+    by-dst CSR lists them; mode 'SAGE': s = 1 / indeg (0 where indeg = 0), 'WSAGE': s = 1, 'GCN': s = 1 and no W_s.  relu: ReLU, then dropout p with
+    ops.dropout's keep-mask for `seed` (None: next_seed()).  Weights are [out, in].  fused (None: tuning.T.sage_fused) asks for the one-kernel layer
+    (256 -> 256 fp32 rows); other shapes and fused=False take the composed path — ops.sage_paths records which."""
+    mode = str(mode).upper()
+    if mode not in SAGE_MODES:
+        raise ValueError(f'sage_layer: mode must be one of {SAGE_MODES}, got {mode!r}')
+    _lib.require_device(x, W_n, W_s, bias)
+    if (mode == 'GCN') != (W_s is None):
+        raise ValueError('sage_layer: SAGE / WSAGE take a self weight W_s, GCN takes none')
+    if x.dtype != torch.float32:
+        raise TypeError('sage_layer expects float32 rows')
+    p = float(p) if relu else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'sage_layer: 0 <= p < 1 expected, got {p}')
+    if p and seed is None:
+        seed = next_seed()
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return _SageLayerFn.apply(graph, x, W_n, W_s, bias, mode, bool(relu), p, int(seed or 0), fused)

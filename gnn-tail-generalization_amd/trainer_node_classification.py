@@ -796,6 +796,97 @@ class trainer:
         save_model(self.teacherGNN, join(self.modeldir, 'teacherGNN'))
         return np.array(losses), metrics
 
+    # -- the same experiment with the encoder the reference trains (model.py:37-88: create_input_layer, create_gnn_layer(--encoder), create_predictor_layer) ----
+    # h = encoder(input_feat, graph) stands where the *_linkpred methods above read the teacher's commonEmb; sampler, predictor.score_pairs, calculate_loss,
+    # gradient clipping, metrics and the device checks are theirs.
+    def setup_linkpred_encoder(self):
+        """Embedding (create_input_layer: trainable, xavier_uniform_, unless --use_node_feats), encoder (create_encoder_layer(--encoder), --gnn_num_layers
+        layers of --gnn_hidden_channels), predictor (input width gnn_hidden_channels) and one fused Adam over all three.  The device graph is built here
+        from data.edge_index (the whole graph on this device) and the link sampler on it."""
+        from . import optim as cb_optim
+        from .graph import CSRGraph, build_graph
+        from .Link_prediction_model import MLPPredictor, create_encoder_layer, create_input_layer, create_predictor_layer
+        from .Link_prediction_model.model import reset_input_layer
+        a = self.args
+        if str(a.optimizer) != 'Adam':
+            raise NotImplementedError(f'--optimizer {a.optimizer} is not built on the HIP path: optim.py has the fused Adam only')
+        if a.encoder in ('CN', 'AA', 'PPR'):
+            raise NotImplementedError(f'--encoder {a.encoder} is a heuristic without parameters: evaluate_linkp_heuristic scores it, there is nothing to train')
+        n = self.global_nodes()
+        self.enc_graph = build_graph(self.data.edge_index, n)
+        if not isinstance(self.enc_graph, CSRGraph):
+            raise NotImplementedError('the encoders need the whole int32-indexed graph on this device; segmented and node-sharded graphs are not built for them')
+        self._link_sampler, self._link_sampler_of = ops.LinkSampler(self.enc_graph, self.data.train_mask), self.data.train_mask
+        input_dim, self.emb = create_input_layer(n, int(self.data.x.shape[1]), a.emb_hidden_channels, a.use_node_feats, a.train_node_emb, a.pretrain_emb)
+        if self.emb is not None:
+            self.emb = self.emb.to(self.device)
+            reset_input_layer(self.emb)
+        self.encoder = create_encoder_layer(input_dim, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout, a.encoder).to(self.device)
+        if a.predictor.upper() == 'MLP':
+            self.predictor = MLPPredictor(a.gnn_hidden_channels, a.mlp_hidden_channels, 1, a.mlp_num_layers, a.dropout).to(self.device)
+        else:
+            self.predictor = create_predictor_layer(a.mlp_hidden_channels, a.mlp_num_layers, a.dropout, a.predictor).to(self.device)
+        params = (list(self.emb.parameters()) if self.emb is not None else []) + list(self.encoder.parameters()) + list(self.predictor.parameters())
+        self.optimizer = cb_optim.Adam(params, lr=a.lr, weight_decay=self.weight_decay)
+
+    def linkpred_encoder_embeddings(self):
+        from .Link_prediction_model import create_input_feat
+        return self.encoder(create_input_feat(self.emb, self.data.x, self.args.use_node_feats), self.enc_graph)
+
+    def training_loss_linkpred_encoder(self):
+        """Forward + objective of BaseModel.train's step (model.py:147-157) on the encoder's embeddings.  Returns the 0-dim loss."""
+        from .Link_prediction_model import calculate_loss
+        h = self.linkpred_encoder_embeddings()
+        pos, neg = self.gen_linkpred_edge_index('train')
+        return calculate_loss(self.args.loss_func, self.predictor.score_pairs(h, pos), self.predictor.score_pairs(h, neg), int(self.args.num_neg))
+
+    def run_trainSet_linkpred_encoder(self):
+        a = self.args
+        self.encoder.train()
+        self.predictor.train()
+        loss = self.training_loss_linkpred_encoder()
+        self.optimizer.zero_grad()
+        loss.backward()
+        if a.grad_clip_norm >= 0:      # (model.py:160-162: encoder and predictor separately; the embedding is not clipped)
+            torch.nn.utils.clip_grad_norm_(self.encoder.parameters(), a.grad_clip_norm)
+            if list(self.predictor.parameters()):
+                torch.nn.utils.clip_grad_norm_(self.predictor.parameters(), a.grad_clip_norm)
+        self.optimizer.step()
+        value = self._checked(loss.item())
+        self.link_sampler().check()
+        ops.pair_check()
+        return value
+
+    def evaluate_linkpred_encoder(self, mode='test'):
+        """{'Hits@20', 'Hits@50', 'Hits@100', 'AUC'} of the eval-mode encoder + predictor on a fresh `mode` sample (as evaluate_linkpred)."""
+        if mode not in ('train', 'test'):
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
+        self.encoder.eval()
+        self.predictor.eval()
+        with torch.no_grad():
+            h = self.linkpred_encoder_embeddings()
+            pos, neg = self.gen_linkpred_edge_index(mode)
+            ps, ns = self.predictor.score_pairs(h, pos).reshape(-1), self.predictor.score_pairs(h, neg).reshape(-1)
+        self.link_sampler().check()
+        ops.pair_check()
+        out = ops.hits_at_k(ps, ns, (20, 50, 100))
+        out['AUC'] = ops.auc(ps, ns)
+        return out
+
+    def train_linkpred_encoder(self):
+        """--epochs steps of run_trainSet_linkpred_encoder, then evaluate_linkpred_encoder('test').  Eager steps only.  Returns
+        (losses [epochs], metrics of the last evaluation)."""
+        self.setup_linkpred_encoder()
+        losses = []
+        for epoch in range(self.epochs):
+            self.epoch = epoch
+            losses.append(self.run_trainSet_linkpred_encoder())
+            if epoch % 20 == 0:
+                print(f'Ep{epoch:03d}, {self.args.loss_func} = {losses[-1]:.5f}')
+        metrics = self.evaluate_linkpred_encoder('test')
+        save_model(self.encoder, join(self.modeldir, f'linkpred-encoder-{self.args.encoder}'))
+        return np.array(losses), metrics
+
     @staticmethod
     def _checked(value):
         """The loss has just been read (host synchronisation): a device-side error recorded by a kernel of this step — a tile hand-over

@@ -76,6 +76,12 @@ class Tuning:
     # same numbers either way (bit for bit for the MLP without dropout).  S = 262 144 pairs, D = 256, profiles/linkpred.md
     score_pairs_fused: bool = True
 
+    # ---- encoder layers of the link-prediction experiment (ops.sage_layer, cb_sage.hip) -----------------------------------------------------------
+    # a 256 -> 256 layer of SAGEEncoder / WSAGEEncoder / GCNEncoder runs as ONE kernel (aggregation into an on-chip tile, [agg | x] @ [W_n ; W_s] on the
+    # matrix cores from there) or composed of graph.spmm and cb_gemm_nn_f32 on the materialised [agg | x].  Same bits either way.  On because the one
+    # kernel is not slower in either direction at the S-arxiv and the S-products shape: 0.60 - 0.82 x forward, 0.77 - 0.93 x backward (profiles/sage.md)
+    sage_fused: bool = True
+
     # ---- adjacency power on the device (ops.spgemm_csr / ops.SparsePower.from_adjacency, cb_spgemm.hip) -------------------------------------
     # products one chunk of the sparse x sparse product expands at most (a single row with more gets a chunk of its own).  A MEMORY bound, not a
     # measured break-even: 24 B of workspace per product, 1.5 GiB at 2^26, about 2 GB with the chunk's compact result beside it; the result's

@@ -928,6 +928,31 @@ int cb_rank_loss_fwd_f32(int32_t kind, const float* pos, int64_t P, const float*
 int cb_rank_loss_bwd_f32(int32_t kind, const float* pos, int64_t P, const float* neg, int64_t k, const float* weight, const float* g, float* dpos,
                          float* dneg, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * One layer of the link-prediction encoders (Link_prediction_model/layer.py:8-35: SAGEConv with mean aggregation, GraphConv with add,
+ * GCNConv(normalize=False)) in one launch; cb_sage.hip.  Widths 256 -> 256, fp32 rows, 16-byte aligned, ld >= 256 and a multiple of 4:
+ *     agg[v, :] = row_scale[v] * sum_{j in row v} col_scale[col[j]] * h[col[j], :]            (row_scale / col_scale may be NULL)
+ *     out[v, :] = epi([agg[v, :] | self[v, :]] @ B + bias)                                    (self == NULL: out = epi(agg @ B + bias), B 256 x 256)
+ *     epi       = identity | ReLU (relu) | ReLU then dropout_p with the keep-mask of cb_dropout_f32 for (seed, seed_dev, flat index (row0 + v) * 256 + column)
+ * The sums are cb_spmm_csr_f32's (rows reduced in CSR order by one wavefront, hub rows by its hub kernels before the layer kernel), the product is
+ * cb_gemm_nn_f32's on the materialised [agg | self] with the stacked B (K = 512, its limb products and K order): the same bits as the two calls.
+ * Forward: by-dst CSR, h = self = X, row_scale = 1 / indeg (SAGE) or NULL, B = [W_n^T ; W_s^T], agg_out NULL.
+ * Backward: by-src CSR, h = self = G, col_scale = 1 / indeg (SAGE) or NULL, B = [W_n ; W_s], agg_out = R = A_s^T G (the weight gradient R^T X reads it).
+ * agg_out [N, ld_agg] (may be NULL when the plan has no hub rows): receives agg; with agg_hubs_only != 0 only the hub rows are written (they reach
+ * the kernel's tile through memory) and the rest of the buffer is left untouched.
+ * image: B split once into bf16 limbs in MFMA fragment order by cb_sage_image_f32 — W_n [256, ld_n] and W_s [256, ld_s] (NULL: 256 x 256 image) as
+ * B = [W_n ; W_s] (transpose = 0) or [W_n^T ; W_s^T] (transpose = 1); cb_sage_image_bytes(has_self) bytes, 16-byte aligned.
+ * cb_sage_layer_supported: 1 where the kernel exists (d_in == d_out == 256, fp32, alignment as above), else 0 — the caller then composes
+ * cb_spmm_csr_f32 and cb_gemm_nn_f32; an unsupported direct call returns CB_E_INVALID.  No atomics, no device error word, deterministic.
+ * ---------------------------------------------------------------------------------- */
+size_t cb_sage_image_bytes(int has_self);
+int cb_sage_image_f32(const float* W_n, int64_t ld_n, const float* W_s, int64_t ld_s, int transpose, void* image, size_t image_bytes, void* stream);
+int cb_sage_layer_supported(int64_t d_in, int64_t d_out, int32_t h_bf16, const void* h, int64_t ld_h, const float* self, int64_t ld_self,
+                            const float* agg_out, int64_t ld_agg, const float* out, int64_t ld_out);
+int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t ld_h, const float* self, int64_t ld_self, const float* col_scale,
+                      const float* row_scale, const void* image, const float* bias, int relu, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                      int64_t row0, float* agg_out, int64_t ld_agg, int32_t agg_hubs_only, float* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
