@@ -11,15 +11,14 @@
 //   negatives  slot s writes (u, v) to column 2 s and (v, u) to column 2 s + 1.  train: u, v from the ascending list of train nodes; test: from all
 //              nodes, rejected if both are train nodes.  Rejected too: u == v, u in row v, v in row u.  A slot without a pair after
 //              CB_LINKP_MAX_TRIES tries writes -1 to its four cells and adds one to an int32 counter (integer atomic: order-independent).
-//   loss       score_e = <emb[h_e], emb[t_e]> (fp32, one wavefront per edge, fixed-shape reduction); one block finishes
+//   loss       score_e = <emb[h_e], emb[t_e]> over pos | neg: k_pair_dot (cb_pair_core.h); one block finishes
 //              loss = mean max(s, 0) - s y + log1p(exp(-|s|)) and mrr = mean 1 / (1 + #{negatives of i's group above pos_i}) in float64, rounded once.
-//   backward   ds_e = g (sigmoid(s_e) - y_e) / (P + Nn); dEmb[h_e] += ds_e emb[t_e], dEmb[t_e] += ds_e emb[h_e] without atomics: the 2 (P + Nn)
-//              contributions are sorted by destination (cb::sort_u64, stable: ascending contribution number inside a node), the wavefront at the
-//              head of a node's run adds the run in that order (float64, rounded once) and writes the row; all other rows are zero-filled before.
+//   backward   ds_e = g (sigmoid(s_e) - y_e) / (P + Nn); dEmb[h_e] += ds_e emb[t_e], dEmb[t_e] += ds_e emb[h_e] without atomics: the sorted
+//              inverted-index scatter of cb_pair_core.h (pair_scatter) with the BCE coefficient, formed in float64 where it is used.
 // No float atomics, no host synchronisation inside an entry, two calls with the same inputs give the same bits.
 #include "cb_common.h"
+#include "cb_pair_core.h"
 #include "cb_philox.h"
-#include "cb_sort.h"
 
 namespace cb {
 
@@ -143,57 +142,13 @@ __global__ void __launch_bounds__(256) k_linkp_negatives(const int32_t* __restri
   if (u < 0) atomicAdd(n_failed, 1);
 }
 
-// ---- scores ---------------------------------------------------------------------------------------------------------------------------
-// edge e < P: (pos[e], pos[P + e]); e >= P: (neg[e - P], neg[Nn + e - P]).  false for an endpoint outside [0, N) (never used as an index).
-__device__ __forceinline__ bool lp_edge(const int32_t* __restrict__ pos, int64_t P, const int32_t* __restrict__ neg, int64_t Nn, int64_t N, int64_t e,
-                                        int& h, int& t) {
-  if (e < P) {
-    h = pos[e];
-    t = pos[P + e];
-  } else {
-    h = neg[e - P];
-    t = neg[Nn + e - P];
-  }
-  return h >= 0 && h < N && t >= 0 && t < N;
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_linkp_scores(const float* __restrict__ emb, int64_t ld, int64_t N, int D, const int32_t* __restrict__ pos,
-                                                      int64_t P, const int32_t* __restrict__ neg, int64_t Nn, float* __restrict__ scores) {
-  const int lane = threadIdx.x & 63;
-  const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (e >= P + Nn) return;
-  int h, t;
-  if (!lp_edge(pos, P, neg, Nn, N, e, h, t)) {      // (wave-uniform)
-    if (lane == 0) scores[e] = __int_as_float(0x7FC00000);
-    return;
-  }
-  const float* a = emb + (int64_t)h * ld;
-  const float* b = emb + (int64_t)t * ld;
-  float s = 0.f;
-  if (VEC) {
-    for (int c = 4 * lane; c < D; c += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(a + c), y = *reinterpret_cast<const float4*>(b + c);
-      s = fmaf(x.x, y.x, s);
-      s = fmaf(x.y, y.y, s);
-      s = fmaf(x.z, y.z, s);
-      s = fmaf(x.w, y.w, s);
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) s = fmaf(a[c], b[c], s);
-  }
-  s = wave_sum(s);
-  if (lane == 0) scores[e] = s;
-}
-
+// ---- loss ------------------------------------------------------------------------------------------------------------------------------
 // One block.  loss (may be NULL) = mean over P + Nn of the stable BCE-with-logits term, labels 1 for the P positives; mrr with k = Nn / P negatives
-// per positive (the last Nn - k P are dropped), ties counting for the positive; status (may be NULL) = number of edges with an endpoint outside
-// [0, N).  Thread-strided float64 partial sums, then a halving tree over the 256 threads: one fixed order.
-__global__ void __launch_bounds__(256) k_linkp_finish(const float* __restrict__ ps, int64_t P, const float* __restrict__ ns, int64_t Nn,
-                                                      const int32_t* __restrict__ pos, const int32_t* __restrict__ neg, int64_t N,
-                                                      float* __restrict__ loss, float* __restrict__ mrr, int32_t* __restrict__ status) {
-  __shared__ double s_loss[256], s_rr[256];
-  __shared__ int s_bad[256];
+// per positive (the last Nn - k P are dropped), ties counting for the positive; status (may be NULL) = number of pairs of src with an endpoint
+// outside [0, N) (a count below 2^31 is exact in float64).  Thread-strided float64 partial sums, then block_tree_f64: one fixed order.
+__global__ void __launch_bounds__(256) k_linkp_finish(const float* __restrict__ ps, int64_t P, const float* __restrict__ ns, int64_t Nn, PairSource<true> src,
+                                                      int64_t N, float* __restrict__ loss, float* __restrict__ mrr, int32_t* __restrict__ status) {
+  __shared__ double sm[3][256];     // loss, reciprocal ranks, unusable pairs
   const int t = threadIdx.x;
   const int64_t S = P + Nn, k = Nn / P;
   double sl = 0.0, sr = 0.0;
@@ -205,8 +160,8 @@ __global__ void __launch_bounds__(256) k_linkp_finish(const float* __restrict__ 
     }
   if (status)
     for (int64_t e = t; e < S; e += 256) {
-      int h, tt;
-      bad += lp_edge(pos, P, neg, Nn, N, e, h, tt) ? 0 : 1;
+      int u, v;
+      bad += src.get(e, N, u, v) ? 0 : 1;
     }
   for (int64_t i = t; i < P; i += 256) {
     const float p = ps[i];
@@ -214,82 +169,16 @@ __global__ void __launch_bounds__(256) k_linkp_finish(const float* __restrict__ 
     for (int64_t j = i * k; j < (i + 1) * k; ++j) rank += ns[j] > p ? 1 : 0;
     sr += 1.0 / (double)rank;
   }
-  s_loss[t] = sl;
-  s_rr[t] = sr;
-  s_bad[t] = bad;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) {
-      s_loss[t] += s_loss[t + off];
-      s_rr[t] += s_rr[t + off];
-      s_bad[t] += s_bad[t + off];
-    }
-    __syncthreads();
-  }
+  sm[0][t] = sl;
+  sm[1][t] = sr;
+  sm[2][t] = (double)bad;
+  block_tree_f64(sm, t);
   if (t == 0) {
-    if (loss) loss[0] = (float)(s_loss[0] / (double)S);
-    mrr[0] = (float)(s_rr[0] / (double)P);
-    if (status) status[0] = s_bad[0];
+    if (loss) loss[0] = (float)(sm[0][0] / (double)S);
+    mrr[0] = (float)(sm[1][0] / (double)P);
+    if (status) status[0] = (int32_t)sm[2][0];
   }
 }
-
-// ---- backward -------------------------------------------------------------------------------------------------------------------------
-// contribution c = 2 e + side goes to node (side ? t_e : h_e); key = c << 32 | node, node = N for an edge that is not usable (sorted last, skipped)
-__global__ void __launch_bounds__(256) k_linkp_keys(const int32_t* __restrict__ pos, int64_t P, const int32_t* __restrict__ neg, int64_t Nn, int64_t N,
-                                                    uint64_t* __restrict__ keys) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= 2 * (P + Nn)) return;
-  int h, t;
-  const bool ok = lp_edge(pos, P, neg, Nn, N, c >> 1, h, t);
-  const uint64_t node = ok ? (uint64_t)((c & 1) ? t : h) : (uint64_t)N;
-  keys[c] = ((uint64_t)c << 32) | node;
-}
-
-// One wavefront per sorted position; the one at the head of a node's run owns the node's row of dEmb.  Columns in chunks of 256 (four per lane);
-// wider rows walk the run once per chunk.
-__global__ void __launch_bounds__(256) k_linkp_bwd_rows(const float* __restrict__ emb, int64_t ld, int64_t N, int D, const int32_t* __restrict__ pos,
-                                                        int64_t P, const int32_t* __restrict__ neg, int64_t Nn, const float* __restrict__ scores,
-                                                        const float* __restrict__ g, const uint64_t* __restrict__ keys, float* __restrict__ demb,
-                                                        int64_t ldd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_keys = 2 * (P + Nn);
-  if (i >= n_keys) return;
-  const uint32_t node = (uint32_t)keys[i];
-  if (node >= (uint32_t)N) return;
-  if (i > 0 && (uint32_t)keys[i - 1] == node) return;      // not the head of its run
-  const double scale = (double)g[0] / (double)(P + Nn);
-  for (int c0 = 0; c0 < D; c0 += 256) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t j = i; j < n_keys; ++j) {
-      const uint64_t key = keys[j];      // (wave-uniform)
-      if ((uint32_t)key != node) break;
-      const int64_t c = (int64_t)(key >> 32), e = c >> 1;
-      int h, t;
-      lp_edge(pos, P, neg, Nn, N, e, h, t);      // (usable: its node is < N)
-      const float* other = emb + (int64_t)((c & 1) ? h : t) * ld;
-      const double s = (double)scores[e];
-      const double ds = scale * (1.0 / (1.0 + exp(-s)) - (e < P ? 1.0 : 0.0));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int cc = c0 + lane + 64 * q;
-        if (cc < D) acc[q] = fma(ds, (double)other[cc], acc[q]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int cc = c0 + lane + 64 * q;
-      if (cc < D) demb[(int64_t)node * ldd + cc] = (float)acc[q];
-    }
-  }
-}
-
-static inline int lp_bits(int64_t n) {
-  int b = 0;
-  while (((int64_t)1 << b) < n) ++b;
-  return b;
-}
-
-static inline size_t lp_keys_bytes(int64_t S) { return align_up((size_t)(2 * S) * sizeof(uint64_t), 256); }
 
 }  // namespace cb
 
@@ -339,65 +228,40 @@ extern "C" int cb_linkp_negatives_i32(const cb_csr_view* g, const uint8_t* mask,
   return CB_OK;
 }
 
-#define LP_CHECK_SIZES(name)                                                                                                           \
-  CB_CHECK_ARG(N > 0 && D > 0 && ld >= D && P >= 1 && Nn >= 0, CB_E_INVALID, name ": bad size (N > 0, D > 0, ld >= D, P >= 1, Nn >= 0 required)"); \
-  CB_CHECK_ARG(N < INT32_MAX && D < (1 << 24) && P + Nn < INT32_MAX / 2, CB_E_RANGE, name ": size out of range")
-
 extern "C" int cb_linkp_mrr_f32(const float* pos_score, int64_t P, const float* neg_score, int64_t Nn, float* mrr, void* stream) {
   CB_CHECK_ARG(P >= 1 && Nn >= 0, CB_E_INVALID, "cb_linkp_mrr_f32: P >= 1 and Nn >= 0 required");
   CB_CHECK_ARG(P + Nn < INT32_MAX / 2, CB_E_RANGE, "cb_linkp_mrr_f32: size out of range");
   CB_CHECK_ARG(pos_score && (neg_score || Nn == 0) && mrr, CB_E_INVALID, "cb_linkp_mrr_f32: null pointer");
-  hipLaunchKernelGGL(k_linkp_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, pos_score, P, neg_score, Nn, (const int32_t*)nullptr,
-                     (const int32_t*)nullptr, (int64_t)0, (float*)nullptr, mrr, (int32_t*)nullptr);
+  hipLaunchKernelGGL(k_linkp_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, pos_score, P, neg_score, Nn, PairSource<true>{nullptr, 0, nullptr, 0},
+                     (int64_t)0, (float*)nullptr, mrr, (int32_t*)nullptr);
   CB_LAUNCH_CHECK();
   return CB_OK;
 }
 
+// the scores over pos | neg are k_pair_dot's; the unusable pairs are counted by the finisher, which reads every pair anyway (no atomic)
 extern "C" int cb_linkp_loss_fwd_f32(const float* emb, int64_t ld, int64_t N, int64_t D, const int32_t* pos, int64_t P, const int32_t* neg, int64_t Nn,
                                      float* scores, float* loss, float* mrr, int32_t* status, void* stream) {
-  LP_CHECK_SIZES("cb_linkp_loss_fwd_f32");
+  CB_PAIR_CHECK_SIZES("cb_linkp_loss_fwd_f32", P + Nn, P >= 1 && Nn >= 0, "P >= 1, Nn >= 0");
   CB_CHECK_ARG(emb && pos && (neg || Nn == 0) && scores && loss && mrr && status, CB_E_INVALID, "cb_linkp_loss_fwd_f32: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nb = (unsigned)blocks_for(P + Nn, 4);
-  if (D % 4 == 0 && ld % 4 == 0 && aligned16(emb))
-    hipLaunchKernelGGL(k_linkp_scores<true>, dim3(nb), dim3(256), 0, st, emb, ld, N, (int)D, pos, P, neg, Nn, scores);
-  else
-    hipLaunchKernelGGL(k_linkp_scores<false>, dim3(nb), dim3(256), 0, st, emb, ld, N, (int)D, pos, P, neg, Nn, scores);
-  CB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_linkp_finish, dim3(1), dim3(256), 0, st, (const float*)scores, P, (const float*)(scores + P), Nn, pos, neg, N, loss, mrr, status);
+  const PairSource<true> src{pos, P, neg, Nn};
+  const int rc = launch_pair_dot(emb, ld, N, D, src, scores, nullptr, st);
+  if (rc != CB_OK) return rc;
+  hipLaunchKernelGGL(k_linkp_finish, dim3(1), dim3(256), 0, st, (const float*)scores, P, (const float*)(scores + P), Nn, src, N, loss, mrr, status);
   CB_LAUNCH_CHECK();
   return CB_OK;
 }
 
 extern "C" size_t cb_linkp_bwd_workspace_bytes(int64_t P, int64_t Nn) {
   if (P < 0 || Nn < 0 || P + Nn <= 0) return 0;
-  const int64_t S = P + Nn;
-  return 2 * lp_keys_bytes(S) + align_up(sort_u64_temp_bytes(2 * S), 256);
+  return pair_scatter_ws_bytes(P + Nn);
 }
 
 extern "C" int cb_linkp_loss_bwd_f32(const float* emb, int64_t ld, int64_t N, int64_t D, const int32_t* pos, int64_t P, const int32_t* neg, int64_t Nn,
                                      const float* scores, const float* g, float* demb, int64_t ldd, void* ws, size_t ws_bytes, void* stream) {
-  LP_CHECK_SIZES("cb_linkp_loss_bwd_f32");
+  CB_PAIR_CHECK_SIZES("cb_linkp_loss_bwd_f32", P + Nn, P >= 1 && Nn >= 0, "P >= 1, Nn >= 0");
   CB_CHECK_ARG(ldd >= D, CB_E_INVALID, "cb_linkp_loss_bwd_f32: ldd >= D required");
   CB_CHECK_ARG(emb && pos && (neg || Nn == 0) && scores && g && demb, CB_E_INVALID, "cb_linkp_loss_bwd_f32: null pointer");
   CB_CHECK_ARG(ws && ws_bytes >= cb_linkp_bwd_workspace_bytes(P, Nn), CB_E_WORKSPACE, "cb_linkp_loss_bwd_f32: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t S = P + Nn;
-  char* base = (char*)ws;
-  uint64_t* keys_in = (uint64_t*)base;
-  uint64_t* keys_out = (uint64_t*)(base + lp_keys_bytes(S));
-  void* temp = base + 2 * lp_keys_bytes(S);
-  if (ldd == D) {
-    CB_HIP(hipMemsetAsync(demb, 0, (size_t)N * (size_t)D * sizeof(float), st));
-  } else {
-    CB_HIP(hipMemset2DAsync(demb, (size_t)ldd * sizeof(float), 0, (size_t)D * sizeof(float), (size_t)N, st));
-  }
-  hipLaunchKernelGGL(k_linkp_keys, dim3((unsigned)blocks_for(2 * S, 256)), dim3(256), 0, st, pos, P, neg, Nn, N, keys_in);
-  CB_LAUNCH_CHECK();
-  const int rc = sort_u64(temp, ws_bytes - 2 * lp_keys_bytes(S), keys_in, keys_out, 2 * S, lp_bits(N + 1), st);
-  if (rc != CB_OK) return rc;
-  hipLaunchKernelGGL(k_linkp_bwd_rows, dim3((unsigned)blocks_for(2 * S, 4)), dim3(256), 0, st, emb, ld, N, (int)D, pos, P, neg, Nn, scores, g,
-                     (const uint64_t*)keys_out, demb, ldd);
-  CB_LAUNCH_CHECK();
-  return CB_OK;
+  return pair_scatter(emb, ld, N, D, PairSource<true>{pos, P, neg, Nn}, CoefBce{scores, g, P, P + Nn}, demb, ldd, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -5,10 +5,9 @@
 //               (PairRowOperand, cb_limb_core.h).  The two gathered [S, K] matrices and their product are never written.  K loop, epilogue and
 //               tile order are those of k_gemm_nn_l3 (cb_gemm_limb.hip), and every product is rounded to fp32 once before the limb split, so the
 //               result has the bits of cb_gemm_nn_f32 / cb_gemm_nn_drop2_f32 on the materialised product.
-//   pair dot    s_e = <h[u_e], h[v_e]>: k_linkp_scores (cb_linkp.hip) without the BCE finisher.
+//   pair dot    s_e = <h[u_e], h[v_e]>: k_pair_dot (cb_pair_core.h), the kernel behind the edge-wise loss's scores, with the status count.
 //   scatter     dH[n] = sum of c_e * h[v_e] into row u_e and c_e * h[u_e] into row v_e, c_e a scalar (dot predictor) or a row (the MLP predictor's
-//               dX) per pair; the method of cb_linkp_loss_bwd_f32: contributions sorted by destination (cb::sort_u64, stable), the wavefront at
-//               the head of a node's run adds the run in ascending contribution number in float64 and writes the row once.
+//               dX) per pair: pair_scatter (cb_pair_core.h), the sorted inverted index that cb_linkp_loss_bwd_f32 runs with its BCE coefficient.
 //   rank loss   auc_loss / adaptive_auc_loss / log_rank_loss / ce_loss / info_nce_loss over pos [P] and neg [P, k]: every term in float64 from the
 //               fp32 scores by the reference's formula as written (its + 1e-15 included), thread-strided float64 partial sums, a halving tree per
 //               block and one over the blocks: one fixed order, rounded once.  The backward writes dpos [P] and dneg [P, k] from a
@@ -22,15 +21,9 @@
 #include "cb_gemm_core.h"
 #include "cb_gemm_limb.h"
 #include "cb_limb_core.h"
-#include "cb_sort.h"
+#include "cb_pair_core.h"
 
 namespace cb {
-
-__device__ __forceinline__ bool pp_pair(const int32_t* __restrict__ pairs, int64_t S, int64_t N, int64_t e, int& u, int& v) {
-  u = pairs[e];
-  v = pairs[S + e];
-  return u >= 0 && u < N && v >= 0 && v < N;
-}
 
 // ---- pair GEMM ------------------------------------------------------------------------------------------------------------------------
 // k_gemm_nn_l3 with PairRowOperand as its A operand; register prefetch depth 1 (the operand holds the second row's quads).
@@ -124,100 +117,11 @@ __global__ void __launch_bounds__(256) k_pair_nan_rows(const int32_t* __restrict
   const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (m >= S) return;
   int u, v;
-  if (pp_pair(pairs, S, N, m, u, v)) return;
+  if (PairSource<false>{pairs, S, nullptr, 0}.get(m, N, u, v)) return;
   for (int n = 0; n < Nout; ++n) C2[m * ldc2 + n] = __int_as_float(0x7FC00000);
 }
 
 static inline bool pair_limb3_on() { return getenv("CB_GEMM_PLAIN_F32") == nullptr; }      // (the switch of cb_gemm.hip)
-
-// ---- pair dot -------------------------------------------------------------------------------------------------------------------------
-template <bool VEC>
-__global__ void __launch_bounds__(256) k_pair_dot(const float* __restrict__ h, int64_t ld, int64_t N, int D, const int32_t* __restrict__ pairs, int64_t S,
-                                                  float* __restrict__ scores, int32_t* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (e >= S) return;
-  int u, v;
-  if (!pp_pair(pairs, S, N, e, u, v)) {      // (wave-uniform)
-    if (lane == 0) {
-      scores[e] = __int_as_float(0x7FC00000);
-      atomicAdd(status, 1);
-    }
-    return;
-  }
-  const float* a = h + (int64_t)u * ld;
-  const float* b = h + (int64_t)v * ld;
-  float s = 0.f;
-  if (VEC) {
-    for (int c = 4 * lane; c < D; c += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(a + c), y = *reinterpret_cast<const float4*>(b + c);
-      s = fmaf(x.x, y.x, s);
-      s = fmaf(x.y, y.y, s);
-      s = fmaf(x.z, y.z, s);
-      s = fmaf(x.w, y.w, s);
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) s = fmaf(a[c], b[c], s);
-  }
-  s = wave_sum(s);
-  if (lane == 0) scores[e] = s;
-}
-
-// ---- scatter --------------------------------------------------------------------------------------------------------------------------
-// contribution c = 2 e + side goes to node (side ? v_e : u_e); key = c << 32 | node, node = N for an unusable pair (sorted last, skipped)
-__global__ void __launch_bounds__(256) k_pair_keys(const int32_t* __restrict__ pairs, int64_t S, int64_t N, uint64_t* __restrict__ keys) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= 2 * S) return;
-  int u, v;
-  const bool ok = pp_pair(pairs, S, N, c >> 1, u, v);
-  const uint64_t node = ok ? (uint64_t)((c & 1) ? v : u) : (uint64_t)N;
-  keys[c] = ((uint64_t)c << 32) | node;
-}
-
-// One wavefront per sorted position; the one at the head of a node's run owns the node's row of dH.  Columns in chunks of 256 (four per lane); wider
-// rows walk the run once per chunk.  ROWS: coef [S, ldcoef] holds a row per pair, else coef [S] a scalar per pair.
-template <bool ROWS>
-__global__ void __launch_bounds__(256) k_pair_scatter_rows(const float* __restrict__ h, int64_t ld, int64_t N, int D, const int32_t* __restrict__ pairs,
-                                                           int64_t S, const float* __restrict__ coef, int64_t ldcoef,
-                                                           const uint64_t* __restrict__ keys, float* __restrict__ dh, int64_t ldd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, n_keys = 2 * S;
-  if (i >= n_keys) return;
-  const uint32_t node = (uint32_t)keys[i];
-  if (node >= (uint32_t)N) return;
-  if (i > 0 && (uint32_t)keys[i - 1] == node) return;      // not the head of its run
-  for (int c0 = 0; c0 < D; c0 += 256) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t j = i; j < n_keys; ++j) {
-      const uint64_t key = keys[j];      // (wave-uniform)
-      if ((uint32_t)key != node) break;
-      const int64_t c = (int64_t)(key >> 32), e = c >> 1;      // (e < S: the keys are a permutation of those k_pair_keys wrote)
-      int u, v;
-      pp_pair(pairs, S, N, e, u, v);      // (usable: its node is < N)
-      const float* other = h + (int64_t)((c & 1) ? u : v) * ld;
-      const float* cr = ROWS ? coef + e * ldcoef : coef + e;
-      const double cs = ROWS ? 0.0 : (double)cr[0];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int cc = c0 + lane + 64 * q;
-        if (cc < D) acc[q] = fma(ROWS ? (double)cr[cc] : cs, (double)other[cc], acc[q]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int cc = c0 + lane + 64 * q;
-      if (cc < D) dh[(int64_t)node * ldd + cc] = (float)acc[q];
-    }
-  }
-}
-
-static inline int pp_bits(int64_t n) {
-  int b = 0;
-  while (((int64_t)1 << b) < n) ++b;
-  return b;
-}
-
-static inline size_t pp_keys_bytes(int64_t S) { return align_up((size_t)(2 * S) * sizeof(uint64_t), 256); }
 
 // ---- ranking losses -------------------------------------------------------------------------------------------------------------------
 constexpr int RL_MAX_BLOCKS = 256;
@@ -251,21 +155,10 @@ __device__ __forceinline__ void rl_row_terms(int kind, const float* __restrict__
   }
 }
 
-__device__ __forceinline__ void rl_block_tree(double* __restrict__ sa, double* __restrict__ sb, int t) {
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) {
-      sa[t] += sa[t + off];
-      sb[t] += sb[t + off];
-    }
-    __syncthreads();
-  }
-}
-
 // block b, thread t: rows b * 256 + t, + gridDim.x * 256, ...; part [2][RL_MAX_BLOCKS]
 __global__ void __launch_bounds__(256) k_rank_loss_partial(int kind, const float* __restrict__ pos, int64_t P, const float* __restrict__ neg, int64_t k,
                                                            const float* __restrict__ weight, double* __restrict__ part) {
-  __shared__ double sa[256], sb[256];
+  __shared__ double s[2][256];
   const int t = threadIdx.x;
   double a = 0.0, b = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < P; i += (int64_t)gridDim.x * 256) {
@@ -274,28 +167,28 @@ __global__ void __launch_bounds__(256) k_rank_loss_partial(int kind, const float
     a += ra;
     b += rb;
   }
-  sa[t] = a;
-  sb[t] = b;
-  rl_block_tree(sa, sb, t);
+  s[0][t] = a;
+  s[1][t] = b;
+  block_tree_f64(s, t);
   if (t == 0) {
-    part[blockIdx.x] = sa[0];
-    part[RL_MAX_BLOCKS + blockIdx.x] = sb[0];
+    part[blockIdx.x] = s[0][0];
+    part[RL_MAX_BLOCKS + blockIdx.x] = s[1][0];
   }
 }
 
 __global__ void __launch_bounds__(256) k_rank_loss_finish(int kind, int64_t P, int64_t k, const double* __restrict__ part, int nb, float* __restrict__ loss) {
-  __shared__ double sa[256], sb[256];
+  __shared__ double s[2][256];
   const int t = threadIdx.x;
-  sa[t] = t < nb ? part[t] : 0.0;
-  sb[t] = t < nb ? part[RL_MAX_BLOCKS + t] : 0.0;
-  rl_block_tree(sa, sb, t);
+  s[0][t] = t < nb ? part[t] : 0.0;
+  s[1][t] = t < nb ? part[RL_MAX_BLOCKS + t] : 0.0;
+  block_tree_f64(s, t);
   if (t == 0) {
-    const double dP = (double)P, dS = (double)P * (double)k;
+    const double dP = (double)P, dS = (double)P * (double)k, sa = s[0][0], sb = s[1][0];
     double r;
-    if (kind == CB_RANK_AUC || kind == CB_RANK_ADAPTIVE_AUC) r = sa[0];
-    else if (kind == CB_RANK_LOG_RANK) r = sa[0] / dS;
-    else if (kind == CB_RANK_CE) r = sa[0] / dP + sb[0] / dS;
-    else r = sa[0] / dP;
+    if (kind == CB_RANK_AUC || kind == CB_RANK_ADAPTIVE_AUC) r = sa;
+    else if (kind == CB_RANK_LOG_RANK) r = sa / dS;
+    else if (kind == CB_RANK_CE) r = sa / dP + sb / dS;
+    else r = sa / dP;
     loss[0] = (float)r;
   }
 }
@@ -347,10 +240,6 @@ __global__ void __launch_bounds__(256) k_rank_loss_bwd(int kind, const float* __
 
 using namespace cb;
 
-#define PP_CHECK_SIZES(name)                                                                                                    \
-  CB_CHECK_ARG(N > 0 && D > 0 && ld >= D && S >= 0, CB_E_INVALID, name ": bad size (N > 0, D > 0, ld >= D, S >= 0 required)"); \
-  CB_CHECK_ARG(N < INT32_MAX && D < (1 << 24) && S < INT32_MAX / 2, CB_E_RANGE, name ": size out of range")
-
 extern "C" int cb_pair_gemm_nn_supported(const float* h, int64_t ld, const float* B, int64_t ldb, int64_t Nout, int64_t K) {
   return pair_limb3_on() && h && B && Nout > 0 && ld >= K && ldb >= Nout && limb3_nn_eligible(h, ld, B, ldb, Nout, K) ? 1 : 0;
 }
@@ -387,54 +276,29 @@ extern "C" int cb_pair_gemm_nn_f32(const float* h, int64_t ld, int64_t N, const 
 
 extern "C" int cb_pair_dot_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* pairs, int64_t S, float* scores, int32_t* status,
                                void* stream) {
-  PP_CHECK_SIZES("cb_pair_dot_f32");
+  CB_PAIR_CHECK_SIZES("cb_pair_dot_f32", S, S >= 0, "S >= 0");
   CB_CHECK_ARG(status, CB_E_INVALID, "cb_pair_dot_f32: null pointer (status)");
   hipStream_t st = (hipStream_t)stream;
   CB_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
   if (S == 0) return CB_OK;
   CB_CHECK_ARG(h && pairs && scores, CB_E_INVALID, "cb_pair_dot_f32: null pointer");
-  const unsigned nb = (unsigned)blocks_for(S, 4);
-  if (D % 4 == 0 && ld % 4 == 0 && aligned16(h))
-    hipLaunchKernelGGL(k_pair_dot<true>, dim3(nb), dim3(256), 0, st, h, ld, N, (int)D, pairs, S, scores, status);
-  else
-    hipLaunchKernelGGL(k_pair_dot<false>, dim3(nb), dim3(256), 0, st, h, ld, N, (int)D, pairs, S, scores, status);
-  CB_LAUNCH_CHECK();
-  return CB_OK;
+  return launch_pair_dot(h, ld, N, D, PairSource<false>{pairs, S, nullptr, 0}, scores, status, st);
 }
 
 extern "C" size_t cb_pair_scatter_workspace_bytes(int64_t S) {
   if (S <= 0 || S >= INT32_MAX / 2) return 0;
-  return 2 * pp_keys_bytes(S) + align_up(sort_u64_temp_bytes(2 * S), 256);
+  return pair_scatter_ws_bytes(S);
 }
 
 extern "C" int cb_pair_scatter_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* pairs, int64_t S, const float* coef, int64_t ldcoef,
                                    float* dh, int64_t ldd, void* ws, size_t ws_bytes, void* stream) {
-  PP_CHECK_SIZES("cb_pair_scatter_f32");
+  CB_PAIR_CHECK_SIZES("cb_pair_scatter_f32", S, S >= 0, "S >= 0");
   CB_CHECK_ARG(ldd >= D && (ldcoef == 0 || ldcoef >= D), CB_E_INVALID, "cb_pair_scatter_f32: ldd >= D and ldcoef == 0 (a scalar per pair) or >= D required");
   CB_CHECK_ARG(h && dh && (S == 0 || (pairs && coef)), CB_E_INVALID, "cb_pair_scatter_f32: null pointer");
   CB_CHECK_ARG(S == 0 || (ws && ws_bytes >= cb_pair_scatter_workspace_bytes(S)), CB_E_WORKSPACE, "cb_pair_scatter_f32: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (ldd == D) {
-    CB_HIP(hipMemsetAsync(dh, 0, (size_t)N * (size_t)D * sizeof(float), st));
-  } else {
-    CB_HIP(hipMemset2DAsync(dh, (size_t)ldd * sizeof(float), 0, (size_t)D * sizeof(float), (size_t)N, st));
-  }
-  if (S == 0) return CB_OK;
-  char* base = (char*)ws;
-  uint64_t* keys_in = (uint64_t*)base;
-  uint64_t* keys_out = (uint64_t*)(base + pp_keys_bytes(S));
-  void* temp = base + 2 * pp_keys_bytes(S);
-  hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)blocks_for(2 * S, 256)), dim3(256), 0, st, pairs, S, N, keys_in);
-  CB_LAUNCH_CHECK();
-  const int rc = sort_u64(temp, ws_bytes - 2 * pp_keys_bytes(S), keys_in, keys_out, 2 * S, pp_bits(N + 1), st);
-  if (rc != CB_OK) return rc;
-  const unsigned nb = (unsigned)blocks_for(2 * S, 4);
-  if (ldcoef)
-    hipLaunchKernelGGL(k_pair_scatter_rows<true>, dim3(nb), dim3(256), 0, st, h, ld, N, (int)D, pairs, S, coef, ldcoef, (const uint64_t*)keys_out, dh, ldd);
-  else
-    hipLaunchKernelGGL(k_pair_scatter_rows<false>, dim3(nb), dim3(256), 0, st, h, ld, N, (int)D, pairs, S, coef, ldcoef, (const uint64_t*)keys_out, dh, ldd);
-  CB_LAUNCH_CHECK();
-  return CB_OK;
+  const PairSource<false> src{pairs, S, nullptr, 0};
+  if (ldcoef) return pair_scatter(h, ld, N, D, src, CoefRows{coef, ldcoef}, dh, ldd, ws, ws_bytes, (hipStream_t)stream);
+  return pair_scatter(h, ld, N, D, src, CoefScalar{coef}, dh, ldd, ws, ws_bytes, (hipStream_t)stream);
 }
 
 #define RL_CHECK(name)                                                                                                                      \

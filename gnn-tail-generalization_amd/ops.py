@@ -33,6 +33,8 @@ Encoders of the link-prediction experiment (Link_prediction_model/layer.py:19-75
 """
 import collections
 import ctypes
+import functools
+import operator
 import os
 
 import torch
@@ -1355,20 +1357,43 @@ class LinkSampler:
             raise RuntimeError(f'LinkSampler: {n} negative slot(s) found no non-edge in {int(self._lib.cb_linkp_max_tries())} tries (their columns hold -1)')
 
 
-def _linkp_pairs(who, t, device):
+def _pairs_arg(who, t, device, n='P'):
+    """The index pairs of every operator on pairs: an int32 / int64 [2, n] device tensor on `device`, handed back as contiguous int32.  who: the
+    caller and its argument ('pair_dot: pairs'), for the messages."""
     if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 2 or t.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f'linkp_loss_eva: {who} must be an int32 / int64 [2, n] tensor')
+        raise ValueError(f'{who} must be an int32 / int64 [2, {n}] tensor')
     _lib.require_device(t)
     if t.device != device:
-        raise ValueError(f'linkp_loss_eva: {who} lives on another device than the embeddings')
+        raise ValueError(f'{who} must live on {device}, the device of the embeddings or graph they index (got {t.device})')
     return _c(t.to(torch.int32))
+
+
+def _pair_rows(h):
+    """h with contiguous rows (a column slice of a wider matrix stays where it is: the kernels take its leading dimension)."""
+    return h if h.stride(1) == 1 and h.stride(0) >= h.shape[1] else h.contiguous()
+
+
+class _Ledger:
+    """Status words kept on their devices between two host reads.  add(word) folds a [1] tensor into the word of its device (no synchronisation);
+    drain() reads every device's word (a host synchronisation), forgets them all and returns their fold as a Python number, 0 if nothing was added."""
+
+    def __init__(self, fold=torch.add, host_fold=operator.add):
+        self._fold, self._host_fold, self._words = fold, host_fold, {}
+
+    def add(self, word):
+        have = self._words.get(word.device)
+        self._words[word.device] = word.clone() if have is None else self._fold(have, word)
+
+    def drain(self):
+        words, self._words = list(self._words.values()), {}
+        return functools.reduce(self._host_fold, (w.item() for w in words), 0)
 
 
 class _LinkpLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb, pos, neg):
         lib = _lib.load()
-        e = emb if emb.stride(1) == 1 and emb.stride(0) >= emb.shape[1] else emb.contiguous()
+        e = _pair_rows(emb)
         N, D = e.shape
         P, Nn = pos.shape[1], neg.shape[1]
         dev = e.device
@@ -1413,8 +1438,8 @@ def linkp_loss_eva(h_src, pos, neg, return_parts=False):
     _lib.require_device(h_src)
     if h_src.dim() != 2 or h_src.dtype != torch.float32 or h_src.shape[0] < 1 or h_src.shape[1] < 1:
         raise ValueError('linkp_loss_eva expects a float32 [N, D] embedding matrix')
-    pos = _linkp_pairs('pos', pos, h_src.device)
-    neg = _linkp_pairs('neg', neg, h_src.device)
+    pos = _pairs_arg('linkp_loss_eva: pos', pos, h_src.device)
+    neg = _pairs_arg('linkp_loss_eva: neg', neg, h_src.device, 'Nn')
     if pos.shape[1] < 1:
         raise ValueError('linkp_loss_eva: at least one positive pair is required (the MRR is a mean over the positives)')
     loss, mrr, scores, status = _LinkpLossFn.apply(h_src, pos, neg)
@@ -1443,14 +1468,7 @@ def cal_MRR(pos_score, neg_score):
 HEUR_KINDS = ('CN', 'AA')
 CN_EXACT_BELOW = float(2 ** 24)      # a CN score is an integer held in fp32
 
-_heur_pending = {}      # device -> [int32 [1] count of out-of-range pairs, fp32 [1] largest CN score] since the last pair_scores_check()
-
-
-def _heur_pairs(t):
-    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 2 or t.dtype not in (torch.int32, torch.int64):
-        raise ValueError('pair_scores: pairs must be an int32 / int64 [2, P] tensor')
-    _lib.require_device(t)
-    return t
+_heur_bad, _heur_top = _Ledger(), _Ledger(torch.fmax, max)      # out-of-range pairs / the largest CN score since the last pair_scores_check()
 
 
 def _out_view(graph):
@@ -1491,22 +1509,19 @@ def pair_scores(graph, pairs, kind='CN', weight=None, return_status=False, group
         raise ValueError("pair_scores: `weight` belongs to kind='AA' (CN counts common neighbours unweighted)")
     if group not in (None, 16, 64):
         raise ValueError('pair_scores: group is 16 or 64')
-    pairs = _heur_pairs(pairs)
-    if pairs.device != graph.device:
-        raise ValueError('pair_scores: pairs live on another device than the graph')
+    p32 = _pairs_arg('pair_scores: pairs', pairs, graph.device)
     if weight is not None:
         _lib.require_device(weight)
         if weight.dtype != torch.float64 or weight.dim() != 1 or weight.numel() != graph.N or weight.device != graph.device:
             raise ValueError(f'pair_scores: weight must be a float64 vector of {graph.N} nodes on the device of the graph')
         weight = _c(weight)
-    P = int(pairs.shape[1])
+    P = int(p32.shape[1])
     dev = graph.device
     score = torch.empty(P, dtype=torch.float32, device=dev)
     if P == 0:
         return (score, torch.zeros(1, dtype=torch.int32, device=dev)) if return_status else score
     lib = _lib.load()
     w = None if kind == 'CN' else (aa_weights(graph) if weight is None else weight)
-    p32 = _c(pairs.to(torch.int32))
     status = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         if group is None:
@@ -1515,12 +1530,9 @@ def pair_scores(graph, pairs, kind='CN', weight=None, return_status=False, group
             rc = lib.cb_heur_pair_scores_width_f32(ctypes.byref(_out_view(graph)), _lib.ptr(w), _lib.ptr(p32), P, group, _lib.ptr(score), _lib.ptr(status),
                                                    _lib.stream_ptr())
         _lib.check(rc, 'cb_heur_pair_scores_f32')
-    pend = _heur_pending.get(dev)
-    if pend is None:
-        pend = _heur_pending[dev] = [torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)]
-    pend[0] += status
+    _heur_bad.add(status)
     if kind == 'CN':
-        pend[1] = torch.fmax(pend[1], torch.nan_to_num(score, nan=0.0).max().reshape(1))
+        _heur_top.add(torch.nan_to_num(score, nan=0.0).max().reshape(1))
     return (score, status) if return_status else score
 
 
@@ -1528,12 +1540,7 @@ def pair_scores_check():
     """Reads the status words of the pair_scores() calls since the last check (a host synchronisation: call it where the scores are read anyway),
     clears them, and raises RuntimeError if a pair had an endpoint outside the graph (its score is NaN) or OverflowError if a CN score reached 2^24
     (fp32 no longer holds every integer there)."""
-    bad, top = 0, 0.0
-    for pend in _heur_pending.values():
-        bad += int(pend[0].item())
-        top = max(top, float(pend[1].item()))
-        pend[0].zero_()
-        pend[1].zero_()
+    bad, top = _heur_bad.drain(), float(_heur_top.drain())
     if bad:
         raise RuntimeError(f'pair_scores: {bad} pair(s) with an endpoint outside [0, N) (their scores are NaN)')
     if top >= CN_EXACT_BELOW:
@@ -1608,40 +1615,21 @@ def auc(pos, neg):
 # ---------------------------------------------------------------------------------------------
 RANK_KINDS = {'auc_loss': 0, 'adaptive_auc_loss': 1, 'log_rank_loss': 2, 'ce_loss': 3, 'info_nce_loss': 4}
 
-_pair_pending = {}      # device -> int32 [1] count of unusable pairs since the last pair_check()
+_pair_bad = _Ledger()      # unusable pairs since the last pair_check()
 
 
 def _pair_args(who, h, pairs):
-    _lib.require_device(h, pairs)
     if not torch.is_tensor(h) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[0] < 1 or h.shape[1] < 1:
         raise ValueError(f'{who} expects a float32 [N, D] embedding matrix')
-    if not torch.is_tensor(pairs) or pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f'{who}: pairs must be an int32 / int64 [2, S] tensor')
-    if pairs.device != h.device:
-        raise ValueError(f'{who}: pairs live on another device than the embeddings')
-    return _c(pairs.to(torch.int32))
-
-
-def _pair_rows(h):
-    """h with contiguous rows (a column slice of a wider matrix stays where it is: the kernels take its leading dimension)."""
-    return h if h.stride(1) == 1 and h.stride(0) >= h.shape[1] else h.contiguous()
-
-
-def _pair_note(status):
-    pend = _pair_pending.get(status.device)
-    if pend is None:
-        pend = _pair_pending[status.device] = torch.zeros(1, dtype=torch.int32, device=status.device)
-    pend += status
+    _lib.require_device(h)
+    return _pairs_arg(f'{who}: pairs', pairs, h.device, 'S')
 
 
 def pair_check():
     """Reads the status words of the pair_dot() / pair_linear() calls since the last check (a host synchronisation: call it where the loss is read
     anyway), clears them, and raises RuntimeError if a pair had an endpoint outside [0, N) — the -1 of a failed LinkSampler slot.  Its score, and
     any loss taken over it, is NaN.  Also reachable as pair_dot.check, pair_linear.check and rank_loss.check."""
-    bad = 0
-    for pend in _pair_pending.values():
-        bad += int(pend.item())
-        pend.zero_()
+    bad = _pair_bad.drain()
     if bad:
         raise RuntimeError(f'link predictor: {bad} pair(s) with an endpoint outside [0, N) (their scores are NaN)')
 
@@ -1695,7 +1683,7 @@ def pair_dot(h, pairs, return_status=False):
     caller reads the loss (return_status: also hand back the int32 [1] count of this call)."""
     pairs = _pair_args('pair_dot', h, pairs)
     scores, status = _PairDotFn.apply(h, pairs)
-    _pair_note(status)
+    _pair_bad.add(status)
     return (scores, status) if return_status else scores
 
 
@@ -1796,7 +1784,7 @@ def pair_linear(h, pairs, weight, bias=None, relu=False, p=0.0, seed=None, row0=
     if p > 0.0 and seed is None:
         seed = next_seed()
     y, status = _PairLinearFn.apply(h, pairs, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
-    _pair_note(status)
+    _pair_bad.add(status)
     return (y, status) if return_status else y
 
 

@@ -682,9 +682,12 @@ class trainer:
             self.setup_teacherGNN()
         pos, neg = self.gen_pn_edge_index(mode)
         g = self.graph()
-        ps, ns = ops.pair_scores(g, pos, kind), ops.pair_scores(g, neg, kind)
+        return self._link_metrics(ops.pair_scores(g, pos, kind), ops.pair_scores(g, neg, kind), ops.pair_scores_check)
+
+    def _link_metrics(self, ps, ns, scores_check):
+        """The scores are about to be read: the sampler's and the scorer's device checks raise here; then Hits@20 / 50 / 100 and the AUC."""
         self.link_sampler().check()
-        ops.pair_scores_check()
+        scores_check()
         out = ops.hits_at_k(ps, ns, (20, 50, 100))
         out['AUC'] = ops.auc(ps, ns)
         return out
@@ -742,45 +745,55 @@ class trainer:
     def training_loss_linkpred(self):
         """Forward + objective of BaseModel.train's step (model.py:147-157): a full teacher forward (res.commonEmb is read on sampled rows, so no
         loss_rows / rows_only promise), predictor.score_pairs on the sampled pairs, calculate_loss(--loss_func).  Returns the 0-dim loss."""
+        return self._linkpred_loss(self._teacher_embeddings)
+
+    def _teacher_embeddings(self):
+        return self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index).commonEmb
+
+    def _linkpred_loss(self, embeddings):
+        """calculate_loss(--loss_func) of the predictor's scores on a fresh train sample; device work in the order embeddings, sampler, scores."""
         from .Link_prediction_model import calculate_loss
-        res = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index)
+        h = embeddings()
         pos, neg = self.gen_linkpred_edge_index('train')
-        h = res.commonEmb
         return calculate_loss(self.args.loss_func, self.predictor.score_pairs(h, pos), self.predictor.score_pairs(h, neg), int(self.args.num_neg))
 
-    def run_trainSet_linkpred(self):
+    def _linkpred_step(self, embeddings, modules):
+        """One optimizer step on _linkpred_loss(embeddings).  modules: set to train() and, each on its own, clipped to --grad_clip_norm
+        (model.py:160-162; a module without parameters, the DOT predictor, is passed over)."""
         a = self.args
-        self.teacherGNN.train()
-        self.predictor.train()
-        loss = self.training_loss_linkpred()
+        for m in modules:
+            m.train()
+        loss = self._linkpred_loss(embeddings)
         self.optimizer.zero_grad()
         loss.backward()
-        if a.grad_clip_norm >= 0:      # (model.py:160-162)
-            torch.nn.utils.clip_grad_norm_(self.teacherGNN.parameters(), a.grad_clip_norm)
-            if list(self.predictor.parameters()):      # (DOT has none)
-                torch.nn.utils.clip_grad_norm_(self.predictor.parameters(), a.grad_clip_norm)
+        if a.grad_clip_norm >= 0:
+            for m in modules:
+                if list(m.parameters()):
+                    torch.nn.utils.clip_grad_norm_(m.parameters(), a.grad_clip_norm)
         self.optimizer.step()
         value = self._checked(loss.item())
         self.link_sampler().check()      # the loss has just been read: a failed negative slot, or a pair outside the graph, raises here
         ops.pair_check()
         return value
 
+    def _linkpred_evaluate(self, embeddings, modules, mode):
+        if mode not in ('train', 'test'):
+            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
+        for m in modules:
+            m.eval()
+        with torch.no_grad():
+            h = embeddings()
+            pos, neg = self.gen_linkpred_edge_index(mode)
+            ps, ns = self.predictor.score_pairs(h, pos).reshape(-1), self.predictor.score_pairs(h, neg).reshape(-1)
+        return self._link_metrics(ps, ns, ops.pair_check)
+
+    def run_trainSet_linkpred(self):
+        return self._linkpred_step(self._teacher_embeddings, (self.teacherGNN, self.predictor))
+
     def evaluate_linkpred(self, mode='test'):
         """{'Hits@20', 'Hits@50', 'Hits@100', 'AUC'} of the eval-mode predictor on a fresh `mode` sample (model.py:187-266 with `hits`; every positive
         is ranked against all sampled negatives, ties as ops.rank_counts counts them)."""
-        if mode not in ('train', 'test'):
-            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
-        self.teacherGNN.eval()
-        self.predictor.eval()
-        with torch.no_grad():
-            h = self.teacherGNN.get_3_embs(self.data.x, self.data.edge_index).commonEmb
-            pos, neg = self.gen_linkpred_edge_index(mode)
-            ps, ns = self.predictor.score_pairs(h, pos).reshape(-1), self.predictor.score_pairs(h, neg).reshape(-1)
-        self.link_sampler().check()
-        ops.pair_check()
-        out = ops.hits_at_k(ps, ns, (20, 50, 100))
-        out['AUC'] = ops.auc(ps, ns)
-        return out
+        return self._linkpred_evaluate(self._teacher_embeddings, (self.teacherGNN, self.predictor), mode)
 
     def train_teacherGNN_linkpred(self):
         """--epochs steps of run_trainSet_linkpred, then evaluate_linkpred('test').  Eager steps only (no --hip_graph, no --resume).  Returns
@@ -835,43 +848,15 @@ class trainer:
 
     def training_loss_linkpred_encoder(self):
         """Forward + objective of BaseModel.train's step (model.py:147-157) on the encoder's embeddings.  Returns the 0-dim loss."""
-        from .Link_prediction_model import calculate_loss
-        h = self.linkpred_encoder_embeddings()
-        pos, neg = self.gen_linkpred_edge_index('train')
-        return calculate_loss(self.args.loss_func, self.predictor.score_pairs(h, pos), self.predictor.score_pairs(h, neg), int(self.args.num_neg))
+        return self._linkpred_loss(self.linkpred_encoder_embeddings)
 
     def run_trainSet_linkpred_encoder(self):
-        a = self.args
-        self.encoder.train()
-        self.predictor.train()
-        loss = self.training_loss_linkpred_encoder()
-        self.optimizer.zero_grad()
-        loss.backward()
-        if a.grad_clip_norm >= 0:      # (model.py:160-162: encoder and predictor separately; the embedding is not clipped)
-            torch.nn.utils.clip_grad_norm_(self.encoder.parameters(), a.grad_clip_norm)
-            if list(self.predictor.parameters()):
-                torch.nn.utils.clip_grad_norm_(self.predictor.parameters(), a.grad_clip_norm)
-        self.optimizer.step()
-        value = self._checked(loss.item())
-        self.link_sampler().check()
-        ops.pair_check()
-        return value
+        """A step on the encoder's embeddings: encoder and predictor train and are clipped separately; the embedding table is neither (model.py:160-162)."""
+        return self._linkpred_step(self.linkpred_encoder_embeddings, (self.encoder, self.predictor))
 
     def evaluate_linkpred_encoder(self, mode='test'):
         """{'Hits@20', 'Hits@50', 'Hits@100', 'AUC'} of the eval-mode encoder + predictor on a fresh `mode` sample (as evaluate_linkpred)."""
-        if mode not in ('train', 'test'):
-            raise NotImplementedError(f"mode must be 'train' or 'test', got {mode!r}")
-        self.encoder.eval()
-        self.predictor.eval()
-        with torch.no_grad():
-            h = self.linkpred_encoder_embeddings()
-            pos, neg = self.gen_linkpred_edge_index(mode)
-            ps, ns = self.predictor.score_pairs(h, pos).reshape(-1), self.predictor.score_pairs(h, neg).reshape(-1)
-        self.link_sampler().check()
-        ops.pair_check()
-        out = ops.hits_at_k(ps, ns, (20, 50, 100))
-        out['AUC'] = ops.auc(ps, ns)
-        return out
+        return self._linkpred_evaluate(self.linkpred_encoder_embeddings, (self.encoder, self.predictor), mode)
 
     def train_linkpred_encoder(self):
         """--epochs steps of run_trainSet_linkpred_encoder, then evaluate_linkpred_encoder('test').  Eager steps only.  Returns

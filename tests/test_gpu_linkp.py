@@ -241,6 +241,65 @@ def test_loss_mrr_and_gradient_against_float64(name):
         assert bool((err_ref <= b_grad + b_ref).all())
 
 
+@pytest.mark.parametrize('D', [4, 7, 300, 'slice8'])
+def test_the_loss_scores_are_the_pair_dot_kernel(D):
+    """One kernel behind both (cb_pair_core.h): the scores of the loss over pos | neg equal pair_dot over the concatenated pairs bit for bit — the
+    float4 path (D = 4), the scalar path (7), more than one 256-column pass (300), and a column slice of a wider matrix — and both count the same
+    unusable pairs, whose scores are NaN on both sides."""
+    from gnn_tail_generalization_amd import ops
+    N, P, Nn = 40, 5, 12
+    if D == 'slice8':
+        emb, pos, neg = _synthetic(N, 8, P, Nn, seed=12, ld=12)
+        emb = emb.to(DEV)[:, :8]
+        assert emb.stride(0) == 12
+    else:
+        emb, pos, neg = _synthetic(N, D, P, Nn, seed=D)
+        emb = emb.to(DEV)
+    neg[:, 3] = -1
+    pos[1, 2] = N
+    pos, neg = pos.to(DEV), neg.to(DEV)
+    scores, status = ops.linkp_loss_eva(emb, pos, neg, return_parts=True)[2:]
+    dot, dot_status = ops.pair_dot(emb, torch.cat([pos, neg], 1), return_status=True)
+    nan = torch.zeros(P + Nn, dtype=torch.bool, device=DEV)
+    nan[[2, P + 3]] = True
+    assert torch.equal(torch.isnan(scores), nan) and torch.equal(torch.isnan(dot), nan)
+    assert torch.equal(scores[~nan], dot[~nan]) and bool(torch.isfinite(dot[~nan]).all())
+    assert int(status) == int(dot_status) == 2
+    with pytest.raises(RuntimeError, match='2 pair'):
+        ops.pair_check()
+
+
+@pytest.mark.parametrize('D', [8, 300])
+def test_the_loss_gradient_is_the_pair_scatter_with_the_bce_coefficient(D):
+    """One scatter behind both: on inputs whose BCE coefficient is exact in fp32 the loss's gradient equals the scalar-coefficient scatter bit for
+    bit.  Nodes 0..11 live in the first D / 2 columns and nodes 12..23 in the last, every pair joins the halves, so every score is exactly 0,
+    sigmoid exactly 0.5, and with S = 64 and an upstream gradient of 1 the coefficient is -0.5 / 64 (positives) or +0.5 / 64 (negatives).  Node 0
+    sits in 20 pairs (a long run of the sorted index); nodes 11 and 23 in none."""
+    from gnn_tail_generalization_amd import ops
+    N, P, Nn = 24, 16, 48
+    S = P + Nn
+    g = torch.Generator().manual_seed(300 + D)
+    emb = torch.randn(N, D, generator=g)
+    emb[:12, D // 2:] = 0
+    emb[12:, :D // 2] = 0
+    left, right = torch.randint(1, 11, (S,), generator=g), torch.randint(12, 23, (S,), generator=g)
+    left[::3][:20] = 0
+    pairs = torch.stack([left, right])
+    pairs[:, 1::2] = pairs[:, 1::2].flip(0)      # both orientations
+    assert int((pairs == 0).sum()) == 20 and not bool(((pairs == 11) | (pairs == 23)).any())
+    pairs = pairs.to(DEV)
+    pos, neg = pairs[:, :P].contiguous(), pairs[:, P:].contiguous()
+    dev_emb = emb.to(DEV).requires_grad_(True)
+    loss, _, scores, status = ops.linkp_loss_eva(dev_emb, pos, neg, return_parts=True)
+    assert bool((scores == 0.0).all()) and int(status) == 0      # the premise: sigmoid is exactly 0.5 everywhere
+    (grad,) = torch.autograd.grad(loss, dev_emb)
+    coef = torch.cat([torch.full((P,), -0.5 / S), torch.full((Nn,), 0.5 / S)]).to(DEV)
+    assert coef.dtype == torch.float32
+    want = ops._pair_scatter_raw(dev_emb.detach(), pairs.to(torch.int32).contiguous(), coef)
+    assert torch.equal(grad, want)
+    assert bool((grad[[11, 23]] == 0).all()) and bool((grad[0] != 0).any()) and bool((grad[0, :D // 2] == 0).all())
+
+
 def test_mrr_of_held_scores_ties_and_the_thin_forms_of_utils():
     from gnn_tail_generalization_amd import ops, utils
     f = lambda *v: torch.tensor(v, dtype=torch.float32, device=DEV)      # noqa: E731

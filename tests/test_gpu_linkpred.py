@@ -272,6 +272,17 @@ def test_pair_dot_and_scatter_against_float64(D):
     ops.pair_check()
 
 
+def test_pair_dot_of_no_pairs_forward_and_backward():
+    """S = 0 through the shared launchers: an empty score vector, a zero status, and a gradient of the full shape that is exactly zero."""
+    from gnn_tail_generalization_amd import ops
+    h = torch.randn(9, 12, generator=torch.Generator().manual_seed(0)).to(DEV).requires_grad_(True)
+    s, st = ops.pair_dot(h, torch.zeros((2, 0), dtype=torch.int64, device=DEV), return_status=True)
+    assert tuple(s.shape) == (0,) and s.dtype == torch.float32 and int(st.item()) == 0
+    s.sum().backward()
+    assert tuple(h.grad.shape) == (9, 12) and bool((h.grad == 0).all())
+    ops.pair_check()
+
+
 # ---- predictors -----------------------------------------------------------------------------------------------------------------------
 def _absnet(sd, h, pairs, gout):
     """sum|terms| of the output and of every gradient: the float64 network on absolute values, ReLU left out."""

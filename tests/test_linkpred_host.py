@@ -214,21 +214,41 @@ def test_options_mirror_the_reference_defaults():
     assert (a.predictor, a.loss_func, a.num_neg, a.batch_size, a.grad_clip_norm, a.mlp_num_layers, a.mlp_hidden_channels) == ('DOT', 'ce_loss', 3, 65536, 2.0, 2, 256)
 
 
-def test_the_new_hip_file_compiles_clean_under_wall_without_scratch(tmp_path):
-    """The cross-compile for gfx950 with the Makefile's flags and -Werror, code generation included; every kernel of the file reports 0 bytes of
-    scratch, and the pair GEMM's 128 x 128 instantiations fit three wavefronts per SIMD."""
+@pytest.mark.parametrize('name', ['cb_linkpred', 'cb_linkp'])
+def test_the_new_hip_file_compiles_clean_under_wall_without_scratch(name, tmp_path):
+    """The cross-compile for gfx950 with the Makefile's flags and -Werror, code generation included, of the two files that share cb_pair_core.h;
+    every kernel of either file reports 0 bytes of scratch, and the pair GEMM's 128 x 128 instantiations fit three wavefronts per SIMD."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    src = os.path.join(ROOT, 'gnn-tail-generalization_amd', 'csrc', 'cb_linkpred.hip')
+    src = os.path.join(ROOT, 'gnn-tail-generalization_amd', 'csrc', name + '.hip')
     flags = re.search(r'^FLAGS\s*:=\s*(.*)$', open(os.path.join(os.path.dirname(src), 'Makefile')).read(), flags=re.M).group(1).replace('$(ARCH)', 'gfx950').split()
     assert '-Wall' in flags
-    r = subprocess.run([hipcc] + flags + ['-Werror', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path / 'cb_linkpred.o')],
+    r = subprocess.run([hipcc] + flags + ['-Werror', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path / (name + '.o'))],
                        capture_output=True, text=True, cwd=os.path.dirname(src))
     assert r.returncode == 0 and 'warning:' not in r.stderr, r.stderr[-2000:]
     names = re.findall(r'Function Name: (\S+)', r.stderr)
     scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', r.stderr)]
     occ = [int(v) for v in re.findall(r'Occupancy \[waves/SIMD\]: (\d+)', r.stderr)]
-    assert len(names) == len(scratch) == len(occ) >= 12 and sum('k_pair_gemm_nn_l3' in n for n in names) == 3
+    assert len(names) == len(scratch) == len(occ) >= 1
     assert not any(scratch), dict(zip(names, scratch))
-    for n, o in zip(names, occ):
-        if 'k_pair_gemm_nn_l3ILi2ELi2ELi2E' in n:
-            assert o >= 3, (n, o)
+    if name == 'cb_linkpred':
+        assert len(names) >= 12 and sum('k_pair_gemm_nn_l3' in n for n in names) == 3
+        for n, o in zip(names, occ):
+            if 'k_pair_gemm_nn_l3ILi2ELi2ELi2E' in n:
+                assert o >= 3, (n, o)
+
+
+def test_the_status_ledger_adds_up_and_forgets():
+    """ops._Ledger behind pair_check() / pair_scores_check(): two words added, one drain returns their fold, the next drain finds nothing."""
+    from gnn_tail_generalization_amd import ops
+    led = ops._Ledger()
+    assert led.drain() == 0
+    first = torch.tensor([2], dtype=torch.int32)
+    led.add(first)
+    led.add(torch.tensor([3], dtype=torch.int32))
+    assert int(first) == 2                      # the caller's own status tensor is not accumulated into
+    assert led.drain() == 5 and led.drain() == 0
+    top = ops._Ledger(torch.fmax, max)
+    top.add(torch.tensor([4.0]))
+    top.add(torch.tensor([9.0]))
+    top.add(torch.tensor([1.0]))
+    assert top.drain() == 9.0 and top.drain() == 0
