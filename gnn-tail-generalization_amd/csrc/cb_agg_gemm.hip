@@ -19,8 +19,9 @@
 //   B operand: the weight, split ONCE per launch by k_weight_image into MFMA fragment order (384 KB, L2 resident): a fragment is
 //              one coalesced global_load_dwordx4 per limb, no LDS, no conversion in the K loop;
 //   C: accumulators -> wave-private LDS strips -> row-major float4 -> epilogue -> 256-byte streaming row segments.
-// Hub rows (more edges than the hub threshold) are reduced by the hub kernels, which run BEFORE this kernel; their finished rows are
-// read back from memory into the tile.
+// Hub rows (more edges than the hub threshold) are reduced by the hub kernels, which run BEFORE this kernel (launch_hub_rows); their finished
+// rows are read back from memory into the tile.  The row block's head (load_row_block), its cut among the gathering wavefronts (tile_row_cut)
+// and the walk itself (stream_rows) are cb_spmm_core.h's, shared with k_spmm_rows and cb_sage.hip.
 // ACC forms (node-sharded path, dist.py): the reduction of a row starts from the partial sums of the earlier passes (interior columns,
 // earlier halo slices) — the LAST halo pass of a rank's aggregation then also produces the next layer's Z / this layer's dX.
 #include <stdlib.h>
@@ -128,6 +129,7 @@ __device__ __forceinline__ void ag_signal(int* flag, int lane) {
 constexpr int kNG = 8;       // gathering wavefronts (3 wavefronts per SIMD at <= 168 registers; 12 gathers in flight each)
 constexpr int kU = 12;       // gathers in flight per gathering wavefront (16: spills; 8: slower — profiles/r03_fused_agg_gemm.md)
 
+// One gathering wavefront's share of tile t (tile_row_cut of cb_spmm_core.h) into the LDS tile and, as k_spmm_rows does, to memory
 template <bool FUSED, int GP, bool ACC, bool CS = false>
 __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile, int w, int lane, const int* __restrict__ rowptr,
                                                 const int* __restrict__ col, const float* __restrict__ h, int64_t ld_h, float* __restrict__ out,
@@ -135,19 +137,9 @@ __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile,
   const int r0 = t * kTM;
   const int nrt = min(kTM, n_rows - r0);
   const int c0 = lane * 4;
-  const int my_ptr = __builtin_nontemporal_load(rowptr + r0 + min(lane, nrt));
-  const int ptr_hi = rowptr[r0 + nrt];                      // (uniform address: scalar load)
-  float my_scale = 1.f;
-  if (ep.row_scale && lane < nrt) my_scale = __builtin_nontemporal_load(ep.row_scale + r0 + lane);
-  int nxt = __shfl_down(my_ptr, 1);
-  if (lane == kWave - 1) nxt = ptr_hi;
-  const unsigned long long hubmask = __ballot(lane < nrt && (nxt - my_ptr) > hub_T);
-  // this wavefront's rows [ra, rb): the rows whose first edge falls into its share of the tile's edge range
-  const int e0 = bcast_lane(my_ptr, 0), e1 = ptr_hi;
-  const int64_t span = (int64_t)e1 - e0;
-  const int ta = e0 + (int)(span * w / kNG), tb = e0 + (int)(span * (w + 1) / kNG);
-  const int ra = w == 0 ? 0 : (int)__popcll(__ballot(lane < nrt && my_ptr < ta));
-  const int rb = w == kNG - 1 ? nrt : (int)__popcll(__ballot(lane < nrt && my_ptr < tb));
+  const auto blk = load_row_block<true>(rowptr, ep.row_scale, hub_T, r0, nrt);
+  const RowCut cut = tile_row_cut<kNG>(blk, nrt, w);
+  const int rb = cut.rb;
   float bvec[4] = {0.f, 0.f, 0.f, 0.f};
   if (ep.bias) {
 #pragma unroll
@@ -157,22 +149,20 @@ __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile,
   float* out_lane = out + c0;
   float* tile_lane = tile + c0;
   const float* init_lane = ACC ? ep.acc_init + c0 : nullptr;
-  int r = ra;
+  int r = cut.ra;
   while (r < rb) {      // maximal hub-free runs of [ra, rb)
-    const unsigned long long m = (hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
+    const unsigned long long m = (blk.hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
     const int nh = m ? r + (__ffsll((long long)m) - 1) : rb;
     if (nh > r)
-      stream_rows<4, kU, true, FUSED, ACC, float, GP, kTLD, true, CS>(r, nh, nrt, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, true,
-                                                                         ep.relu, bvec, fe, c0, init_lane, ep.ld_init, ep, tile_lane, ptr_hi);
+      stream_rows<4, kU, true, FUSED, ACC, float, GP, kTLD, true, CS>(r, nh, nrt, blk.my_ptr, blk.my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, true,
+                                                                         ep.relu, bvec, fe, c0, init_lane, ep.ld_init, ep, tile_lane, blk.ptr_hi);
     if (nh < rb) {      // hub row nh: finished by the hub kernels, which ran before this launch
       const float* src = FUSED ? fe.out_next + (int64_t)(r0 + nh) * fe.ld_next + c0 : out + (int64_t)(r0 + nh) * ld_out + c0;
       *reinterpret_cast<float4*>(tile_lane + nh * kTLD) = *reinterpret_cast<const float4*>(src);
     }
     r = nh + 1;
   }
-  if (w == kNG - 1) {
-    for (int i = nrt; i < kTM; ++i) *reinterpret_cast<float4*>(tile_lane + i * kTLD) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  if (w == kNG - 1) zero_tile_rows<kTLD>(tile_lane, nrt, kTM);
 }
 
 // One K step of B fragments in flight per multiplying wavefront (two register buffers, K loop unrolled by two): next to wavefronts that
@@ -387,7 +377,6 @@ __global__ void __launch_bounds__(64) k_agg_handover_selftest(int* err) {
   ag_wait(&never, 1, err, 1 << 10);
 }
 
-static inline int64_t ag_partial_ld(int64_t d) { return (d + 3) / 4 * 4; }
 constexpr int kMaxBlocks = 1024;      // cap of the persistent grid
 
 // blocks of the persistent kernel: one per CU of the current device (139 KB of LDS each)
@@ -401,61 +390,34 @@ static int ag_n_blocks(int n_tiles) {
 template <bool FUSED, bool ACC>
 static int launch_agg_gemm(const cb_csr_view& g, const float* h, int64_t ld_h, Epilogue ep, float* out, int64_t ld_out, hipStream_t st, FusedEpi fe,
                            GemmTail gt) {
-  const int32_t *rowptr = g.rowptr, *col = g.col, *hub_rows = g.hub_rows, *hub_chunk_ptr = g.hub_chunk_ptr;
-  const int64_t N = g.n_rows;
-  const int hub_T = g.hub_threshold, n_hubs = g.n_hubs, n_chunks = g.n_chunks;
-  float* partial = (float*)g.ws;
-  const int d = kKD;
-  const dim3 blk(256);
   int* err = device_error_word();
   CB_CHECK_ARG(err != nullptr, CB_E_HIP, "cb_spmm_gemm: the device error word could not be allocated (%s)", cb_last_error());
   CB_CHECK_ARG(*(volatile int*)err == 0, CB_E_DEVICE, "cb_spmm_gemm: an earlier launch recorded a device-side error (%s); results since then are invalid",
                device_error_text());
   gt.err = err;
-  if (n_hubs > 0) {      // hub rows first: the main kernel reads their finished rows back
-    const int64_t ld_p = ag_partial_ld(d);
-    const dim3 gridc((unsigned)((n_chunks + 3) / 4), 1);
-    if (ep.col_scale) {      // SR: the source-row factor, as cb_spmm_csr_f32's hub kernels apply it
-      if (ep.col_flags)
-        hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2, true>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
-                           hub_chunk_ptr, partial, ld_p, ep);
-      else
-        hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 0, true>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
-                           hub_chunk_ptr, partial, ld_p, ep);
-    } else if (ep.col_flags)
-      hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
-                         hub_chunk_ptr, partial, ld_p, ep);
-    else
-      hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 0>), gridc, blk, 0, st, rowptr, col, h, ld_h, d, hub_T, n_hubs, n_chunks, hub_rows,
-                         hub_chunk_ptr, partial, ld_p, ep);
-    CB_LAUNCH_CHECK();
-    const dim3 grid2((unsigned)((n_hubs + 3) / 4), 1);
-    FusedEpi fe_hub = fe;
-    fe_hub.skip_next = 0;      // hub rows always go through memory: the persistent kernel reads them back into its tile
-    hipLaunchKernelGGL((k_spmm_hub_finish<4, FUSED>), grid2, blk, 0, st, d, n_hubs, hub_rows, hub_chunk_ptr, partial, ld_p, out, ld_out, ep, fe_hub);
-    CB_LAUNCH_CHECK();
-  }
-  const int n_tiles = (int)((N + kTM - 1) / kTM);
+  FusedEpi fe_hub = fe;      // hub rows first: the main kernel reads their finished rows back
+  fe_hub.skip_next = 0;      // (they always go through memory)
+  const int rch = launch_hub_rows<4, float, FUSED>(g, h, ld_h, kKD, out, ld_out, ep, fe_hub, st);
+  if (rch != CB_OK) return rch;
+  const int n_tiles = (int)((g.n_rows + kTM - 1) / kTM);
   const dim3 grid((unsigned)ag_n_blocks(n_tiles)), block(64 * (kNG + 4));
-  bool narrow = false, sr = false;
-  if constexpr (!FUSED && !ACC) {      // the trunk's store on a subset of the node rows as the tail (source-row factor in the gathers)
-    sr = gt.row_ids != nullptr;
-    if (sr) {
-      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<false, 2, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-      else hipLaunchKernelGGL((k_agg_gemm2<false, 0, false, false, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+  // the tail: the trunk's store on a subset of the node rows (gt.row_ids; source-row factor in the gathers), the output Linear of <= 64 classes
+  // (gt.n_out > 0), or the plain 256 x 256 product
+  dispatch_gp_cs<true, false>(ep.col_flags ? 2 : 0, false, [&](auto GP, auto) {
+    auto go = [&](auto NARROW, auto SR) {
+      hipLaunchKernelGGL((k_agg_gemm2<FUSED, decltype(GP)::value, ACC, decltype(NARROW)::value, decltype(SR)::value>), grid, block, 0, st, g.rowptr, g.col, h, ld_h, out,
+                         ld_out, (int)g.n_rows, ep, g.hub_threshold, fe, gt, n_tiles);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if constexpr (!FUSED && !ACC) {
+      if (gt.row_ids) return go(no, yes);
     }
-  }
-  if constexpr (FUSED) {      // the output Linear (<= 64 classes) as the tail: gt.n_out > 0
-    narrow = gt.n_out > 0;
-    if (narrow) {
-      if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<true, 2, ACC, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-      else hipLaunchKernelGGL((k_agg_gemm2<true, 0, ACC, true>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
+    if constexpr (FUSED) {
+      if (gt.n_out > 0) return go(yes, no);
     }
-  }
-  if (!narrow && !sr) {
-    if (ep.col_flags) hipLaunchKernelGGL((k_agg_gemm2<FUSED, 2, ACC>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-    else hipLaunchKernelGGL((k_agg_gemm2<FUSED, 0, ACC>), grid, block, 0, st, rowptr, col, h, ld_h, out, ld_out, (int)N, ep, hub_T, fe, gt, n_tiles);
-  }
+    go(no, no);
+  });
   CB_LAUNCH_CHECK();
   return CB_OK;
 }

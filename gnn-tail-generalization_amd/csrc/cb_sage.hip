@@ -8,8 +8,8 @@
 // Shape of a block: 8 wavefronts, one 64-row tile, three phases kept apart by ONE block barrier (no hand-over through counters, no persistent
 // loop, no spin, no atomics, nothing to report in the device error word):
 //   1. all eight wavefronts copy their 8 rows of `self` into columns 256..511 of the LDS tile and reduce their share of the tile's rows into columns
-//      0..255 — stream_rows of cb_spmm_core.h, the walk and the sums of cb_spmm_csr_f32 (rows cut among the wavefronts at equal edge counts as in
-//      cb_agg_gemm.hip; hub rows are reduced by the hub kernels BEFORE this launch and read back from `agg_out`);
+//      0..255 — stream_rows of cb_spmm_core.h, the walk and the sums of cb_spmm_csr_f32 (rows cut among the wavefronts at equal edge counts by its
+//      tile_row_cut, as in cb_agg_gemm.hip; hub rows are reduced by launch_hub_rows BEFORE this launch and read back from `agg_out`);
 //   2. __syncthreads();
 //   3. wavefronts 0..3 multiply the 64 x 512 tile by the image (tile_times_image of cb_tile_gemm.h: three bf16 limbs, the six limb products of
 //      cb_gemm_nn_f32 in its order, K steps 0..31 in order into the same accumulators) and store through their private C strips.
@@ -84,20 +84,11 @@ __global__ void __launch_bounds__(64 * kSG) k_sage_layer(SageArgs a) {
     for (int i = 0; i < kTM / kSG; ++i) *reinterpret_cast<float4*>(tile_lane + (wv * (kTM / kSG) + i) * TLD + kKD) = sv[i];
   }
 
-  // ---- phase 1b: the aggregation of this wavefront's rows (cb_agg_gemm.hip's cut of the tile at equal edge counts) ----
+  // ---- phase 1b: the aggregation of this wavefront's rows (tile_row_cut of cb_spmm_core.h: the tile cut at equal edge counts) ----
   {
-    const int my_ptr = __builtin_nontemporal_load(a.rowptr + r0 + min(lane, nrt));
-    const int ptr_hi = a.rowptr[r0 + nrt];
-    float my_scale = 1.f;
-    if (a.row_scale && lane < nrt) my_scale = __builtin_nontemporal_load(a.row_scale + r0 + lane);
-    int nxt = __shfl_down(my_ptr, 1);
-    if (lane == kWave - 1) nxt = ptr_hi;
-    const unsigned long long hubmask = __ballot(lane < nrt && (nxt - my_ptr) > a.hub_T);
-    const int e0 = bcast_lane(my_ptr, 0), e1 = ptr_hi;
-    const int64_t span = (int64_t)e1 - e0;
-    const int ta = e0 + (int)(span * wv / kSG), tb = e0 + (int)(span * (wv + 1) / kSG);
-    const int ra = wv == 0 ? 0 : (int)__popcll(__ballot(lane < nrt && my_ptr < ta));
-    const int rb = wv == kSG - 1 ? nrt : (int)__popcll(__ballot(lane < nrt && my_ptr < tb));
+    const auto blk = load_row_block<true>(a.rowptr, a.row_scale, a.hub_T, r0, nrt);
+    const RowCut cut = tile_row_cut<kSG>(blk, nrt, wv);
+    const int rb = cut.rb;
     const float bvec[4] = {0.f, 0.f, 0.f, 0.f};
     Epilogue ep{};
     ep.row_scale = a.row_scale;
@@ -105,20 +96,18 @@ __global__ void __launch_bounds__(64 * kSG) k_sage_layer(SageArgs a) {
     const FusedEpi fe{};
     const float* h_lane = a.h + c0;
     float* out_lane = WAGG ? a.agg + c0 : nullptr;
-    int r = ra;
+    int r = cut.ra;
     while (r < rb) {      // maximal hub-free runs of [ra, rb)
-      const unsigned long long m = (hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
+      const unsigned long long m = (blk.hubmask >> r) & (rb - r >= 64 ? ~0ull : ((1ull << (rb - r)) - 1ull));
       const int nh = m ? r + (__ffsll((long long)m) - 1) : rb;
       if (nh > r)
-        stream_rows<4, kSU, true, false, false, float, GP, TLD, true, CS, false, !WAGG>(r, nh, nrt, my_ptr, my_scale, r0, a.col, h_lane, a.ld_h, out_lane, a.ld_agg,
-                                                                                         true, 0, bvec, fe, c0, nullptr, 0, ep, tile_lane, ptr_hi);
+        stream_rows<4, kSU, true, false, false, float, GP, TLD, true, CS, false, !WAGG>(r, nh, nrt, blk.my_ptr, blk.my_scale, r0, a.col, h_lane, a.ld_h, out_lane,
+                                                                                         a.ld_agg, true, 0, bvec, fe, c0, nullptr, 0, ep, tile_lane, blk.ptr_hi);
       if (nh < rb)        // hub row nh: finished by the hub kernels, which ran before this launch
         *reinterpret_cast<float4*>(tile_lane + nh * TLD) = *reinterpret_cast<const float4*>(a.agg + (int64_t)(r0 + nh) * a.ld_agg + c0);
       r = nh + 1;
     }
-    if (wv == kSG - 1) {
-      for (int i = nrt; i < kTM; ++i) *reinterpret_cast<float4*>(tile_lane + i * TLD) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    if (wv == kSG - 1) zero_tile_rows<TLD>(tile_lane, nrt, kTM);
   }
   __syncthreads();
 
@@ -152,18 +141,6 @@ __global__ void __launch_bounds__(64 * kSG) k_sage_layer(SageArgs a) {
       store_stream<4>(a.out + m * a.ld_out + n, o);
     });
   }
-}
-
-template <bool HAS_SELF, bool CS, bool WAGG>
-static void launch_sage_gp(int gp, dim3 grid, hipStream_t st, const SageArgs& a) {
-  if (gp) hipLaunchKernelGGL((k_sage_layer<HAS_SELF, CS, WAGG, 2>), grid, dim3(64 * kSG), 0, st, a);
-  else hipLaunchKernelGGL((k_sage_layer<HAS_SELF, CS, WAGG, 0>), grid, dim3(64 * kSG), 0, st, a);
-}
-
-template <bool HAS_SELF>
-static void launch_sage(bool cs, bool wagg, int gp, dim3 grid, hipStream_t st, const SageArgs& a) {
-  if (cs) { if (wagg) launch_sage_gp<HAS_SELF, true, true>(gp, grid, st, a); else launch_sage_gp<HAS_SELF, true, false>(gp, grid, st, a); }
-  else { if (wagg) launch_sage_gp<HAS_SELF, false, true>(gp, grid, st, a); else launch_sage_gp<HAS_SELF, false, false>(gp, grid, st, a); }
 }
 
 static inline bool sage_rows_ok(const float* p, int64_t ld) { return aligned16(p) && ld % 4 == 0 && ld >= kKD; }
@@ -212,24 +189,13 @@ extern "C" int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t l
   CB_CHECK_ARG(agg_out || (v.n_hubs == 0 && !agg_hubs_only), CB_E_INVALID, "%s: a plan with hub rows needs agg_out (the hub rows' way into the tile)", who);
   hipStream_t st = (hipStream_t)stream;
   const bool cs = col_scale != nullptr, wagg = agg_out && !agg_hubs_only;
-  if (v.n_hubs > 0) {      // hub rows first: the layer kernel reads their finished rows back (cb_spmm_csr_f32's hub kernels, its sums)
+  {      // hub rows first: the layer kernel reads their finished rows back (cb_spmm_csr_f32's hub kernels, its sums)
     Epilogue ep{};
     ep.row_scale = row_scale;
     ep.col_scale = col_scale;
     ep.col_flags = v.col_flags;
-    float* partial = (float*)v.ws;
-    const int64_t ld_p = kKD;
-    const dim3 gridc((unsigned)((v.n_chunks + 3) / 4), 1), blk(256);
-#define CB_SAGE_HUB(GP_, CS_)                                                                                                                       \
-  hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, GP_, CS_>), gridc, blk, 0, st, v.rowptr, v.col, h, ld_h, kKD, v.hub_threshold, v.n_hubs, v.n_chunks, \
-                     v.hub_rows, v.hub_chunk_ptr, partial, ld_p, ep)
-    if (cs) { if (v.col_flags) CB_SAGE_HUB(2, true); else CB_SAGE_HUB(0, true); }
-    else { if (v.col_flags) CB_SAGE_HUB(2, false); else CB_SAGE_HUB(0, false); }
-#undef CB_SAGE_HUB
-    CB_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_spmm_hub_finish<4, false>), dim3((unsigned)((v.n_hubs + 3) / 4), 1), blk, 0, st, kKD, v.n_hubs, v.hub_rows, v.hub_chunk_ptr, partial,
-                       ld_p, agg_out, ld_agg, ep, FusedEpi{});
-    CB_LAUNCH_CHECK();
+    const int rch = launch_hub_rows<4, float, false>(v, h, ld_h, kKD, agg_out, ld_agg, ep, FusedEpi{}, st);
+    if (rch != CB_OK) return rch;
   }
   SageArgs a{};
   a.rowptr = v.rowptr; a.col = v.col; a.n_rows = (int)v.n_rows; a.hub_T = v.hub_threshold;
@@ -239,8 +205,13 @@ extern "C" int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t l
   a.seed = seed; a.seed_dev = seed_dev; a.row0 = row0;
   a.agg = agg_out; a.ld_agg = ld_agg; a.out = out; a.ld_out = ld_out;
   const dim3 grid((unsigned)((v.n_rows + kTM - 1) / kTM));
-  if (self) launch_sage<true>(cs, wagg, v.col_flags, grid, st, a);
-  else launch_sage<false>(cs, wagg, v.col_flags, grid, st, a);
+  dispatch_gp_cs<true, true>(v.col_flags ? 2 : 0, cs, [&](auto GP, auto CS) {
+    dispatch_bool(self != nullptr, [&](auto HAS_SELF) {
+      dispatch_bool(wagg, [&](auto WAGG) {
+        hipLaunchKernelGGL((k_sage_layer<decltype(HAS_SELF)::value, decltype(CS)::value, decltype(WAGG)::value, decltype(GP)::value>), grid, dim3(64 * kSG), 0, st, a);
+      });
+    });
+  });
   CB_LAUNCH_CHECK();
   return CB_OK;
 }

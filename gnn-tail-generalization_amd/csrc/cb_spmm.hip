@@ -33,93 +33,35 @@
 
 namespace cb {
 
-static inline int64_t partial_ld(int64_t d) { return (d + 3) / 4 * 4; }
-
-// Gather policy of a launch: 2 when the caller hands over flagged column ids (col_flags: hot source rows keep the default cache policy,
-// every other gather streams), else 0 (all-streaming measured slower: profiles/r02_spmm_gather_policy.md).
-static inline int gather_policy(int col_flags) { return col_flags ? 2 : 0; }
-
 template <int VEC, bool FUSED, int RPW, int U, typename HT>
 static int launch_spmm_cfg(const cb_csr_view& g, const HT* h, int64_t ld_h, int64_t d, Epilogue ep, float* out, int64_t ld_out, hipStream_t st,
                            FusedEpi fe) {
-  const int32_t *rowptr = g.rowptr, *col = g.col, *hub_rows = g.hub_rows, *hub_chunk_ptr = g.hub_chunk_ptr;
-  const int64_t N = g.n_rows;
-  const int hub_T = g.hub_threshold, n_hubs = g.n_hubs, n_chunks = g.n_chunks;
-  float* partial = (float*)g.ws;
-  const int tile = kWave * VEC;
-  const int ny = (int)((d + tile - 1) / tile);
-  const int waves_per_block = 4;
-  {
-    int64_t n_waves = (N + RPW - 1) / RPW;
-    dim3 grid((unsigned)((n_waves + waves_per_block - 1) / waves_per_block), ny);
-#define CB_ROWS_LAUNCH_GP(FULL_, FUSED_, ACC_, GP_)                                                                                 \
-  hipLaunchKernelGGL((k_spmm_rows<VEC, RPW, U, FULL_, FUSED_, HT, ACC_, GP_>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h, \
-                     ld_h, out, ld_out, (int)N, (int)d, ep, hub_T, fe)
-#define CB_ROWS_LAUNCH(FULL_, FUSED_, ACC_) CB_ROWS_LAUNCH_GP(FULL_, FUSED_, ACC_, 0)
-    const bool acc = ep.acc_init != nullptr;
-    constexpr bool kGP = VEC == 4 && RPW == 16 && U == 8;   // gather-policy variants: the d % 256 == 0 kernels (fp32 and bf16-stored rows)
-    const int gp = kGP && d % tile == 0 ? (acc ? (ep.col_flags ? 2 : 0) : gather_policy(ep.col_flags)) : 0;
-    CB_CHECK_ARG(!ep.col_flags || gp == 2, CB_E_INVALID, "flagged column ids are only understood by the d %% 256 == 0 kernels");
-    bool cs_done = false;      // source-row factor (ep.col_scale): the d % 256 == 0 fp32 kernels with the plain store
-    if constexpr (kGP && !FUSED && sizeof(HT) == 4) {
-      if (ep.col_scale) {
-        CB_CHECK_ARG(!acc && d % tile == 0, CB_E_INVALID, "a source-row factor needs d %% 256 == 0 and no running sums");
-        if (gp == 2)
-          hipLaunchKernelGGL((k_spmm_rows<VEC, RPW, U, true, false, HT, false, 2, true>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h,
-                             ld_h, out, ld_out, (int)N, (int)d, ep, hub_T, fe);
-        else
-          hipLaunchKernelGGL((k_spmm_rows<VEC, RPW, U, true, false, HT, false, 0, true>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h,
-                             ld_h, out, ld_out, (int)N, (int)d, ep, hub_T, fe);
-        cs_done = true;
-      }
-    }
-    if (cs_done) {
-    } else if constexpr (FUSED) {
-      if (acc) { if constexpr (kGP) { if (gp == 2) CB_ROWS_LAUNCH_GP(true, true, true, 2); else CB_ROWS_LAUNCH(true, true, true); } else CB_ROWS_LAUNCH(true, true, true); }
-      else if constexpr (kGP) { if (gp == 2) CB_ROWS_LAUNCH_GP(true, true, false, 2); else CB_ROWS_LAUNCH(true, true, false); }
-      else CB_ROWS_LAUNCH(true, true, false);
-    } else if (d % tile == 0) {
-      if (acc) { if constexpr (kGP) { if (gp == 2) CB_ROWS_LAUNCH_GP(true, false, true, 2); else CB_ROWS_LAUNCH(true, false, true); } else CB_ROWS_LAUNCH(true, false, true); }
-      else if constexpr (kGP) { if (gp == 2) CB_ROWS_LAUNCH_GP(true, false, false, 2); else CB_ROWS_LAUNCH(true, false, false); }
-      else CB_ROWS_LAUNCH(true, false, false);
-    } else {
-      if (acc) CB_ROWS_LAUNCH(false, false, true); else CB_ROWS_LAUNCH(false, false, false);
-    }
-#undef CB_ROWS_LAUNCH
-#undef CB_ROWS_LAUNCH_GP
-    CB_LAUNCH_CHECK();
+  const int tile = kWave * VEC, wpb = 4;
+  const int64_t n_waves = (g.n_rows + RPW - 1) / RPW;
+  const dim3 grid((unsigned)((n_waves + wpb - 1) / wpb), (unsigned)((d + tile - 1) / tile));
+  // Which k_spmm_rows exist: gather policy 2 (flagged column ids: hot source rows keep the default cache policy, every other gather streams; all-streaming
+  // measured slower, profiles/r02_spmm_gather_policy.md) in the d % 256 == 0 kernels, fp32 and bf16-stored rows; the source-row factor in the plain fp32
+  // ones of those, without running sums
+  constexpr bool kGP = VEC == 4 && RPW == 16 && U == 8;
+  constexpr bool kCS = kGP && !FUSED && sizeof(HT) == 4;
+  const bool tiled = d % tile == 0, full = FUSED || tiled, acc = ep.acc_init != nullptr, cs = kCS && ep.col_scale;      // (the fused entries take d % 256 == 0 only)
+  const int gp = kGP && tiled && ep.col_flags ? 2 : 0;
+  CB_CHECK_ARG(!ep.col_flags || gp == 2, CB_E_INVALID, "flagged column ids are only understood by the d %% 256 == 0 kernels");
+  CB_CHECK_ARG(!cs || (!acc && tiled), CB_E_INVALID, "a source-row factor needs d %% 256 == 0 and no running sums");
+  auto rows = [&](auto FULL, auto ACC, auto GP, auto CS) {
+    hipLaunchKernelGGL((k_spmm_rows<VEC, RPW, U, decltype(FULL)::value, FUSED, HT, decltype(ACC)::value, decltype(GP)::value, decltype(CS)::value>), grid,
+                       dim3(kWave * wpb), 0, st, g.rowptr, g.col, h, ld_h, out, ld_out, (int)g.n_rows, (int)d, ep, g.hub_threshold, fe);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (full) {
+    if (acc) dispatch_gp_cs<kGP, false>(gp, false, [&](auto GP, auto CS) { rows(yes, yes, GP, CS); });
+    else dispatch_gp_cs<kGP, kCS>(gp, cs, [&](auto GP, auto CS) { rows(yes, no, GP, CS); });
+  } else if constexpr (!FUSED) {      // ragged last column tile: default gathers, no factor
+    dispatch_bool(acc, [&](auto ACC) { rows(no, ACC, std::integral_constant<int, 0>{}, no); });
   }
-  if (n_hubs > 0) {
-    const int64_t ld_p = partial_ld(d);
-    dim3 grid((unsigned)((n_chunks + waves_per_block - 1) / waves_per_block), ny);
-    constexpr bool kGPh = VEC == 4 && RPW == 16 && U == 8;
-    const int gph = kGPh && d % tile == 0 ? gather_policy(ep.col_flags) : 0;
-#define CB_HUB_LAUNCH(GP_)                                                                                                       \
-  hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, GP_>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h, ld_h, (int)d, \
-                     hub_T, n_hubs, n_chunks, hub_rows, hub_chunk_ptr, partial, ld_p, ep)
-    bool cs_hub = false;
-    if constexpr (kGPh && !FUSED && sizeof(HT) == 4) {
-      if (ep.col_scale) {
-        if (gph == 2)
-          hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, 2, true>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h, ld_h, (int)d, hub_T,
-                             n_hubs, n_chunks, hub_rows, hub_chunk_ptr, partial, ld_p, ep);
-        else
-          hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, 0, true>), grid, dim3(kWave * waves_per_block), 0, st, rowptr, col, h, ld_h, (int)d, hub_T,
-                             n_hubs, n_chunks, hub_rows, hub_chunk_ptr, partial, ld_p, ep);
-        cs_hub = true;
-      }
-    }
-    if (cs_hub) {
-    } else if constexpr (kGPh) { if (gph == 2) CB_HUB_LAUNCH(2); else CB_HUB_LAUNCH(0); }
-    else CB_HUB_LAUNCH(0);
-#undef CB_HUB_LAUNCH
-    CB_LAUNCH_CHECK();
-    dim3 grid2((unsigned)((n_hubs + waves_per_block - 1) / waves_per_block), ny);
-    hipLaunchKernelGGL((k_spmm_hub_finish<VEC, FUSED>), grid2, dim3(kWave * waves_per_block), 0, st, (int)d, n_hubs, hub_rows,
-                       hub_chunk_ptr, partial, ld_p, out, ld_out, ep, fe);
-    CB_LAUNCH_CHECK();
-  }
-  return CB_OK;
+  CB_LAUNCH_CHECK();
+  return launch_hub_rows<VEC, HT, FUSED>(g, h, ld_h, d, out, ld_out, ep, fe, st);
 }
 
 template <int VEC, bool FUSED = false, typename HT = float>
@@ -357,34 +299,16 @@ extern "C" int cb_spmm_csr_store_bwd_mix_f32(const cb_csr_view* g, const float* 
   }
   fe.cs_partial = colsum ? (float*)ws2 : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const int ny = (int)(d / 256);
   const int64_t nb_rows = mix_row_blocks(N), nb_hub = v.n_hubs > 0 ? mix_hub_blocks(v.n_hubs) : 0;
-  {
-    dim3 grid((unsigned)nb_rows, ny);
-    fe.cs_block0 = 0;
-    if (v.col_flags)
-      hipLaunchKernelGGL((k_spmm_rows<4, 16, 8, true, true, float, false, 2, false, true>), grid, dim3(256), 0, st, v.rowptr, v.col, h, ld_h, out_gr, ld_gr, (int)N,
-                         (int)d, ep, v.hub_threshold, fe);
-    else
-      hipLaunchKernelGGL((k_spmm_rows<4, 16, 8, true, true, float, false, 0, false, true>), grid, dim3(256), 0, st, v.rowptr, v.col, h, ld_h, out_gr, ld_gr, (int)N,
-                         (int)d, ep, v.hub_threshold, fe);
-    CB_LAUNCH_CHECK();
-  }
-  if (v.n_hubs > 0) {
-    const int64_t ld_p = partial_ld(d);
-    dim3 grid((unsigned)((v.n_chunks + 3) / 4), ny);
-    if (v.col_flags)
-      hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 2>), grid, dim3(256), 0, st, v.rowptr, v.col, h, ld_h, (int)d, v.hub_threshold, v.n_hubs, v.n_chunks,
-                         v.hub_rows, v.hub_chunk_ptr, (float*)v.ws, ld_p, ep);
-    else
-      hipLaunchKernelGGL((k_spmm_hub_chunks<4, 8, float, 0>), grid, dim3(256), 0, st, v.rowptr, v.col, h, ld_h, (int)d, v.hub_threshold, v.n_hubs, v.n_chunks,
-                         v.hub_rows, v.hub_chunk_ptr, (float*)v.ws, ld_p, ep);
-    CB_LAUNCH_CHECK();
-    fe.cs_block0 = (int)nb_rows;
-    hipLaunchKernelGGL((k_spmm_hub_finish<4, true, true>), dim3((unsigned)nb_hub, ny), dim3(256), 0, st, (int)d, v.n_hubs, v.hub_rows, v.hub_chunk_ptr,
-                       (const float*)v.ws, ld_p, out_gr, ld_gr, ep, fe);
-    CB_LAUNCH_CHECK();
-  }
+  fe.cs_block0 = 0;
+  dispatch_gp_cs<true, false>(v.col_flags ? 2 : 0, false, [&](auto GP, auto) {
+    hipLaunchKernelGGL((k_spmm_rows<4, 16, 8, true, true, float, false, decltype(GP)::value, false, true>), dim3((unsigned)nb_rows, (unsigned)(d / 256)), dim3(256), 0,
+                       st, v.rowptr, v.col, h, ld_h, out_gr, ld_gr, (int)N, (int)d, ep, v.hub_threshold, fe);
+  });
+  CB_LAUNCH_CHECK();
+  fe.cs_block0 = (int)nb_rows;      // (the hub-finish blocks' partial column sums follow the row kernel's)
+  const int rch = launch_hub_rows<4, float, true, true>(v, h, ld_h, d, out_gr, ld_gr, ep, fe, st);
+  if (rch != CB_OK) return rch;
   if (colsum) {
     const int nparts = (int)(nb_rows + nb_hub);
     const int per = (nparts + kFoldGroups - 1) / kFoldGroups;

@@ -1,7 +1,14 @@
-// Device side of the CSR sum-aggregation (design notes: cb_spmm.hip): vector helpers, the epilogues, the edge-stream walk of a
-// wavefront's row block (stream_rows), the row / hub kernels — and, at the end, the one host-side check of a cb_csr_view.  Shared by
-// cb_spmm.hip (the aggregation entry points) and cb_agg_gemm.hip (aggregation + next dense transform in one kernel).
+// The core of the CSR sum-aggregation (design notes: cb_spmm.hip), shared by cb_spmm.hip (the aggregation entry points), cb_agg_gemm.hip (aggregation +
+// next dense transform in one kernel), cb_sage.hip (the encoder layer) and, for the row block's head, cb_spmm_small.hip.
+//   device: vector helpers and the epilogues; RowBlock + load_row_block (the head of a wavefront's row block), tile_row_cut / zero_tile_rows (a 64-row
+//           tile among the gathering wavefronts), stream_rows (the edge-stream walk), the row / hub kernels;
+//   host:   check_csr_view, partial_ld, dispatch_bool / dispatch_gp_cs (run-time flags as compile-time constants) and launch_hub_rows.
+// What is still written out per kernel, on purpose (profiles/agg_core.md: each of these, shared, changes the registers or the schedule of a kernel):
+// stream_rows' positional operands, its three accumulation forks and k_spmm_hub_chunks' two, the loop over the runs between hub rows, and
+// k_spmm_rows' own copy of the head.
 #pragma once
+#include <type_traits>
+
 #include "cb_common.h"
 #include "cb_philox.h"
 #include "cb_trunk_store.h"
@@ -262,9 +269,58 @@ __device__ __forceinline__ void write_row(float* __restrict__ out_row, const flo
   store_stream<VEC>(out_row, r);
 }
 
-// Walks the contiguous edge range of local rows [rlo, rhi) of this wavefront's row block.
-// my_ptr: lane i holds rowptr[r0 + i] (i <= nr).  All control flow is wave-uniform.
-// wave-uniform `craw` = column id as stored (GP == 2: bit 31 = hot flag)
+// What a wavefront knows about the consecutive rows r0 .. r0 + nr - 1 it walks: lane i holds my_ptr = rowptr[r0 + min(i, nr)] and my_scale =
+// row_scale[r0 + i] (1 without row_scale; broadcast at flush time: no load on the flush path), bit i of hubmask marks a row with more than hub_T
+// edges (left to the hub kernels).  BLOCK64: the block may have 64 rows (the tile kernels), so rowptr[r0 + nr] has no lane of its own and is kept
+// in ptr_hi — the successor of lane 63's pointer, stream_rows' P65.  Blocks of fewer than 64 rows keep their end pointer in lane nr; ptr_hi is 0.
+template <bool BLOCK64>
+struct RowBlock {
+  int my_ptr, ptr_hi;
+  float my_scale;
+  unsigned long long hubmask;
+};
+
+template <bool BLOCK64>
+__device__ __forceinline__ RowBlock<BLOCK64> load_row_block(const int* __restrict__ rowptr, const float* __restrict__ row_scale, int hub_T, int r0, int nr) {
+  const int lane = lane_id();
+  RowBlock<BLOCK64> b;
+  b.my_ptr = __builtin_nontemporal_load(rowptr + r0 + min(lane, nr));
+  b.ptr_hi = 0;
+  if constexpr (BLOCK64) b.ptr_hi = rowptr[r0 + nr];      // (uniform address: scalar load)
+  b.my_scale = 1.f;
+  if (row_scale && lane < nr) b.my_scale = __builtin_nontemporal_load(row_scale + r0 + lane);
+  int nxt = __shfl_down(b.my_ptr, 1);
+  if constexpr (BLOCK64) {
+    if (lane == kWave - 1) nxt = b.ptr_hi;
+  }
+  b.hubmask = __ballot(lane < nr && (nxt - b.my_ptr) > hub_T);
+  return b;
+}
+
+// A 64-row tile cut among NW gathering wavefronts at equal EDGE counts: wavefront w takes the rows [ra, rb) whose first edge falls into its
+// share of the tile's edge range (row boundaries from the tile's rowptr values, two ballots), so that the wavefronts finish together.
+struct RowCut {
+  int ra, rb;
+};
+template <int NW>
+__device__ __forceinline__ RowCut tile_row_cut(const RowBlock<true>& blk, int nrt, int w) {
+  const int lane = lane_id();
+  const int e0 = bcast_lane(blk.my_ptr, 0), e1 = blk.ptr_hi;
+  const int64_t span = (int64_t)e1 - e0;
+  const int ta = e0 + (int)(span * w / NW), tb = e0 + (int)(span * (w + 1) / NW);
+  RowCut c;
+  c.ra = w == 0 ? 0 : (int)__popcll(__ballot(lane < nrt && blk.my_ptr < ta));
+  c.rb = w == NW - 1 ? nrt : (int)__popcll(__ballot(lane < nrt && blk.my_ptr < tb));
+  return c;
+}
+
+// Tile rows [from, to) (past the matrix's last row) as zeros: one wavefront, this lane's 4 columns
+template <int TLD>
+__device__ __forceinline__ void zero_tile_rows(float* tile_lane, int from, int to) {
+  for (int i = from; i < to; ++i) *reinterpret_cast<float4*>(tile_lane + i * TLD) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// One source row under gather policy GP.  wave-uniform `craw` = column id as stored (GP == 2: bit 31 = hot flag)
 template <int VEC, typename HT, int GP>
 __device__ __forceinline__ void gather_pol(float (&v)[VEC], const HT* __restrict__ h_lane, int64_t ld_h, int craw) {
   if constexpr (GP == 0 || VEC != 4) {
@@ -280,6 +336,8 @@ __device__ __forceinline__ void gather_pol(float (&v)[VEC], const HT* __restrict
   }
 }
 
+// Walks the contiguous edge range of local rows [rlo, rhi) of this wavefront's row block (no hub row inside).
+// my_ptr_v / my_scale / ptr_hi: the RowBlock's.  All control flow is wave-uniform.
 // TLD > 0 (cb_agg_gemm.hip): every finished row is also written to an LDS tile — tile_lane = this lane's 4 columns of the
 // wavefront's local row 0, TLD floats per tile row.
 // P65 (64-row blocks, cb_agg_gemm.hip): lane i holds rowptr[r0 + i] for i < 64 and ptr_hi = rowptr[r0 + 64].
@@ -534,7 +592,7 @@ __global__ void __launch_bounds__(256) k_spmm_rows(const int* __restrict__ rowpt
   const int c0 = (blockIdx.y * kWave + lane) * VEC;  // this lane's first column
   const bool active = c0 < d;
 
-  int my_ptr = __builtin_nontemporal_load(rowptr + r0 + min(lane, nr));
+  int my_ptr = __builtin_nontemporal_load(rowptr + r0 + min(lane, nr));      // (load_row_block<false>, written out: as a call it moves the fused kernels' schedules)
   float my_scale = 1.f;  // lane i: row_scale[r0 + i], broadcast at flush time (no load on the flush path)
   if (ep.row_scale && lane < nr) my_scale = __builtin_nontemporal_load(ep.row_scale + r0 + lane);
   const int nxt = __shfl_down(my_ptr, 1);
@@ -751,6 +809,54 @@ static inline int check_csr_view(const char* who, const cb_csr_view* g, int64_t 
   CB_CHECK_ARG(v.n_hubs == 0 || (v.hub_rows && v.hub_chunk_ptr && v.ws && v.ws_bytes >= need), CB_E_WORKSPACE,
                "%s: hub plan given but workspace missing/too small (%zu < %zu)", who, v.ws_bytes, need);
   if (v.n_hubs == 0) v.hub_threshold = INT32_MAX;
+  return CB_OK;
+}
+
+// row pitch of the hub partial sums in a view's workspace (cb_spmm_workspace_bytes)
+static inline int64_t partial_ld(int64_t d) { return (d + 3) / 4 * 4; }
+
+// A run-time flag as a compile-time constant: f(std::true_type / std::false_type)
+template <class F>
+static inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// The run-time pair (gather policy 0 / 2, source-row factor or not) as compile-time constants: f(std::integral_constant<int, GP>, std::bool_constant<CS>).
+// GP2 / CSF: whether the caller's kernels are compiled for gp == 2 / for a source-row factor at all — what is not compiled is not instantiated
+// here either (the narrow-row kernels have neither, the fused and bf16 ones no factor), and the caller never asks for it.
+template <bool GP2, bool CSF, class F>
+static inline void dispatch_gp_cs(int gp, bool cs, F&& f) {
+  auto with_gp = [&](auto CS) {
+    if constexpr (GP2) {
+      if (gp == 2) return f(std::integral_constant<int, 2>{}, CS);
+    }
+    f(std::integral_constant<int, 0>{}, CS);
+  };
+  if constexpr (CSF) {
+    if (cs) return with_gp(std::true_type{});
+  }
+  with_gp(std::false_type{});
+}
+
+// The hub rows of a view: one wavefront per chunk of hub_threshold edges -> a partial row in the view's workspace, then one wavefront per hub row sums
+// its partials in chunk order and applies the epilogue (k_spmm_hub_chunks, k_spmm_hub_finish).  ep.col_flags chooses the gather policy (float4 lanes);
+// ep.col_scale the source-row factor (float4 lanes, fp32 rows, plain epilogue: a fused epilogue never takes one).
+template <int VEC, typename HT, bool FUSED, bool MIXB = false>
+static int launch_hub_rows(const cb_csr_view& g, const HT* h, int64_t ld_h, int64_t d, float* out, int64_t ld_out, const Epilogue& ep, const FusedEpi& fe,
+                           hipStream_t st) {
+  if (g.n_hubs <= 0) return CB_OK;
+  const int wpb = 4, ny = (int)((d + kWave * VEC - 1) / (kWave * VEC));
+  const int64_t ld_p = partial_ld(d);
+  float* partial = (float*)g.ws;
+  const dim3 blk(kWave * wpb), gridc((unsigned)((g.n_chunks + wpb - 1) / wpb), ny), gridf((unsigned)((g.n_hubs + wpb - 1) / wpb), ny);
+  dispatch_gp_cs<VEC == 4, VEC == 4 && !FUSED && sizeof(HT) == 4>(ep.col_flags ? 2 : 0, ep.col_scale != nullptr, [&](auto GP, auto CS) {
+    hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, decltype(GP)::value, decltype(CS)::value>), gridc, blk, 0, st, g.rowptr, g.col, h, ld_h, (int)d,
+                       g.hub_threshold, g.n_hubs, g.n_chunks, g.hub_rows, g.hub_chunk_ptr, partial, ld_p, ep);
+  });
+  CB_LAUNCH_CHECK();
+  hipLaunchKernelGGL((k_spmm_hub_finish<VEC, FUSED, MIXB>), gridf, blk, 0, st, (int)d, g.n_hubs, g.hub_rows, g.hub_chunk_ptr, partial, ld_p, out, ld_out, ep, fe);
+  CB_LAUNCH_CHECK();
   return CB_OK;
 }
 

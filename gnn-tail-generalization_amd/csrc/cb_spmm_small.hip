@@ -17,6 +17,7 @@
 // of the stream exactly as in cb_spmm.hip and reduced by k_small_hub_chunks (one wavefront per chunk of T edges, groups
 // take edges round-robin, one cross-group reduction at the end) + k_small_hub_finish.
 #include "cb_common.h"
+#include "cb_spmm_core.h"
 #include "cb_spmm_small.h"
 
 namespace cb {
@@ -179,11 +180,10 @@ __global__ void __launch_bounds__(256) k_spmm_small(const int* __restrict__ rowp
   if (r0 >= n_rows) return;
   const int nr = min(RPW, n_rows - r0);
   const int c0 = (lane % G) * VEC;
-  const int my_ptr = __builtin_nontemporal_load(rowptr + r0 + min(lane, nr));
-  float my_scale = 1.f;
-  if (ep.row_scale && lane < nr) my_scale = __builtin_nontemporal_load(ep.row_scale + r0 + lane);
-  const int nxt = __shfl_down(my_ptr, 1);
-  const unsigned long long hubmask = __ballot(lane < nr && (nxt - my_ptr) > hub_T);
+  const auto blk = load_row_block<false>(rowptr, ep.row_scale, hub_T, r0, nr);      // (cb_spmm_core.h)
+  const int my_ptr = blk.my_ptr;
+  const float my_scale = blk.my_scale;
+  const unsigned long long hubmask = blk.hubmask;
   float bvec[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) bvec[i] = (ep.bias && c0 + i < d) ? ep.bias[c0 + i] : 0.f;
