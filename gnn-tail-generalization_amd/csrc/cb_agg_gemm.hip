@@ -166,52 +166,87 @@ __device__ __forceinline__ void ag2_gather_tile(int t, float* __restrict__ tile,
 }
 
 // One K step of B fragments in flight per multiplying wavefront (two register buffers, K loop unrolled by two): next to wavefronts that
-// keep dozens of gathers outstanding, a load of this CU — L2 hit or not — comes back after microseconds.
+// keep dozens of gathers outstanding, a load of this CU — L2 hit or not — comes back after microseconds.  For the same reason the tails below
+// put NO load between their stores (profiles/tail_loads.md): what an epilogue reads per row (row scale, row id, mixed-in row index) is loaded
+// once per tile BEFORE the K loop, one row per lane (lane l: tile row l; lanes past the tile's last row read nothing), and reaches the epilogue
+// by a lane exchange; what it reads per column (bias) is loaded once per wavefront, outside the tile loop.  On gfx9 vmcnt counts stores as
+// well as loads, so a load between two stores makes its wait cover the earlier store: sixteen serial round trips per tile before.
+__device__ __forceinline__ float tile_lane_scale(const float* __restrict__ rowscale, int r0, int lane, int n_rows) {
+  return (rowscale && r0 + lane < n_rows) ? rowscale[(int64_t)r0 + lane] : 1.f;
+}
+
+// The lane id as a value the compiler must take as new in every tile.  What a tail derives from it (the sixteen source lanes of a tile's lane
+// exchanges, the addresses of the per-lane row loads) would otherwise be invariants of the persistent tile loop, hoisted out of it and kept in
+// registers across the K loop: spills.
+__device__ __forceinline__ int tile_variant(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
 __device__ __forceinline__ void ag2_mfma_tile(int t, const float* __restrict__ tile, float* __restrict__ cs, int w, int lane, int n_rows,
                                               const GemmTail& gt, int* freed) {
   const int l31 = lane & 31, lh = lane >> 5;
+  const int r0 = t * kTM;
+  const int lane_v = tile_variant(lane), lrow = lane_v >> 4;
+  const float rs_lane = tile_lane_scale(gt.rowscale, r0, lane_v, n_rows);      // (in flight under the K loop)
   f32x16 acc[2][2];
   tile_times_image<kNS, kTLD>(tile, gt.image, w, lane, acc);
   ag_signal(freed, lane);      // the tile has been read for the last time
   // epilogue through a WAVE-PRIVATE staging strip (the tile itself is still being read by the other three multiplying wavefronts
   // and there is no barrier among four of twelve wavefronts): 8 rows x 64 columns per pass, transposed so that a lane applies
-  // `rowscale * acc + addend` on a float4 and the strip leaves as 256-byte row segments
-  const int r0 = t * kTM;
+  // `rowscale * acc + addend` on a float4 and the strip leaves as 256-byte row segments.  Two copies, with and without an addend: without
+  // one (the training step) the sixteen stores of a tile follow each other with no wait on memory in between; with one, a pass's two addend
+  // vectors are fetched before the pass's transposition.
   const float zero_bias = 0.f;      // (keeps the epilogue expression of cb_gemm_core.h's nn_epilogue: o * rs + addend + bias)
+  auto epilogue = [&](auto HAS_ADD) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < 4; ++q) {
+        const int mt0 = 32 * i + 8 * q + lrow;      // tile row of half 0; half 1: + 4
+        float ad[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        if constexpr (decltype(HAS_ADD)::value) {
 #pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cs[(r4 + 4 * lh) * kCLD + 32 * j + l31] = acc[i][j][4 * q + r4];
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int idx = lane + 64 * half, row = idx >> 4, c4 = (idx & 15) * 4;
-        const int64_t m = r0 + 32 * i + 8 * q + row;
-        const float4 v = *reinterpret_cast<const float4*>(cs + row * kCLD + c4);
-        if (m < n_rows) {
-          const int n = 64 * w + c4;
-          const float rs = gt.rowscale ? gt.rowscale[m] : 1.f;
-          float ad[4] = {0.f, 0.f, 0.f, 0.f};
-          if (gt.addend) {
-            const float4 a4 = *reinterpret_cast<const float4*>(gt.addend + m * gt.ld_add + n);
-            ad[0] = a4.x; ad[1] = a4.y; ad[2] = a4.z; ad[3] = a4.w;
+          for (int half = 0; half < 2; ++half) {
+            const int64_t m = (int64_t)r0 + mt0 + 4 * half;      // (rows past the end re-read the last row, unused: unpredicated loads keep the waits counted)
+            gather<4>(ad[half], gt.addend + (m < n_rows ? m : (int64_t)n_rows - 1) * gt.ld_add + 64 * w + (lane & 15) * 4);
           }
-          float o[4] = {v.x, v.y, v.z, v.w};
+        }
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = o[e] * rs + ad[e] + zero_bias;
-          store_stream<4>(gt.out + m * gt.ld_out + n, o);
+        for (int r4 = 0; r4 < 4; ++r4)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) cs[(r4 + 4 * lh) * kCLD + 32 * j + l31] = acc[i][j][4 * q + r4];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const int idx = lane + 64 * half, row = idx >> 4, c4 = (idx & 15) * 4;
+          const int64_t m = r0 + 32 * i + 8 * q + row;
+          const float4 v = *reinterpret_cast<const float4*>(cs + row * kCLD + c4);
+          const float rs = __shfl(rs_lane, mt0 + 4 * half);      // (every lane takes part: the source lane may hold a row past the end)
+          if (m < n_rows) {
+            const int n = 64 * w + c4;
+            float o[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = o[e] * rs + ad[half][e] + zero_bias;
+            store_stream<4>(gt.out + m * gt.ld_out + n, o);
+          }
         }
       }
-    }
+  };
+  if (gt.addend) epilogue(std::true_type{});
+  else epilogue(std::false_type{});
 }
 
 // NARROW tail: multiplying wavefront w takes the 32 x 32 block (rows 32 (w & 1), columns 32 (w >> 1)) of the tile's 64 x 64 output = the
 // logits of 64 rows (C <= 64 classes): out = acc + bias, the epilogue expression of cb_gemm_nn_f32 with a bias and neither row scale nor addend.
+// hb = the bias of this lane's four columns (head_lane_bias: loaded once per wavefront, zero beyond n_out or without a bias)
+__device__ __forceinline__ void head_lane_bias(const GemmTail& gt, int w, int lane, float (&hb)[4]) {
+  const int n = 32 * (w >> 1) + (lane & 7) * 4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) hb[e] = (gt.bias && n + e < gt.n_out) ? gt.bias[n + e] : 0.f;
+}
+
 __device__ __forceinline__ void ag2_mfma_tile_head(int t, const float* __restrict__ tile, float* __restrict__ cs, int w, int lane, int n_rows,
-                                                   const GemmTail& gt, int* freed) {
+                                                   const GemmTail& gt, int* freed, const float (&hb)[4]) {
   const int l31 = lane & 31, lh = lane >> 5, bi = w & 1, bj = w >> 1;
   f32x16 acc;
   tile_times_image_block<kNS, kTLD>(tile, gt.image, bi, bj, lane, acc);
@@ -229,7 +264,7 @@ __device__ __forceinline__ void ag2_mfma_tile_head(int t, const float* __restric
       const float zero_add = 0.f;
       float o[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = o[e] * 1.f + zero_add + ((gt.bias && n + e < gt.n_out) ? gt.bias[n + e] : 0.f);
+      for (int e = 0; e < 4; ++e) o[e] = o[e] * 1.f + zero_add + hb[e];
       float* dst = gt.out + m * gt.ld_out + n;
       if (n + 4 <= gt.n_out && (gt.ld_out & 3) == 0) {
         store_stream<4>(dst, o);
@@ -246,72 +281,104 @@ __device__ __forceinline__ void ag2_mfma_tile_head(int t, const float* __restric
 // each of the row's four mask words (word e, bit L <-> column 4 L + e).  Its pieces go to the tile's 2 KB of LDS words (ushort w of word e of
 // tile row mt); the LAST of the four wavefronts to finish the tile (LDS counter mw_cnt, no barrier) writes the assembled words, one 16-byte
 // vector store per two words, and releases the buffer (mw_done: the pieces of buffer b's next tile wait for it).
+// Per row the tail needs the node row id (Philox counter, mask-word address), the row scale and the mixed-in row's index: loaded one row per
+// lane before the K loop.  The mixed-in rows themselves are gathered one pass ahead of their use (two register sets), so that a wait for
+// them never covers a load issued in the same pass.  bias_lds = the 256 bias values (zeros without a bias), put into LDS once per block: four
+// registers held across the K loop are four too many here (the kernel sits at its register limit).
 __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restrict__ tile, float* __restrict__ cs, int w, int lane, int n_rows,
                                                    const GemmTail& gt, uint64_t seed_eff, int* freed, unsigned short* __restrict__ words,
-                                                   int* mw_cnt, int* mw_done, int use) {
+                                                   int* mw_cnt, int* mw_done, int use, const float* __restrict__ bias_lds) {
   const int l31 = lane & 31, lh = lane >> 5;
-  f32x16 acc[2][2];
-  tile_times_image<kNS, kTLD>(tile, gt.image, w, lane, acc);
-  ag_signal(freed, lane);      // the tile has been read for the last time
-  if (gt.st.bits && use > 0) ag_wait(mw_done, use, gt.err);      // the words of this buffer's previous tile have left
   const int r0 = t * kTM;
   const int n = 64 * w + (lane & 15) * 4;
-  float bv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (gt.bias) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bv[e] = gt.bias[n + e];
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cs[(r4 + 4 * lh) * kCLD + 32 * j + l31] = acc[i][j][4 * q + r4];
+  // lane l: tile row l
+  const int lane_v = tile_variant(lane), lrow = lane_v >> 4;
+  const int64_t m_lane = (int64_t)r0 + lane_v;
+  const bool live_lane = m_lane < n_rows;
+  const long long gm_lane = live_lane ? (long long)gt.row_ids[m_lane] : 0ll;
+  const float rs_lane = tile_lane_scale(gt.rowscale, r0, lane_v, n_rows);
+  // (store_mix_row: mix_index[m] where the store has a mix_index, the node row otherwise — chosen after the exchange, so that nothing here waits for gm_lane)
+  const long long mixi_lane = (live_lane && gt.st.mix_src && gt.st.mix_index) ? (long long)gt.st.mix_index[m_lane] : 0ll;
+  f32x16 acc[2][2];
+  int64_t image_off = 0;
+  asm volatile("" : "+s"(image_off));      // (tile-variant as well: the K loop's start addresses are not kept as invariants beside its running ones)
+  tile_times_image<kNS, kTLD>(tile, gt.image + image_off, w, lane, acc);
+  ag_signal(freed, lane);      // the tile has been read for the last time
+  if (gt.st.bits && use > 0) ag_wait(mw_done, use, gt.err);      // the words of this buffer's previous tile have left
+  const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + n);
+  const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+  auto epilogue = [&](auto MIX) {
+    constexpr bool kMix = decltype(MIX)::value;
+    float qn[2][2][4];      // the mixed-in rows of two passes: [pass parity][half]
+    auto fetch_mix = [&](int pass, float (&dst)[2][4]) {
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
-        const int idx = lane + 64 * half, row = idx >> 4, c4 = (idx & 15) * 4;
-        const int mt = 32 * i + 8 * q + row;
-        const int64_t m = r0 + mt;
-        const float4 v = *reinterpret_cast<const float4*>(cs + row * kCLD + c4);
-        const bool live = m < n_rows;
-        float o[4] = {v.x, v.y, v.z, v.w}, mk[4] = {1.f, 1.f, 1.f, 1.f};
-        int64_t gm = 0;
-        if (live) {      // nn_epilogue's expression (cb_gemm_core.h), then the store's steps (cb_trunk_store.h)
-          gm = gt.row_ids[m];
-          const float rs = gt.rowscale ? gt.rowscale[m] : 1.f;
-          const float ad[4] = {0.f, 0.f, 0.f, 0.f};
+        const int mt = 8 * pass + 4 * half + lrow;
+        const long long mr = __shfl(gt.st.mix_index ? mixi_lane : gm_lane, mt);
+        gather<4>(dst[half], gt.st.mix_src + mr * gt.st.ld_mix + n);      // (rows past the end: mr == 0, row 0 of mix_src, unused — unpredicated, so that the waits stay counted)
+      }
+    };
+    if constexpr (kMix) fetch_mix(0, qn[0]);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            o[e] = o[e] * rs + ad[e] + bv[e];
-            o[e] = fmaxf(o[e], 0.f);
-          }
-          store_keep4(gt.st, seed_eff, gm, kND, n, mk);
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int pass = 4 * i + q;
+        if constexpr (kMix) {
+          if (pass + 1 < 8) fetch_mix(pass + 1, qn[(pass + 1) & 1]);
         }
-        if (gt.st.bits) {
-          // ballot e: bits 16 k .. 16 k + 15 = row (lane >> 4 == k) of this pass, columns 64 w .. 64 w + 63 -> bits 16 w .. of word e
-          unsigned long long bal[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) bal[e] = __ballot(live && store_passes_grad(gt.st, o[e], mk[e]));
-          if (lane < 16) {
-            const int k = lane >> 2, e = lane & 3;
-            unsigned long long be = bal[0];
+        for (int r4 = 0; r4 < 4; ++r4)
 #pragma unroll
-            for (int f = 1; f < 4; ++f) if (e == f) be = bal[f];
-            const int mtk = 32 * i + 8 * q + 4 * half + k;
-            words[(mtk * 4 + e) * 4 + w] = (unsigned short)(be >> (16 * k));
+          for (int j = 0; j < 2; ++j) cs[(r4 + 4 * lh) * kCLD + 32 * j + l31] = acc[i][j][4 * q + r4];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const int idx = lane + 64 * half, row = idx >> 4, c4 = (idx & 15) * 4;
+          const int mt = 32 * i + 8 * q + row, mts = 32 * i + 8 * q + 4 * half + lrow;      // (mts == mt, tile-variant for the compiler)
+          const int64_t m = r0 + mt;
+          const float4 v = *reinterpret_cast<const float4*>(cs + row * kCLD + c4);
+          const bool live = m < n_rows;
+          const int64_t gm = __shfl(gm_lane, mts);      // (every lane takes part: the source lane may hold a row past the end)
+          const float rs = __shfl(rs_lane, mts);
+          float o[4] = {v.x, v.y, v.z, v.w}, mk[4] = {1.f, 1.f, 1.f, 1.f};
+          if (live) {      // nn_epilogue's expression (cb_gemm_core.h), then the store's steps (cb_trunk_store.h)
+            const float ad[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              o[e] = o[e] * rs + ad[e] + bv[e];
+              o[e] = fmaxf(o[e], 0.f);
+            }
+            store_keep4(gt.st, seed_eff, gm, kND, n, mk);
           }
-        }
-        if (live) {
-          if (gt.st.out_act) store_stream<4>(gt.st.out_act + m * gt.st.ld_act + n, o);
-          float qv[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
-          if (gt.st.mix_src) gather<4>(qv, gt.st.mix_src + store_mix_row(gt.st, m, gm) * gt.st.ld_mix + n);
-          store_value(gt.st, o, qv, mk, x);
-          store_stream<4>(gt.out + m * gt.ld_out + n, x);
+          if (gt.st.bits) {
+            // ballot e: bits 16 k .. 16 k + 15 = row (lane >> 4 == k) of this pass, columns 64 w .. 64 w + 63 -> bits 16 w .. of word e
+            unsigned long long bal[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bal[e] = __ballot(live && store_passes_grad(gt.st, o[e], mk[e]));
+            if (lane < 16) {
+              const int k = lane >> 2, e = lane & 3;
+              unsigned long long be = bal[0];
+#pragma unroll
+              for (int f = 1; f < 4; ++f) if (e == f) be = bal[f];
+              const int mtk = 32 * i + 8 * q + 4 * half + k;
+              words[(mtk * 4 + e) * 4 + w] = (unsigned short)(be >> (16 * k));
+            }
+          }
+          if (live) {
+            if (gt.st.out_act) store_stream<4>(gt.st.out_act + m * gt.st.ld_act + n, o);
+            float qv[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
+            if constexpr (kMix) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) qv[e] = qn[pass & 1][half][e];
+            }
+            store_value(gt.st, o, qv, mk, x);
+            store_stream<4>(gt.out + m * gt.ld_out + n, x);
+          }
         }
       }
-    }
+  };
+  if (gt.st.mix_src) epilogue(std::true_type{});
+  else epilogue(std::false_type{});
   if (gt.st.bits) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wavefront's pieces are in LDS
     int prev = 0;
@@ -319,11 +386,10 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
     prev = __shfl(prev, 0);
     asm volatile("" ::: "memory");
     if (prev == 4 * use + 3) {      // the last of the four: every piece of the tile is in place
-      const int64_t m = r0 + lane;
-      if (m < n_rows) {
+      if (live_lane) {
         const uint4* src = reinterpret_cast<const uint4*>(words + lane * 16);
         const uint4 w01 = src[0], w23 = src[1];
-        uint4* dst = reinterpret_cast<uint4*>(gt.st.bits + gt.row_ids[m] * 4);
+        uint4* dst = reinterpret_cast<uint4*>(gt.st.bits + gm_lane * 4);
         dst[0] = w01;
         dst[1] = w23;
       }
@@ -342,12 +408,16 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
   __shared__ int ready[2], freed[2];
   __shared__ __attribute__((aligned(16))) unsigned short mwords[SR ? 2 : 1][SR ? kTM * 16 : 8];      // SR: the tile's mask words, in pieces
   __shared__ int mw_cnt[2], mw_done[2];
+  __shared__ __attribute__((aligned(16))) float sr_bias[SR ? kND : 4];      // SR: the tail's bias (zeros without one)
   const int lane = lane_id(), wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (wave-uniform by construction: tell the compiler, so that what derives from it stays in SGPRs)
   const bool gathers = wv < kNG;
   const int w = gathers ? wv : wv - kNG;
   const int n_it = ((int)blockIdx.x < n_tiles) ? (n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
   const uint64_t seed_eff = SR ? store_seed(gt.st) : 0ull;
   if (threadIdx.x < 2) ready[threadIdx.x] = freed[threadIdx.x] = mw_cnt[threadIdx.x] = mw_done[threadIdx.x] = 0;
+  if constexpr (SR) {
+    if (threadIdx.x < kND) sr_bias[threadIdx.x] = gt.bias ? gt.bias[threadIdx.x] : 0.f;
+  }
   __syncthreads();
   if (gathers) {
     for (int it = 0; it < n_it; ++it) {
@@ -357,12 +427,15 @@ __global__ void __launch_bounds__(64 * (kNG + 4), (kNG + 4) / 4) k_agg_gemm2(con
       ag_signal(&ready[b], lane);
     }
   } else {
+    float head_bias[4] = {0.f, 0.f, 0.f, 0.f};      // NARROW: the bias of this lane's columns, once per wavefront
+    if constexpr (NARROW) head_lane_bias(gt, w, lane, head_bias);
     for (int it = 0; it < n_it; ++it) {
       const int b = it & 1, use = it >> 1;
       ag_wait(&ready[b], kNG * (use + 1), gt.err);
-      if constexpr (NARROW) ag2_mfma_tile_head(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b]);
+      if constexpr (NARROW) ag2_mfma_tile_head(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b], head_bias);
       else if constexpr (SR)
-        ag2_mfma_tile_rows(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, seed_eff, &freed[b], mwords[b], &mw_cnt[b], &mw_done[b], use);
+        ag2_mfma_tile_rows(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, seed_eff, &freed[b], mwords[b], &mw_cnt[b], &mw_done[b], use,
+                           sr_bias);
       else ag2_mfma_tile(blockIdx.x + it * gridDim.x, tiles[b], cstrip[w], w, lane, n_rows, gt, &freed[b]);
     }
   }

@@ -20,6 +20,8 @@
 // pass and stores), so what the kernel buys is the 20 GB of traffic, not yet an overlap of its own phases.
 // Bit-identical to the two-kernel form: same operand values (dropout products rounded to fp32 before the limb split), same limb products
 // in the same order, same epilogue expressions (tests/test_gpu_kernels.py::test_forward_front_*).
+#include <type_traits>
+
 #include "cb_common.h"
 #include "cb_limb_core.h"
 #include "cb_philox.h"
@@ -79,16 +81,23 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
       xr[j] = (tile_id < fa.n_tiles && m < fa.M) ? *reinterpret_cast<const float4*>(fa.x + m * fa.ld_x + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
+  // row scale of tile row t of a tile (threads 0 .. 63), 1 past the end: issued AHEAD of the tile's x loads, so that the wait for x covers it
+  float rs_next = 1.f;
+  auto load_rs = [&](int tile_id) {
+    const int64_t m = (int64_t)tile_id * kTM + t;
+    rs_next = (t < kTM && fa.rowscale && tile_id < fa.n_tiles && m < fa.M) ? fa.rowscale[m] : 1.f;
+  };
   float bvec[4] = {0.f, 0.f, 0.f, 0.f};
   if (fa.bias_in) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) bvec[i] = fa.bias_in[4 * lane + i];
   }
+  load_rs(blockIdx.x);
+  load_x(blockIdx.x);
   int par = 0;
   for (int tile_id = blockIdx.x; tile_id < fa.n_tiles; tile_id += gridDim.x, par ^= 1) {
     const int64_t m0 = (int64_t)tile_id * kTM;
-    load_x(tile_id);      // (not prefetched across the GEMMs: those registers hold a third ring buffer of B fragments instead; the block that
-                          //  shares the CU multiplies while this one waits)
+    // xr / rs_next hold THIS tile's x and row scales: their loads were issued before the previous tile's Z0 epilogue (the first tile's: above)
     // ---- P0: dropout of x (the product cb_dropout_f32 forms, rounded to fp32 as a value of its own) -> LDS
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -102,7 +111,7 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
       }
       *reinterpret_cast<float4*>(tile + row * LDX + 4 * c4) = make_float4(v[0], v[1], v[2], v[3]);
     }
-    if (t < kTM) rs_tile[par][t] = (fa.rowscale && m0 + t < fa.M) ? fa.rowscale[m0 + t] : 1.f;      // (read in P4's epilogue: four barriers later)
+    if (t < kTM) rs_tile[par][t] = rs_next;      // (read in P4's epilogue: four barriers later)
     __syncthreads();
     // ---- P1: X0 pre-activation = tile(x) @ W_in^T
     f32x16 acc[2][2];
@@ -149,22 +158,33 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
     __syncthreads();
     // ---- P4: Z0 = rowscale . (tile(X0d) @ W_0) + addend
     tile_times_image_coop<kNS, kTLD, 1>(tile, scratch, fa.image_0, w, lane, t, acc);      // (ends with a block barrier: tile and planes are dead; the strips are wave-private)
-    acc_rows_through_strip(acc, cstrip[w], w, lane, [&](int row, int n, const float4& v) {
-      const int64_t m = m0 + row;
-      if (m < fa.M) {
-        const float rs = rs_tile[par][row];
-        float ad[4] = {0.f, 0.f, 0.f, 0.f};
-        if (fa.addend) {
-          const float4 a4 = *reinterpret_cast<const float4*>(fa.addend + m * fa.ld_add + n);
-          ad[0] = a4.x; ad[1] = a4.y; ad[2] = a4.z; ad[3] = a4.w;
-        }
-        const float zero_bias = 0.f;      // (the epilogue expression of cb_gemm_core.h's nn_epilogue: o * rs + addend + bias)
-        float o[4] = {v.x, v.y, v.z, v.w};
+    // the NEXT tile's row scales and x (zeros / 1 past the last tile), issued after the last B fragment load of the tile: they fly under the Z0 epilogue, whose
+    // stores wait for nothing, and are waited for at the top of the next tile.  (Issued before P4 they would be held across its K loop — 256 registers and a
+    // spill at K1 = 128 — and, loads completing in order, be waited for with the K loop's first B fragment.)
+    load_rs(tile_id + gridDim.x);
+    load_x(tile_id + gridDim.x);
+    // two copies, with and without an addend: without one (the training step) the tile's sixteen Z0 stores follow each other with no wait on memory in
+    // between (vmcnt counts stores too: a load, or a wait the two cases share, between two stores waits for the earlier store to complete)
+    auto z0_epilogue = [&](auto HAS_ADD) {
+      acc_rows_through_strip(acc, cstrip[w], w, lane, [&](int row, int n, const float4& v) {
+        const int64_t m = m0 + row;
+        if (m < fa.M) {
+          const float rs = rs_tile[par][row];
+          float ad[4] = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (decltype(HAS_ADD)::value) {
+            const float4 a4 = *reinterpret_cast<const float4*>(fa.addend + m * fa.ld_add + n);
+            ad[0] = a4.x; ad[1] = a4.y; ad[2] = a4.z; ad[3] = a4.w;
+          }
+          const float zero_bias = 0.f;      // (the epilogue expression of cb_gemm_core.h's nn_epilogue: o * rs + addend + bias)
+          float o[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] * rs + ad[e] + zero_bias;
-        store_stream4(fa.z0 + m * fa.ld_z + n, o);
-      }
-    });
+          for (int e = 0; e < 4; ++e) o[e] = o[e] * rs + ad[e] + zero_bias;
+          store_stream4(fa.z0 + m * fa.ld_z + n, o);
+        }
+      });
+    };
+    if (fa.addend) z0_epilogue(std::true_type{});
+    else z0_epilogue(std::false_type{});
   }
 }
 
