@@ -8,16 +8,17 @@
 // 64 rows of X0d in LDS and multiplies them by W_0 before anything else is read: 10 GB of writes and 10 GB of reads per step disappear.
 //
 // One persistent block of 4 wavefronts per slot (two slots per CU: 75 KB of LDS each), tiles of 64 rows, per tile
-//   P0  the tile of x -> dropout -> fp32 LDS tile [64][K1 + 4]
+//   P0  the tile of x -> dropout (keep bits drawn earlier, see k_front) -> fp32 LDS tile [64][K1 + 4]
 //   P1  tile x W_in^T on the matrix cores (tile_times_image_coop: three-limb bf16 products, A limbs split once per K step into LDS planes, B fragments
-//       from the L2-resident image)
+//       from the L2-resident image); between its MFMAs: the Philox keep bits of P0 of the block's next tile
 //   P2  accumulators -> the SAME LDS region as a [64][260] tile (the x tile is dead)
 //   P3  row pass: a wavefront owns 16 rows, a lane 4 columns: + bias, ReLU -> X0 row store (1 KiB, streaming), four ballots = the row's mask
-//       words, Philox keep-mask of the dropout in front of layer 0 -> X0d back into the tile (-> out_drop row store if requested)
-//   P4  tile x W_0 on the matrix cores -> rowscale . acc + addend -> Z0 through wave-private strips
+//       words, keep-mask of the dropout in front of layer 0 (bits drawn earlier) -> X0d back into the tile (-> out_drop row store if requested)
+//   P4  tile x W_0 on the matrix cores -> rowscale . acc + addend -> Z0 through wave-private strips; between its MFMAs: the keep bits of P3 of the next tile
 // Two blocks share a CU.  Measured (profiles/r04_front_kernel.md): 14.4 ms at the headline shape against 15.3 ms for the two kernels; the
 // co-resident blocks fall into lock step (the phases' times add up: 8.9 ms of K loops at 52 % of the bf16 MFMA peak + 5.4 ms of loads, row
-// pass and stores), so what the kernel buys is the 20 GB of traffic, not yet an overlap of its own phases.
+// pass and stores), so what the kernel buys is the 20 GB of traffic, not yet an overlap of its own phases.  What does overlap is vector-ALU work inside a
+// wavefront's own MFMA stream: with the 24 Philox draws of a tile moved from P0 / P3 into the K loops the kernel runs 13.3 -> 12.4 ms (profiles/mask_draws.md).
 // Bit-identical to the two-kernel form: same operand values (dropout products rounded to fp32 before the limb split), same limb products
 // in the same order, same epilogue expressions (tests/test_gpu_kernels.py::test_forward_front_*).
 #include <type_traits>
@@ -55,10 +56,18 @@ struct FrontArgs {
   int n_tiles;
 };
 
-template <int NS1>      // K1 = 16 * NS1 input features
+// DROP: fa.thresh != 0.  The keep decisions of both dropouts are functions of (seed, flat index) alone, so they are drawn where the vector ALU is otherwise
+// idle — one Philox quad per K step, issued between the step's MFMAs (tile_times_image_coop's side work) — and carried as bits to the phases that use them:
+//   kx  P0's mask of a tile: the thread's NV = NS1 quads = 4 NS1 <= 32 bits, drawn under P1 of the block's PREVIOUS tile (NS1 steps)
+//   k3  P3's mask of a tile: the lane's 16 quads (rows 16 w .. 16 w + 15, columns 4 lane ..) = 64 bits, drawn under P4 of the previous tile (16 steps)
+// Both words are shift registers (a draw enters at the top, the first draw ends up in the lowest bits) and the quad counters run, so a draw does not depend
+// on the K step's number: no select and no branch enters the steps.  The block's first tile has no previous one: its masks are drawn before the loop, under
+// its x loads.  Past the block's last tile the draws are made and never read.  Same decisions, same products (bit ? keep_scale : 0 is keep4's m[i]).
+template <int NS1, bool DROP>      // K1 = 16 * NS1 input features
 __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
   constexpr int K1 = 16 * NS1, LDX = K1 + 4, NV = kTM * K1 / 4 / 256;      // float4 of x per thread per tile
   static_assert(NV >= 1 && kTM * LDX <= kTM * kTLD, "x tile must fit the region of the X0 tile");
+  static_assert(NV == NS1 && NS1 <= 8, "mask draws: one quad per K step, P0's bits in one word");
   __shared__ __attribute__((aligned(16))) float tile[kTM * kTLD];
   // Round 6: the K loops split the A tile's limbs ONCE per element (tile_times_image_coop: the block's 256 threads split each K step's 64 x 16 slab into
   // bf16 planes, every wavefront reads its fragments from them) instead of once per multiplying wavefront: 14.3 -> 13.7 ms at the headline shape, bit-identical
@@ -94,6 +103,36 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
   }
   load_rs(blockIdx.x);
   load_x(blockIdx.x);
+  uint32_t kx = 0;
+  uint64_t k3 = 0;
+  int64_t qx = 0, q3 = 0;      // running quad counters of the draws
+  auto aim_x = [&](int tile_id) { qx = (fa.row0 + (int64_t)tile_id * kTM) * (K1 / 4) + t; };             // quad of float4 j of the thread: + 256 j
+  auto aim_3 = [&](int tile_id) { q3 = (fa.row0 + (int64_t)tile_id * kTM + 16 * w) * (kND / 4) + lane; };      // quad of row r of the wavefront: + 64 r
+  // (the empty asm pins a draw to the K step it was written in: without it the compiler sinks the draws of several steps into one)
+  // (... and the one on the seed keeps the twenty round keys of a draw from becoming invariants of the tile loop: 40 scalar registers, which then spill)
+  auto draw_x = [&](int) {
+    uint64_t seed = sx;
+    asm volatile("" : "+s"(seed));
+    kx = (kx >> 4) | (keep4_bits(seed, qx, fa.thresh) << 28);
+    qx += 256;
+    asm volatile("" : "+v"(kx));
+  };
+  auto draw_3 = [&](int) {
+    uint64_t seed = s0;
+    asm volatile("" : "+s"(seed));
+    k3 = (k3 >> 4) | ((uint64_t)keep4_bits(seed, q3, fa.thresh) << 60);
+    q3 += kND / 4;
+    asm volatile("" : "+v"(k3));
+  };
+  if constexpr (DROP) {
+    aim_x(blockIdx.x);
+    aim_3(blockIdx.x);
+#pragma unroll 1
+    for (int s = 0; s < 16; ++s) {
+      if (s < NS1) draw_x(s);
+      draw_3(s);
+    }
+  }
   int par = 0;
   for (int tile_id = blockIdx.x; tile_id < fa.n_tiles; tile_id += gridDim.x, par ^= 1) {
     const int64_t m0 = (int64_t)tile_id * kTM;
@@ -103,19 +142,19 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
     for (int j = 0; j < NV; ++j) {
       const int idx = t + 256 * j, row = idx / (K1 / 4), c4 = idx % (K1 / 4);
       float v[4] = {xr[j].x, xr[j].y, xr[j].z, xr[j].w};
-      if (fa.thresh) {
-        float mk[4];
-        keep4(sx, ((fa.row0 + m0 + row) * K1 + 4 * c4) >> 2, fa.thresh, fa.keep_scale, mk);
+      if constexpr (DROP) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = mul_rounded(v[i], mk[i]);
+        for (int i = 0; i < 4; ++i) v[i] = mul_rounded(v[i], (kx >> (32 - 4 * NV + 4 * j + i)) & 1u ? fa.keep_scale : 0.f);
       }
       *reinterpret_cast<float4*>(tile + row * LDX + 4 * c4) = make_float4(v[0], v[1], v[2], v[3]);
     }
+    if constexpr (DROP) aim_x(tile_id + (int)gridDim.x);
     if (t < kTM) rs_tile[par][t] = rs_next;      // (read in P4's epilogue: four barriers later)
     __syncthreads();
     // ---- P1: X0 pre-activation = tile(x) @ W_in^T
     f32x16 acc[2][2];
-    tile_times_image_coop<NS1, LDX, 1>(tile, scratch, fa.image_in, w, lane, t, acc);      // (ends with a block barrier: the x tile is dead)
+    if constexpr (DROP) tile_times_image_coop<NS1, LDX, 1>(tile, scratch, fa.image_in, w, lane, t, acc, draw_x);
+    else tile_times_image_coop<NS1, LDX, 1>(tile, scratch, fa.image_in, w, lane, t, acc);      // (ends with a block barrier: the x tile is dead)
     // ---- P2: accumulators -> [64][260] tile (C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
     {
       const int l31 = lane & 31, lh = lane >> 5;
@@ -139,11 +178,10 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) o[i] = fmaxf(o[i] + bvec[i], 0.f);      // nn_epilogue: o * 1 + 0 + bias, then ReLU
       float xd[4] = {o[0], o[1], o[2], o[3]};
-      if (fa.thresh) {
-        float mk[4];
-        keep4(s0, ((fa.row0 + m) * kND + 4 * lane) >> 2, fa.thresh, fa.keep_scale, mk);
+      if constexpr (DROP) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xd[i] = o[i] * mk[i];
+        for (int i = 0; i < 4; ++i) xd[i] = o[i] * ((uint32_t)k3 >> i & 1u ? fa.keep_scale : 0.f);
+        k3 >>= 4;      // (row r's four bits are the lowest)
       }
       *reinterpret_cast<float4*>(tp) = make_float4(xd[0], xd[1], xd[2], xd[3]);
       if (m < fa.M) {      // (wave-uniform)
@@ -157,7 +195,9 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
     }
     __syncthreads();
     // ---- P4: Z0 = rowscale . (tile(X0d) @ W_0) + addend
-    tile_times_image_coop<kNS, kTLD, 1>(tile, scratch, fa.image_0, w, lane, t, acc);      // (ends with a block barrier: tile and planes are dead; the strips are wave-private)
+    if constexpr (DROP) aim_3(tile_id + (int)gridDim.x);
+    if constexpr (DROP) tile_times_image_coop<kNS, kTLD, 1>(tile, scratch, fa.image_0, w, lane, t, acc, draw_3);
+    else tile_times_image_coop<kNS, kTLD, 1>(tile, scratch, fa.image_0, w, lane, t, acc);      // (ends with a block barrier: tile and planes are dead; the strips are wave-private)
     // the NEXT tile's row scales and x (zeros / 1 past the last tile), issued after the last B fragment load of the tile: they fly under the Z0 epilogue, whose
     // stores wait for nothing, and are waited for at the top of the next tile.  (Issued before P4 they would be held across its K loop — 256 registers and a
     // spill at K1 = 128 — and, loads completing in order, be waited for with the K loop's first B fragment.)
@@ -234,8 +274,10 @@ extern "C" int cb_trunk_front_f32(const float* x, int64_t ld_x, int64_t M, int64
   const int blocks = fa.n_tiles < 2 * n_cu ? fa.n_tiles : 2 * n_cu;      // two persistent blocks per CU
   const dim3 grid((unsigned)blocks), blk(256);
   hipStream_t st = (hipStream_t)stream;
-  if (K == 64) hipLaunchKernelGGL((k_front<4>), grid, blk, 0, st, fa);
-  else hipLaunchKernelGGL((k_front<8>), grid, blk, 0, st, fa);
+  if (K == 64 && fa.thresh) hipLaunchKernelGGL((k_front<4, true>), grid, blk, 0, st, fa);
+  else if (K == 64) hipLaunchKernelGGL((k_front<4, false>), grid, blk, 0, st, fa);
+  else if (fa.thresh) hipLaunchKernelGGL((k_front<8, true>), grid, blk, 0, st, fa);
+  else hipLaunchKernelGGL((k_front<8, false>), grid, blk, 0, st, fa);
   CB_LAUNCH_CHECK();
   return CB_OK;
 }

@@ -31,6 +31,17 @@ __device__ __forceinline__ void keep4(uint64_t seed, int64_t quad, uint32_t thre
   for (int i = 0; i < 4; ++i) m[i] = (r[i] >= thresh) ? scale : 0.f;
 }
 
+// the same four decisions as a 4-bit field: bit i = keep(seed, 4*quad + i), so that keep4's m[i] == (bit i ? scale : 0.f).  For kernels that draw a
+// mask ahead of its use (cb_front.hip: under a K loop) and carry it as bits instead of four floats.
+__device__ __forceinline__ uint32_t keep4_bits(uint64_t seed, int64_t quad, uint32_t thresh) {
+  uint32_t r[4];
+  philox4x32_10((uint32_t)quad, (uint32_t)((uint64_t)quad >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  uint32_t f = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) f |= (r[i] >= thresh ? 1u : 0u) << i;
+  return f;
+}
+
 static inline uint32_t dropout_threshold(float p) {
   const double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;

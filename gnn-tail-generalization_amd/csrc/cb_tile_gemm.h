@@ -7,6 +7,8 @@
 //   B operand: the weight, split ONCE per launch by k_weight_image into MFMA fragment order (K x 256 x 6 bytes, L2 resident): a fragment
 //              is one coalesced global_load_dwordx4 per limb, no LDS, no conversion in the K loop.
 #pragma once
+#include <type_traits>
+
 #include "cb_common.h"
 #include "cb_limb_core.h"
 
@@ -108,9 +110,16 @@ __device__ __forceinline__ void tile_times_image(const float* __restrict__ tile,
 // 32-row block) — the K loop's limb-split VALU work drops from 4 x (the whole slab per wavefront) to 1 x, for one block barrier per K step.  Same limb
 // values (split4), same limb products in the same order: bit-identical to tile_times_image.  All four wavefronts of the block must call it together.
 // planes: 2 * RowOperand<kTM>::BYTES bytes of LDS.
-template <int NSTEPS, int TLD, int PF = 1>
+// side: optional side work, side(s) called once per K step s in the basic block of the step's 24 MFMAs, between the last of them and the step's barrier in
+// program order — so that its register-only vector-ALU work, which depends on no data of the product (cb_front.hip: Philox keep-masks of a later phase), is
+// free to issue between the step's MFMAs, after the step's loads, staging and fragment reads, instead of in a phase of its own.  It must not branch, touch
+// memory or synchronise.  NoSideWork: nothing is generated.
+struct NoSideWork {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <int NSTEPS, int TLD, int PF = 1, class Side = NoSideWork>
 __device__ __forceinline__ void tile_times_image_coop(const float* __restrict__ tile, char* __restrict__ planes, const uint4* __restrict__ image, int w, int lane,
-                                                      int t, f32x16 (&acc)[2][2]) {
+                                                      int t, f32x16 (&acc)[2][2], Side&& side = Side{}) {
   using OA = RowOperand<kTM>;
   static_assert(OA::NV == 1 && PF >= 1 && PF <= 3 && PF < NSTEPS, "64-row tiles, one float4 of the slab per thread");
 #pragma unroll
@@ -165,6 +174,15 @@ __device__ __forceinline__ void tile_times_image_coop(const float* __restrict__ 
       CB_TG_MFMA2(a_hi, 1)
       CB_TG_MFMA2(a_hi, 0)
 #undef CB_TG_MFMA2
+    }
+    side(s);
+    if constexpr (!std::is_same_v<std::decay_t<Side>, NoSideWork>) {
+      // spread the side work evenly: left alone the scheduler issues most of the step's MFMAs first and the side work behind them
+#pragma unroll
+      for (int k = 0; k < 24; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // four vector-ALU instructions
+      }
     }
     __syncthreads();      // the slab of step s + 1 is staged; every wavefront has read the planes of step s
   };
