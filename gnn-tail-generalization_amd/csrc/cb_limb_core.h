@@ -12,15 +12,9 @@ namespace cb {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// a == hi + mid + lo exactly, each limb a bf16 obtained by round-to-nearest-even (v_cvt_pk_bf16_f32) of what is left:
+// a == hi + mid + lo exactly, each limb a bf16 obtained by round-to-nearest-even (v_cvt_pk_bf16_f32: cvt_pk_bf16 of cb_common.h) of what is left:
 // |a - hi| <= 2^-9 |a|, |a - hi - mid| <= 2^-17 |a|, and the last residual has at most 8 significant bits, so its conversion
 // is exact.  Works on pairs because the hardware converts and packs two values per instruction.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float x0, float x1) {   // {bf16(x0), bf16(x1)} in one dword
-  const f32x2 v = {x0, x1};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ void split3x2(float a0, float a1, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
   hi = cvt_pk_bf16(a0, a1);
   const float r0 = a0 - __uint_as_float(hi << 16), r1 = a1 - __uint_as_float(hi & 0xffff0000u);       // exact
