@@ -5,9 +5,15 @@ next to the refusing `layer.SAGE` / `GCN` / `WSAGE` / `MLP` (which keep raising:
     WSAGEEncoder   convs.{i} = PyG GraphConv(add), no edge weight: (A X) lin_rel^T + lin_rel.bias + X lin_root^T
     GCNEncoder     convs.{i} = PyG GCNConv(normalize=False):       (A X) lin^T + bias
     MLPEncoder     convs.{i} = torch.nn.Linear, through gemm.linear
+    TransformerEncoder  convs.{i} = PyG TransformerConv(first, second) with every default (layer.py:77-83): heads = 1, concat, no beta, no edge
+                   features, no attention dropout, bias, root weight.  With Q, K, V, S = lin_query / lin_key / lin_value / lin_skip of X (all with bias):
+                       out[v] = sum_j softmax_j(<Q[v], K[u_j]> / sqrt(out)) V[u_j] + S[v]      over the in-edges (u_j -> v), duplicates each their own term;
+                   a row without in-edges gives S[v].  One stacked GEMM and one attention kernel per layer (ops.transformer_conv, csrc/cb_attn.hip);
+                   out_channels % 4 == 0 and <= 512.  PyG's 1e-16 in the softmax's denominator is dropped (invisible in fp32 once the maximum is
+                   subtracted); heads > 1, edge_dim and beta are not built.
 
 ReLU then dropout after every layer but the last (layer.py:29-35).  forward(x, graph) takes a graph.CSRGraph where the reference takes PyG's adj_t; every
-graph layer is one ops.sage_layer call (csrc/cb_sage.hip where the widths are 256 -> 256, the composed kernels elsewhere).
+SAGE / WSAGE / GCN layer is one ops.sage_layer call (csrc/cb_sage.hip where the widths are 256 -> 256, the composed kernels elsewhere).
 
 Constructor arguments, parameter names and shapes ([out, in]) are PyG's, created layer by layer in PyG's order.  Initial values: every weight and bias
 is drawn by torch.nn.Linear's reset_parameters (kaiming_uniform with a = sqrt(5); GCN's bias likewise from its Linear).  torch_geometric is not
@@ -77,6 +83,25 @@ class GCNConv(torch.nn.Module):
         return ops.sage_layer(graph, x, self.lin.weight, None, self.bias, mode='GCN', relu=relu, p=p)
 
 
+class TransformerConv(torch.nn.Module):
+    """PyG TransformerConv(in_channels, out_channels) with every default: four Linears with bias, created in PyG's order (key, query, value, skip)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        for name in ('lin_key', 'lin_query', 'lin_value', 'lin_skip'):
+            setattr(self, name, torch.nn.Linear(in_channels, out_channels, bias=True))
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):
+            lin.reset_parameters()
+
+    def forward(self, x, graph, relu=False, p=0.0):
+        y = ops.transformer_conv(graph, x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias, self.lin_value.weight,
+                                 self.lin_value.bias, self.lin_skip.weight, self.lin_skip.bias, relu=relu)
+        return ops.dropout(y, p, training=True) if p else y
+
+
 class _Encoder(torch.nn.Module):
     conv = None
 
@@ -114,6 +139,11 @@ class WSAGEEncoder(_Encoder):
 class GCNEncoder(_Encoder):
     """layer.py:61-67 `GCN`."""
     conv = GCNConv
+
+
+class TransformerEncoder(_Encoder):
+    """layer.py:77-83 `Transformer`."""
+    conv = TransformerConv
 
 
 class MLPEncoder(_Encoder):

@@ -203,6 +203,12 @@ SIGNATURES = {
     'cb_sage_layer_supported': (ctypes.c_int, [_I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64]),
     'cb_sage_layer_f32': (ctypes.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I64, _I32,
                                          _P, _I64, _P]),
+    # attention over CSR rows (cb_attn.hip): the view as a plain pointer like cb_sage_layer_f32's; its checks are exercised by tests/test_attn_host.py
+    'cb_attn_supported': (ctypes.c_int, [_I64, _P, _I64]),
+    'cb_attn_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_attn_fwd_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, ctypes.c_int, _P, _I64, _P, _P]),
+    'cb_attn_bwd_dst_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P]),
+    'cb_attn_bwd_src_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P]),
 }
 
 _lib = None

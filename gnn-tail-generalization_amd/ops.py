@@ -1995,3 +1995,137 @@ def sage_layer(graph, x, W_n, W_s=None, bias=None, mode='SAGE', relu=False, p=0.
     if x.shape[1] > 1 and x.stride(1) != 1:
         x = x.contiguous()
     return _SageLayerFn.apply(graph, x, W_n, W_s, bias, mode, bool(relu), p, int(seed or 0), fused)
+
+
+# ---------------------------------------------------------------------------------------------
+# attention over the rows of the CSR: PyG TransformerConv(heads=1) (Link_prediction_model/layer.py:77-83; csrc/cb_attn.hip)
+# ---------------------------------------------------------------------------------------------
+ATTN_MAX_D = 512
+
+
+def _attn_rows(who, d, **named):
+    """Every operand an fp32 [N, d] matrix whose rows the kernels can take (cb_attn_supported); ValueError naming the constraint otherwise."""
+    lib = _lib.load()
+    for name, t in named.items():
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d:
+            raise ValueError(f'{who}: {name} must be a float32 [N, {d}] matrix, got {t.dtype} {tuple(t.shape)}')
+        if not lib.cb_attn_supported(d, _lib.ptr(t), t.stride(0)) or (d > 1 and t.stride(1) != 1):
+            raise ValueError(f'{who}: {name}: rows of D = {d} floats at stride {t.stride(0)} are not built: D % 4 == 0, D <= {ATTN_MAX_D}, 16-byte aligned rows '
+                             f'with contiguous elements and a row stride that is a multiple of 4 and >= D are required')
+
+
+def _attn_graph(who, graph, n):
+    from .graph import CSRGraph
+    if not isinstance(graph, CSRGraph) or graph.n_cols != graph.N or graph.N != n:
+        raise ValueError(f'{who}: the whole square graph on this device (a graph.CSRGraph over the {n} rows) is required')
+
+
+def _attn_view(graph, d, transpose, use_flags):
+    """The view of one orientation with the workspace of the attention kernels' hub partials: 2 d + 4 floats per chunk (cb_attn_workspace_bytes), which is
+    what the aggregation's view holds for rows of 2 d + 4 elements — also the bytes of the K | V pair a gather brings in, for the hot-row count."""
+    view = graph._view(2 * d + 4, transpose, use_flags=use_flags)
+    assert view.ws_bytes >= _lib.load().cb_attn_workspace_bytes(view.n_chunks, d)
+    return view
+
+
+def attn_raw(graph, q, k, v, skip, relu=False, want_lse=True, use_flags=True):
+    """(out, lse): out[v] = act(sum_j a_j V[u_j] + skip[v]) with a = the softmax of <Q[v], K[u_j]> / sqrt(D) over the in-edges of v as the by-dst CSR lists
+    them (each copy of a duplicate edge its own term; a row without in-edges gives act(skip[v]) and lse = -inf), lse[v] = log sum_j exp(s_j) as fp32 [N]
+    (None with want_lse=False: evaluation).  The operands are fp32 [N, D] matrices or column slices of a wider one.  No autograd."""
+    lib = _lib.load()
+    _lib.require_device(q, k, v, skip)
+    d = q.shape[1] if q.dim() == 2 else -1
+    _attn_rows('attn_raw', d, q=q, k=k, v=v, skip=skip)
+    _attn_graph('attn_raw', graph, q.shape[0])
+    n = graph.N
+    out = torch.empty((n, d), dtype=torch.float32, device=q.device)
+    lse = torch.empty(n, dtype=torch.float32, device=q.device) if want_lse else None
+    view = _attn_view(graph, d, False, use_flags)
+    with torch.cuda.device(q.device):
+        _lib.check(lib.cb_attn_fwd_f32(ctypes.byref(view), d, _lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(v), v.stride(0), _lib.ptr(skip),
+                                       skip.stride(0), int(bool(relu)), _lib.ptr(out), out.stride(0), _lib.ptr(lse), _lib.stream_ptr()), 'cb_attn_fwd_f32')
+    return out, lse
+
+
+def attn_bwd_raw(graph, q, k, v, dout, lse, dq, dk, dv, use_flags=True, parts=('dst', 'src'), delta_in=None):
+    """The gradients of attn_raw's sum with respect to Q, K, V written into dq, dk, dv (fp32 [N, D], column slices allowed) from dout = the gradient of
+    the sum (the ReLU mask already applied; the skip's gradient is dout itself).  Returns delta [N].  Needs both orientations of the graph.
+    parts / delta_in (tools/bench_attn.py): one of the two kernels alone — 'dst' writes dq and delta, 'src' reads delta_in and writes dk, dv."""
+    lib = _lib.load()
+    _lib.require_device(q, k, v, dout, lse, dq, dk, dv)
+    d = q.shape[1] if q.dim() == 2 else -1
+    _attn_rows('attn_bwd_raw', d, q=q, k=k, v=v, dout=dout, dq=dq, dk=dk, dv=dv)
+    _attn_graph('attn_bwd_raw', graph, q.shape[0])
+    if graph.rowptr_t is None:
+        raise ValueError('attn_bwd_raw: this graph holds the forward orientation only; the backward gathers along the reverse one')
+    delta = torch.empty(graph.N, dtype=torch.float32, device=q.device)
+    ops_ = (_lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(v), v.stride(0), _lib.ptr(dout), dout.stride(0), _lib.ptr(lse))
+    with torch.cuda.device(q.device):
+        if 'dst' in parts:
+            view = _attn_view(graph, d, False, use_flags)
+            _lib.check(lib.cb_attn_bwd_dst_f32(ctypes.byref(view), d, *ops_, _lib.ptr(dq), dq.stride(0), _lib.ptr(delta), _lib.stream_ptr()),
+                       'cb_attn_bwd_dst_f32')
+        elif delta_in is not None:
+            delta = delta_in
+        if 'src' in parts:
+            view = _attn_view(graph, d, True, use_flags)
+            _lib.check(lib.cb_attn_bwd_src_f32(ctypes.byref(view), d, *ops_, _lib.ptr(delta), _lib.ptr(dk), dk.stride(0), _lib.ptr(dv), dv.stride(0),
+                                               _lib.stream_ptr()), 'cb_attn_bwd_src_f32')
+    return delta
+
+
+class _TransformerConvFn(torch.autograd.Function):
+    """P = X [W_q ; W_k ; W_v ; W_s]^T + [b_q ; b_k ; b_v ; b_s] = [Q | K | V | S], one GEMM; Y = act(attention(Q, K, V) + S), one kernel.  Saved: X, P, lse and,
+    under the ReLU, Y (its mask).  Backward: dO = dY * 1[Y > 0]; the two attention kernels fill [dQ | dK | dV] of one [N, 4 D] matrix whose last block is
+    dS = dO; dX = dP W, dW = dP^T X and db = colsum(dP), each one GEMM / one pass over dP, split back to the eight parameters."""
+
+    @staticmethod
+    def forward(ctx, graph, x, W, b, relu):
+        from . import gemm
+        d = W.shape[0] // 4
+        P = gemm.mm_nn(x, W.t().contiguous(), bias=b)
+        y, lse = attn_raw(graph, P[:, :d], P[:, d:2 * d], P[:, 2 * d:3 * d], P[:, 3 * d:], relu=relu, want_lse=True)
+        ctx.graph, ctx.relu, ctx.d = graph, relu, d
+        ctx.save_for_backward(x, W, P, lse, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import gemm
+        x, W, P, lse, y = ctx.saved_tensors
+        d, graph = ctx.d, ctx.graph
+        if graph.rowptr_t is None:
+            raise ValueError('transformer_conv: this graph holds the forward orientation only; the backward gathers along the reverse one')
+        dy = _c(dy)
+        dP = torch.empty_like(P)
+        dS = dP[:, 3 * d:]
+        if ctx.relu:
+            dS.copy_(act_bwd(dy, y, None, want_out=True, want_colsum=False)[0])
+        else:
+            dS.copy_(dy)
+        attn_bwd_raw(graph, P[:, :d], P[:, d:2 * d], P[:, 2 * d:3 * d], dS, lse, dP[:, :d], dP[:, d:2 * d], dP[:, 2 * d:3 * d])
+        dx = gemm.mm_nn(dP, W) if ctx.needs_input_grad[1] else None          # [N, 4D] @ [4D, in]
+        dW = gemm.mm_tn(dP, x) if ctx.needs_input_grad[2] else None          # [4D, in]
+        db = act_bwd(dP, None, None, want_out=False, want_colsum=True)[1] if ctx.needs_input_grad[3] else None
+        return None, dx, dW, db, None
+
+
+def transformer_conv(graph, x, W_key, b_key, W_query, b_query, W_value, b_value, W_skip, b_skip, relu=False):
+    """One PyG TransformerConv(in, out) layer with every default (heads = 1, concat, no beta, no edge features, no attention dropout, bias, root weight) and
+    its autograd: with Q, K, V, S = the four Linears of x (weights [out, in]),  out[v] = act(sum_j softmax_j(<Q[v], K[u_j]> / sqrt(out)) V[u_j] + S[v])  over
+    the in-edges of v as the by-dst CSR lists them.  Deviation from PyG: its 1e-16 in the softmax's denominator is dropped (the maximum is subtracted, the
+    denominator is >= 1, the addition is invisible in fp32).  The backward needs both orientations of the graph."""
+    params = (W_query, b_query, W_key, b_key, W_value, b_value, W_skip, b_skip)      # stacked as [Q | K | V | S]: K and V of a row adjacent
+    _lib.require_device(x, *params)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise TypeError('transformer_conv expects float32 rows')
+    d = W_query.shape[0]
+    for w, b in zip(params[0::2], params[1::2]):
+        if tuple(w.shape) != (d, x.shape[1]) or tuple(b.shape) != (d,) or w.dtype != torch.float32 or b.dtype != torch.float32:
+            raise ValueError(f'transformer_conv: four float32 [out, in] = [{d}, {x.shape[1]}] weights with [{d}] biases expected')
+    if d % 4 or d > ATTN_MAX_D:
+        raise ValueError(f'transformer_conv: out_channels = {d} is not built: D % 4 == 0 and D <= {ATTN_MAX_D} are required')
+    _attn_graph('transformer_conv', graph, x.shape[0])
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return _TransformerConvFn.apply(graph, x, torch.cat(params[0::2]), torch.cat(params[1::2]), bool(relu))

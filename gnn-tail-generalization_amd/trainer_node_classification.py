@@ -814,7 +814,7 @@ class trainer:
     # gradient clipping, metrics and the device checks are theirs.
     def setup_linkpred_encoder(self):
         """Embedding (create_input_layer: trainable, xavier_uniform_, unless --use_node_feats), encoder (create_encoder_layer(--encoder), --gnn_num_layers
-        layers of --gnn_hidden_channels), predictor (input width gnn_hidden_channels) and one fused Adam over all three.  The device graph is built here
+        layers of --gnn_hidden_channels; args.encoder = 'TRANSFORMER' builds the TransformerEncoder here), predictor (input width gnn_hidden_channels) and one fused Adam over all three.  The device graph is built here
         from data.edge_index (the whole graph on this device) and the link sampler on it."""
         from . import optim as cb_optim
         from .graph import CSRGraph, build_graph
@@ -834,7 +834,11 @@ class trainer:
         if self.emb is not None:
             self.emb = self.emb.to(self.device)
             reset_input_layer(self.emb)
-        self.encoder = create_encoder_layer(input_dim, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout, a.encoder).to(self.device)
+        if str(a.encoder).upper() == 'TRANSFORMER':      # (create_encoder_layer's 'Transformer' stands for the torch_geometric module and raises)
+            from .Link_prediction_model import TransformerEncoder
+            self.encoder = TransformerEncoder(input_dim, a.gnn_hidden_channels, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout).to(self.device)
+        else:
+            self.encoder = create_encoder_layer(input_dim, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout, a.encoder).to(self.device)
         if a.predictor.upper() == 'MLP':
             self.predictor = MLPPredictor(a.gnn_hidden_channels, a.mlp_hidden_channels, 1, a.mlp_num_layers, a.dropout).to(self.device)
         else:

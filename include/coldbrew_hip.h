@@ -953,6 +953,32 @@ int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t ld_h, const 
                       const float* row_scale, const void* image, const float* bias, int relu, float drop_p, uint64_t seed, const uint64_t* seed_dev,
                       int64_t row0, float* agg_out, int64_t ld_agg, int32_t agg_hubs_only, float* out, int64_t ld_out, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * Attention over the rows of a CSR (PyG TransformerConv with heads = 1, no edge features, no beta: Link_prediction_model/layer.py:77-83);
+ * cb_attn.hip.  Q, K, V, S, dO and every result are fp32 rows of D elements with a leading dimension each (column slices of one [N, 4 D]
+ * matrix): D % 4 == 0, D <= 512, 16-byte aligned, ld % 4 == 0, ld >= D — cb_attn_supported(D, rows, ld) answers per operand before any
+ * launch; an unsupported call returns CB_E_INVALID.  For an in-edge j = (u_j -> v) of the by-dst view, s_j = <Q[v], K[u_j]> / sqrt(D):
+ *     fwd:      a_j = softmax_j(s_j) (the row's maximum subtracted; each copy of a duplicate edge is its own term),
+ *               out[v] = act(sum_j a_j V[u_j] + S[v]),  lse[v] = max_j s + log sum_j exp(s_j - max_j s)   (lse may be NULL: not written)
+ *               a row without in-edges: out[v] = act(S[v]), lse[v] = -inf
+ *     bwd_dst:  a_j = exp(s_j - lse[v]);  delta[v] = sum_j a_j <dO[v], V[u_j]>;  dQ[v] = 1/sqrt(D) sum_j a_j (<dO[v], V[u_j]> - delta[v]) K[u_j]
+ *     bwd_src:  on the by-src view, for the out-edges j = (u -> v) of u:  dK[u] = 1/sqrt(D) sum_j a_j (<dO[v], V[u]> - delta[v]) Q[v],
+ *               dV[u] = sum_j a_j dO[v]        (lse and delta as bwd_dst left them; dS = dO needs no kernel)
+ * No atomics, nothing of length E is written, every sum in CSR order: bit-reproducible.  Hub rows (a view with n_hubs > 0) are reduced in chunks
+ * of hub_threshold edges, one wavefront per chunk, the partials — (max, sum, acc[D]) in the forward, plain sums of D (bwd_dst) and 2 D (bwd_src)
+ * floats — combined in chunk order; all three entries need ws_bytes >= cb_attn_workspace_bytes(n_chunks, D) = n_chunks * (2 D + 4) floats
+ * (CB_E_WORKSPACE otherwise), ws 16-byte aligned.  col_flags = 1 chooses the cache policy of the gathered rows only.
+ * ---------------------------------------------------------------------------------- */
+int cb_attn_supported(int64_t d, const void* rows, int64_t ld);
+size_t cb_attn_workspace_bytes(int64_t n_chunks, int64_t d);
+int cb_attn_fwd_f32(const cb_csr_view* g, int64_t d, const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v,
+                    const float* skip, int64_t ld_s, int relu, float* out, int64_t ld_out, float* lse, void* stream);
+int cb_attn_bwd_dst_f32(const cb_csr_view* g, int64_t d, const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v,
+                        const float* dout, int64_t ld_do, const float* lse, float* dq, int64_t ld_dq, float* delta, void* stream);
+int cb_attn_bwd_src_f32(const cb_csr_view* g_src, int64_t d, const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v,
+                        const float* dout, int64_t ld_do, const float* lse, const float* delta, float* dk, int64_t ld_dk, float* dv, int64_t ld_dv,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
