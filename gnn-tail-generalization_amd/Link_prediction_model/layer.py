@@ -1,7 +1,8 @@
 """`DotPredictor`, `MLPPredictor` and `Heuristics` of the reference's Link_prediction_model/layer.py with its constructor arguments, parameter names
 (`lins.{i}.weight` / `.bias`), reset_parameters and same-seed initialisation.  forward(x_i, x_j) is the reference's surface on gathered rows;
 score_pairs(h, pairs) is the fused path on the full embedding matrix and an index tensor [2, S]: the gathered rows and their product are never
-written (ops.pair_dot / ops.pair_linear, csrc/cb_linkpred.hip).  The other predictors are not built and say what they need.  The encoders' names
+written (ops.pair_dot / ops.pair_linear, csrc/cb_linkpred.hip).  The other predictors' names are not built here and say what they need; they are
+built under names of their own in pair_predictor.py (BilinearPairPredictor, MLPDotPairPredictor, MLPBilPairPredictor, MLPCatPairPredictor).  The encoders' names
 (`MLP`, `SAGE`, `GCN`, `WSAGE`, `Transformer`) stand for the torch_geometric modules and raise likewise; all five are built on the HIP path under their
 own names in encoder.py (SAGEEncoder, WSAGEEncoder, GCNEncoder, MLPEncoder, TransformerEncoder)."""
 import torch

@@ -195,6 +195,14 @@ SIGNATURES = {
     'cb_rank_loss_workspace_bytes': (_SZ, []),
     'cb_rank_loss_fwd_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
     'cb_rank_loss_bwd_f32': (ctypes.c_int, [_I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    # the indexed-row GEMM, the bilinear pair score and the row scatter of the BIL / MLPDOT / MLPBIL / MLPCAT predictors (cb_pairpred.hip)
+    'cb_rows_gemm_nn_supported': (ctypes.c_int, [_P, _I64, _I64, _I32, _P, _I64, _I64]),
+    'cb_rows_gemm_nn_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I32, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, ctypes.c_int, ctypes.c_float,
+                                           ctypes.c_uint64, _P, _I64, _P, _P]),
+    'cb_rows_bilinear_supported': (ctypes.c_int, [_P, _I64, _I64, _P, _I64]),
+    'cb_rows_bilinear_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_rows_bilinear_f32': (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'cb_rows_scatter_f32': (ctypes.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
     # one layer of the SAGE / WSAGE / GCN encoders (cb_sage.hip).  The layer entry's view carries a hub plan like the aggregation entries'; it is bound
     # as a plain pointer (ctypes.byref(view)) like the samplers above: the table of _G entries in tests/test_csr_view_host.py is closed, and this
     # entry's view checks are exercised by tests/test_sage_host.py instead

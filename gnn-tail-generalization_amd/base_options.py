@@ -150,7 +150,7 @@ def build_parser():
     a('--LP_device', type=str, default='cuda:4', choices=['cpu', 'cuda:0', 'cuda:4'])
     a('--exp_on_cold_edge', type=bool, default=False)
     a('--encoder', type=str, default='SAGE', choices=['SAGE', 'MLP', 'CN', 'AA', 'PPR'])
-    a('--predictor', type=str, default='DOT', choices=['MLP', 'DOT'])
+    a('--predictor', type=str, default='DOT', choices=['MLP', 'DOT', 'BIL', 'MLPDOT', 'MLPBIL', 'MLPCAT'])
     a('--optimizer', type=str, default='Adam')
     a('--loss_func', type=str, default='ce_loss', choices=['AUC', 'ce_loss', 'log_rank_loss', 'info_nce_loss'])
     a('--neg_sampler', type=str, default='global')

@@ -171,6 +171,73 @@ struct PairRowOperand {
   static __device__ __forceinline__ bf16x8 frag(const char* __restrict__ S, uint32_t addr, int plane) { return RowOperand<R>::frag(S, addr, plane); }
 };
 
+// ---- "row" operand whose rows are GATHERED (NSEG == 1: value[r][k] = h[i0_r][k]) or CONCATENATED from two gathered rows (NSEG == 2:
+// value[r][s D + k] = h[is_r][k]; the link predictors' x_i / [x_i | x_j], Link_prediction_model/layer.py:124, 151) — the gathered matrix is never
+// written.  Same LDS image and fragment reads as RowOperand<R>; the values are staged as they stand, so the limbs are those of the materialised matrix.
+// `base` of load() is &h[0][0] for EVERY K step (the K loop is run with a step advance of 0): the operand finds the step's first column
+// k0 = Ktot - k_left itself, and from it the segment and the column inside the row of h, both wave-uniform.  NSEG == 2 needs D % KS == 0 (no K step
+// straddles the seam); NSEG == 1 needs D % 4 == 0 like RowOperand.  A row with an index outside [0, N) addresses node 0 and stages zeros (the kernel
+// overwrites its row of C).  One stream of loads per K step: nothing but the indices lives in the operand.
+template <int R, int NSEG>
+struct IndexedRowOperand {
+  static constexpr int PLANE = R * 32, BYTES = 3 * PLANE, NV = R / 64;
+  static_assert(NV >= 1 && (NSEG == 1 || NSEG == 2), "tile rows; one or two segments");
+  int32_t nd[NSEG][NV];        // the nodes of tile row t/4 + 64 j; nd[0][j] < 0: the row stages zeros (outside the matrix, or an unusable index)
+  uint32_t woff;
+  int32_t D, Ktot;             // row length of h; NSEG * D
+  static constexpr bool HAS_SC = false;
+  float sc[1];
+  // usable row `row` (idx = &idx[0][tile row 0], Rn = its row length, rows_left = Rn - tile row 0); in: the row lies inside the matrix
+  static __device__ __forceinline__ bool row_of(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int row, int (&n)[NSEG], bool& in) {
+    in = row < rows_left;
+    bool ok = in;
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s) {
+      n[s] = in ? idx[s * Rn + row] : 0;
+      ok = ok && n[s] >= 0 && n[s] < N;
+    }
+    return ok;
+  }
+  __device__ __forceinline__ void init(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int d, int t) {
+    const int row = t >> 2, kq = t & 3;
+    woff = row * 32 + (((kq >> 1) ^ ((row >> 3) & 1)) << 4) + ((kq & 1) << 3);
+    D = d;
+    Ktot = NSEG * d;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      int n[NSEG];
+      bool in;
+      const bool ok = row_of(idx, Rn, rows_left, N, row + 64 * j, n, in);
+#pragma unroll
+      for (int s = 0; s < NSEG; ++s) nd[s][j] = ok ? n[s] : (s == 0 ? -1 : 0);
+    }
+  }
+  template <int J>
+  __device__ __forceinline__ void load(float4 (&f)[NV], const float* __restrict__ base, int64_t ld, int64_t k_left, const float*, int t) const {
+    const int k0 = Ktot - (int)k_left;      // (wave-uniform)
+    const int kq4 = (t & 3) * 4 < k_left ? (t & 3) * 4 : 0;
+    int node = nd[0][J] < 0 ? 0 : nd[0][J], col = k0;
+    if constexpr (NSEG == 2) {
+      if (k0 >= D) {
+        node = nd[1][J];
+        col = k0 - D;
+      }
+    }
+    f[J] = *reinterpret_cast<const float4*>(base + ((int64_t)node * ld + col + kq4));
+  }
+  template <int J>
+  __device__ __forceinline__ void stage(const float4 (&f)[NV], char* __restrict__ S, int64_t k_left, int t) const {
+    const bool live = nd[0][J] >= 0 && (t & 3) * 4 < k_left;
+    const float v[4] = {live ? f[J].x : 0.f, live ? f[J].y : 0.f, live ? f[J].z : 0.f, live ? f[J].w : 0.f};
+    uint2 pl[3];
+    split4(v, pl);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(S + p * PLANE + woff + J * (64 * 32)) = pl[p];
+  }
+  static __device__ __forceinline__ uint32_t frag_addr(int r0, int lane) { return RowOperand<R>::frag_addr(r0, lane); }
+  static __device__ __forceinline__ bf16x8 frag(const char* __restrict__ S, uint32_t addr, int plane) { return RowOperand<R>::frag(S, addr, plane); }
+};
+
 // ---- "col" operand: global [k][cols] (cols contiguous) -> LDS planes [16 k][C cols] ------------------
 template <int C, bool SCALED, bool DROP = false, int NT = 256>      // NT: threads of the block that stage the operand
 struct ColOperand {

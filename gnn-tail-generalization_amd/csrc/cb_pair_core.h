@@ -10,7 +10,8 @@
 //             key c << 32 | node (k_pair_keys), the keys are sorted by node (cb::sort_u64, stable: ascending contribution number inside a node),
 //             and the wavefront at the head of a node's run adds the run in that order in float64, rounds once and writes the row
 //             (k_pair_scatter_rows); all other rows are zero-filled before.  The coefficient is a functor: a scalar per pair, a row per pair, or
-//             the BCE-with-logits derivative formed in float64 from the score.
+//             the BCE-with-logits derivative formed in float64 from the score; CoefAsIs contributes a row as it stands instead of a multiple of the
+//             other endpoint's row (cb_pairpred.hip).
 //   tree      block_tree_f64: the 256-thread float64 halving tree of the loss finishers.
 // No float atomics, no host synchronisation, two calls with the same inputs give the same bits.
 #pragma once
@@ -91,6 +92,7 @@ static int launch_pair_dot(const float* h, int64_t ld, int64_t N, int64_t D, con
 // The coefficient of contribution (pair e, column cc) in float64, in three steps so that each form does its work where it always did:
 // wave() once per wavefront, pair(e, w) once per contribution, col(e, cc, p) per column.
 struct CoefScalar {      // c [S]: a scalar per pair
+  static constexpr bool AS_IS = false;
   const float* c;
   __device__ __forceinline__ double wave() const { return 0.0; }
   __device__ __forceinline__ double pair(int64_t e, double) const { return (double)c[e]; }
@@ -98,6 +100,7 @@ struct CoefScalar {      // c [S]: a scalar per pair
 };
 
 struct CoefRows {      // c [S, ld]: a row per pair
+  static constexpr bool AS_IS = false;
   const float* c;
   int64_t ld;
   __device__ __forceinline__ double wave() const { return 0.0; }
@@ -106,6 +109,7 @@ struct CoefRows {      // c [S, ld]: a row per pair
 };
 
 struct CoefBce {      // g (sigmoid(s_e) - y_e) / S from the scores; y_e = 1 for the P first pairs
+  static constexpr bool AS_IS = false;
   const float* scores;
   const float* g;
   int64_t P, S;
@@ -115,6 +119,19 @@ struct CoefBce {      // g (sigmoid(s_e) - y_e) / S from the scores; y_e = 1 for
     return scale * (1.0 / (1.0 + exp(-s)) - (e < P ? 1.0 : 0.0));
   }
   __device__ __forceinline__ double col(int64_t, int, double p) const { return p; }
+};
+
+// AS_IS: the contribution is a row as it stands, g0[e] into row u_e and g1[e] into row v_e (the backward of the two gathers of an indexed-row GEMM):
+// no row of h is read (the scatter is run with h == nullptr), and term() replaces coefficient times other row.
+struct CoefAsIs {
+  static constexpr bool AS_IS = true;
+  const float* g0;
+  int64_t ld0;
+  const float* g1;
+  int64_t ld1;
+  __device__ __forceinline__ double wave() const { return 0.0; }
+  __device__ __forceinline__ double pair(int64_t, double) const { return 0.0; }
+  __device__ __forceinline__ double term(int64_t e, int side, int cc) const { return (double)(side ? g1[e * ld1 + cc] : g0[e * ld0 + cc]); }
 };
 
 // contribution c = 2 e + side goes to node (side ? v_e : u_e); key = c << 32 | node, node = N for an unusable pair (sorted last, skipped)
@@ -148,12 +165,20 @@ __global__ void __launch_bounds__(256) k_pair_scatter_rows(const float* __restri
       const int64_t c = (int64_t)(key >> 32), e = c >> 1;      // (e < S: the keys are a permutation of those k_pair_keys wrote)
       int u, v;
       src.get(e, N, u, v);      // (usable: its node is < N)
-      const float* other = h + (int64_t)((c & 1) ? u : v) * ld;
-      const double cp = coef.pair(e, cw);
+      if constexpr (Coef::AS_IS) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int cc = c0 + lane + 64 * q;
-        if (cc < D) acc[q] = fma(coef.col(e, cc, cp), (double)other[cc], acc[q]);
+        for (int q = 0; q < 4; ++q) {
+          const int cc = c0 + lane + 64 * q;
+          if (cc < D) acc[q] += coef.term(e, (int)(c & 1), cc);
+        }
+      } else {
+        const float* other = h + (int64_t)((c & 1) ? u : v) * ld;
+        const double cp = coef.pair(e, cw);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int cc = c0 + lane + 64 * q;
+          if (cc < D) acc[q] = fma(coef.col(e, cc, cp), (double)other[cc], acc[q]);
+        }
       }
     }
 #pragma unroll

@@ -27,6 +27,10 @@ Link predictors and ranking losses (Link_prediction_model/layer.py:85-106, 182-1
   pair_dot          <h[u], h[v]> per index pair (DotPredictor); gradient through the sorted inverted index, no atomics
   pair_linear       act((h[u] * h[v]) @ W^T + b) (+ dropout): MLPPredictor's first layer, its A operand formed while the GEMM stages it
   rank_loss         auc / adaptive_auc / log_rank / ce / info_nce over pos [P] and neg [P, k], every term in float64, rounded once
+  rows_linear       act(h[idx] @ W^T + b) or act([h[idx0] | h[idx1]] @ W^T + b) (+ dropout): the first layer of the MLP-dot / MLP-bilinear /
+                    concatenating predictors (layer.py:108-180), the gathered operand formed while the GEMM stages it
+  pair_bilinear     sum(bilin(h[u]) * h[v], -1) (BilinearPredictor, layer.py:193-203): the dot taken in the GEMM's epilogue, no [S, D] matrix
+  pair_scatter_rows the backward of the two gathers: rows as they stand through the sorted inverted index, no atomics
 Encoders of the link-prediction experiment (Link_prediction_model/layer.py:19-75; model.py:290-304):
   sage_layer        act((s * (A X)) W_n^T + X W_s^T + b): one SAGEConv / GraphConv / GCNConv(normalize=False) layer with the ReLU and dropout after it; one
                     kernel per direction at 256 -> 256 (aggregation into an on-chip tile, the GEMM from there), the composed kernels elsewhere
@@ -1841,7 +1845,239 @@ def rank_loss(kind, pos, neg, num_neg=None, weight=None):
     return _RankLossFn.apply(RANK_KINDS[kind], _c(pos.reshape(-1)), _c(neg.reshape(-1)), k, weight)
 
 
-pair_dot.check = pair_linear.check = rank_loss.check = pair_check
+# ---------------------------------------------------------------------------------------------
+# the predictors that take their endpoint rows one at a time: Link_prediction_model/layer.py:108-180, 193-203  (cb_pairpred.hip)
+# ---------------------------------------------------------------------------------------------
+def pair_scatter_rows(pairs, g0, g1, n_rows, out=None):
+    """fp32 [n_rows, D]: sum_e (g0[e] into row pairs[0, e], g1[e] into row pairs[1, e]) — the backward of the two gathers h[u], h[v], built through
+    the sorted inverted index of pair_dot's gradient: no atomics, float64 sums in ascending contribution order rounded once, bit-identical from call
+    to call, untouched rows exactly zero, pairs with an endpoint outside [0, n_rows) skipped.  g0, g1: float32 [S, D] with contiguous rows and leading
+    dimensions of their own (halves or column halves of one matrix pass without a copy).  out: optional [n_rows, D] destination with contiguous
+    rows (a wider leading dimension leaves the columns beyond D untouched)."""
+    _lib.require_device(pairs, g0, g1, out)
+    if not torch.is_tensor(g0) or not torch.is_tensor(g1) or g0.dim() != 2 or g0.shape != g1.shape or g0.dtype != torch.float32 or g1.dtype != torch.float32:
+        raise ValueError('pair_scatter_rows: g0 and g1 must be float32 [S, D] matrices of one shape')
+    pairs = _pairs_arg('pair_scatter_rows: pairs', pairs, g0.device, 'S')
+    S, D = g0.shape
+    N = int(n_rows)
+    if pairs.shape[1] != S or N < 1 or D < 1 or g1.device != g0.device:
+        raise ValueError(f'pair_scatter_rows: {pairs.shape[1]} pairs for {S} rows, or n_rows < 1, or an empty row')
+    lib = _lib.load()
+    g0, g1 = _pair_rows(g0), _pair_rows(g1)
+    dh = torch.empty((N, D), dtype=torch.float32, device=g0.device) if out is None else out
+    if tuple(dh.shape) != (N, D) or dh.dtype != torch.float32 or dh.stride(1) != 1 or dh.stride(0) < D or dh.device != g0.device:
+        raise ValueError(f'pair_scatter_rows: out must be a float32 [{N}, {D}] matrix with contiguous rows on the device of the rows')
+    wsb = lib.cb_pair_scatter_workspace_bytes(S)
+    ws = _ws(wsb, g0.device)
+    with torch.cuda.device(g0.device):
+        _lib.check(lib.cb_rows_scatter_f32(N, D, _lib.ptr(pairs), S, _lib.ptr(g0), g0.stride(0) if S > 1 else D, _lib.ptr(g1), g1.stride(0) if S > 1 else D,
+                                                _lib.ptr(dh), dh.stride(0) if N > 1 else D, _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_rows_scatter_f32')
+    return dh
+
+
+def _rows_idx_arg(who, h, idx):
+    if not torch.is_tensor(h) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[0] < 1 or h.shape[1] < 1:
+        raise ValueError(f'{who} expects a float32 [N, D] embedding matrix')
+    _lib.require_device(h, idx)
+    if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[0] not in (1, 2) or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{who}: idx must be an int32 / int64 [nseg, R] tensor, nseg 1 or 2')
+    if idx.device != h.device:
+        raise ValueError(f'{who}: idx must live on {h.device}, the device of the embeddings it indexes (got {idx.device})')
+    return _c(idx.to(torch.int32))
+
+
+def _rows_ok(h, idx):
+    """bool [R]: every index of the row lies in [0, N)."""
+    return ((idx >= 0) & (idx < h.shape[0])).all(0)
+
+
+def _rows_operand(h, idx):
+    """The A operand materialised: [h[idx[0]] | h[idx[1]] ...]; the row of an unusable index is zero (its indices are replaced by node 0 first)."""
+    ok = _rows_ok(h, idx)
+    safe = torch.where(ok[None, :], idx, torch.zeros_like(idx)).long()
+    return torch.cat([h[safe[s]] for s in range(idx.shape[0])], dim=1) * ok[:, None].to(h.dtype)
+
+
+def rows_linear_supported(h, idx, weight):
+    """The fused form exists for this shape (cb_rows_gemm_nn_supported): out width a multiple of 4, row length a multiple of 4 (one segment) or of 16
+    (two segments: no K step straddles the seam), 16-byte aligned rows."""
+    lib = _lib.load()
+    e, b = _pair_rows(h), weight.t().contiguous()
+    K, Nout = b.shape
+    nseg = idx.shape[0]
+    return nseg * e.shape[1] == K and bool(lib.cb_rows_gemm_nn_supported(_lib.ptr(e), e.stride(0), e.shape[1], nseg, _lib.ptr(b), Nout, Nout))
+
+
+def _rows_linear_raw(e, idx, b, bias, relu, p, seed, row0):
+    """(y, dropout_p(y) | None, status) of cb_rows_gemm_nn_f32: y = act([e[idx[0]] | ...] @ b + bias), b [nseg * D, Nout] contiguous."""
+    lib = _lib.load()
+    N, D = e.shape
+    (nseg, R), Nout = idx.shape, b.shape[1]
+    dev = e.device
+    y = torch.empty((R, Nout), dtype=torch.float32, device=dev)
+    yd = torch.empty((R, Nout), dtype=torch.float32, device=dev) if p > 0.0 else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_rows_gemm_nn_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(idx), nseg, R, _lib.ptr(b), Nout, _lib.ptr(y), Nout, _lib.ptr(yd), Nout,
+                                           Nout, _lib.ptr(bias), int(bool(relu)), float(p), ctypes.c_uint64(seed), seed_dev_ptr(), int(row0),
+                                           _lib.ptr(status), _lib.stream_ptr()), 'cb_rows_gemm_nn_f32')
+    return y, yd, status
+
+
+def _rows_linear_any(e, idx, b, bias=None, relu=False, p=0.0, seed=0, row0=0, fused=None):
+    """_rows_linear_raw where the fused form exists (and fused is not False), else the same operators one after the other; no autograd."""
+    from . import gemm
+    lib = _lib.load()
+    (nseg, R), Nout = idx.shape, b.shape[1]
+    can = R > 0 and bool(lib.cb_rows_gemm_nn_supported(_lib.ptr(e), e.stride(0), e.shape[1], nseg, _lib.ptr(b), Nout, Nout))
+    if fused and not can:
+        raise _lib.HipExtensionError('rows_linear: the fused form does not exist for this shape (rows_linear_supported)')
+    if can and fused is not False:
+        return _rows_linear_raw(e, idx, b, bias, relu, p, seed, row0)
+    ok = _rows_ok(e, idx)
+    y = gemm.mm_nn(_rows_operand(e, idx), b, bias=bias, relu=relu)
+    y = torch.where(ok[:, None], y, torch.full_like(y, float('nan')))
+    status = (~ok).sum().to(torch.int32).reshape(1)
+    return y, (_dropout_raw(y, p, seed, row0 * Nout) if p > 0.0 else None), status
+
+
+def _scatter_segments(idx, dx, D, n_rows):
+    """dH of a rows GEMM from dX [R, nseg * D].  Two segments: the column halves of dX go to idx[0] and idx[1].  One segment: rows r < R / 2 and
+    r >= R / 2 are the two sides of R / 2 pairs (an odd R gets one zero row with the last index once more)."""
+    if idx.shape[0] == 2:
+        return pair_scatter_rows(idx, dx[:, :D], dx[:, D:], n_rows)
+    R = idx.shape[1]
+    if R % 2:
+        idx = torch.cat([idx, idx[:, -1:]], dim=1)
+        dx = torch.cat([dx, torch.zeros_like(dx[-1:])], dim=0)
+        R += 1
+    return pair_scatter_rows(idx.reshape(2, R // 2), dx[:R // 2], dx[R // 2:], n_rows)
+
+
+class _RowsLinearFn(torch.autograd.Function):
+    """Y = act([h[idx[0]] | h[idx[1]]] @ W^T + b), nn.Linear's weight layout [out, in]; returns dropout_p(Y) when p > 0."""
+
+    @staticmethod
+    def forward(ctx, h, idx, weight, bias, relu, p, seed, row0, fused):
+        e = _pair_rows(h)
+        y, yd, status = _rows_linear_any(e, idx, weight.t().contiguous(), bias, relu, p, seed, row0, fused)
+        ctx.relu, ctx.p, ctx.seed, ctx.row0, ctx.has_bias = bool(relu), float(p), int(seed), int(row0), bias is not None
+        ctx.save_for_backward(e, idx, weight, y if relu else None)
+        ctx.mark_non_differentiable(status)
+        return (yd if p > 0.0 else y), status
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        from . import gemm
+        e, idx, weight, y = ctx.saved_tensors
+        Nout = weight.shape[0]
+        g = _c(g)
+        if ctx.p > 0.0:
+            g = _dropout_raw(g, ctx.p, ctx.seed, ctx.row0 * Nout)
+        need_b = ctx.has_bias and ctx.needs_input_grad[3]
+        if ctx.relu or need_b:
+            gm, db = act_bwd(g, y if ctx.relu else None, None, want_out=ctx.relu, want_colsum=need_b)
+            if gm is None:
+                gm = g
+        else:
+            gm, db = g, None
+        dh = _scatter_segments(idx, gemm.mm_nn(gm, weight), e.shape[1], e.shape[0]) if ctx.needs_input_grad[0] else None      # dX = gm @ W
+        dw = gemm.mm_tn(gm, _rows_operand(e, idx)) if ctx.needs_input_grad[2] else None                                      # A exists here only
+        return dh, None, dw, db, None, None, None, None, None
+
+
+def rows_linear(h, idx, weight, bias=None, relu=False, p=0.0, seed=None, row0=0, return_status=False, fused=None):
+    """act(A @ weight^T + bias), then F.dropout(p) when p > 0, with A the gather h[idx[0]] (idx [1, R]) or the concatenation [h[idx[0]] | h[idx[1]]]
+    (idx [2, R]); weight [out, nseg * D].  A is formed while the three-limb GEMM stages it (cb_rows_gemm_nn_f32) and never written in the forward;
+    the output has the bits of gemm.mm_nn(A, weight.t(), bias, relu) — with p > 0 those of gemm.mm_nn_drop2 for (seed, row0).  Backward: act_bwd,
+    dX = gm @ W on mm_nn, dH through pair_scatter_rows (no atomics; with one segment row r is scattered as one side of the pair (r, r + R / 2), so
+    an unusable index drops that pair's two rows), dW = gm^T @ A on mm_tn over an A materialised there.  Where the fused form does not exist for
+    the shape (rows_linear_supported) the same operators run one after the other; fused=False asks for that, fused=True raises there.  A row with
+    an index outside [0, N) is NaN and counts in the status that pair_check() reads."""
+    idx = _rows_idx_arg('rows_linear', h, idx)
+    _lib.require_device(weight, bias)
+    if weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[1] != idx.shape[0] * h.shape[1]:
+        raise ValueError(f'rows_linear: weight must be a float32 [out, {idx.shape[0] * h.shape[1]}] matrix')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('rows_linear: 0 <= p < 1 required')
+    if p > 0.0 and seed is None:
+        seed = next_seed()
+    y, status = _RowsLinearFn.apply(h, idx, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
+    _pair_bad.add(status)
+    return (y, status) if return_status else y
+
+
+def pair_bilinear_supported(h, weight):
+    """The fused bilinear score exists for this shape (cb_rows_bilinear_supported): D a multiple of 4, 16-byte aligned rows."""
+    lib = _lib.load()
+    e, wt = _pair_rows(h), weight.t().contiguous()
+    D = e.shape[1]
+    return tuple(weight.shape) == (D, D) and bool(lib.cb_rows_bilinear_supported(_lib.ptr(e), e.stride(0), D, _lib.ptr(wt), D))
+
+
+class _PairBilinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, pairs, weight):
+        lib = _lib.load()
+        e = _pair_rows(h)
+        N, D = e.shape
+        S = pairs.shape[1]
+        dev = e.device
+        wt = weight.t().contiguous()
+        if S > 0 and bool(lib.cb_rows_bilinear_supported(_lib.ptr(e), e.stride(0), D, _lib.ptr(wt), D)):
+            scores = torch.empty(S, dtype=torch.float32, device=dev)
+            status = torch.empty(1, dtype=torch.int32, device=dev)
+            wsb = lib.cb_rows_bilinear_workspace_bytes(S, D)
+            ws = _ws(wsb, dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.cb_rows_bilinear_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(pairs), S, _lib.ptr(wt), D, _lib.ptr(scores), _lib.ptr(status),
+                                                    _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_rows_bilinear_f32')
+        else:      # the shape is outside the fused form: the rows GEMM (itself composed there), then the dot
+            ok = _rows_ok(e, pairs)
+            z, _, _ = _rows_linear_any(e, pairs[:1], wt)
+            safe_v = torch.where(ok, pairs[1], torch.zeros_like(pairs[1])).long()
+            scores = torch.where(ok, (z * e[safe_v]).sum(-1), torch.full((S,), float('nan'), dtype=torch.float32, device=dev))
+            status = (~ok).sum().to(torch.int32).reshape(1)
+        ctx.save_for_backward(e, pairs, weight)
+        ctx.mark_non_differentiable(status)
+        return scores, status
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        from . import gemm
+        e, pairs, weight = ctx.saved_tensors
+        g = _c(g.detach().to(torch.float32))[:, None]
+        dh = dw = None
+        if ctx.needs_input_grad[0]:
+            g0 = _rows_linear_any(e, pairs[1:], _c(weight))[0] * g                      # g * (h[v] @ W) into row u
+            g1 = _rows_linear_any(e, pairs[:1], weight.t().contiguous())[0] * g         # g * (h[u] @ W^T) into row v
+            dh = pair_scatter_rows(pairs, g0, g1, e.shape[0])
+        if ctx.needs_input_grad[2]:
+            ok = _rows_ok(e, pairs)
+            gz = torch.where(ok[:, None], g, torch.zeros_like(g))                        # (an unusable pair's g is the NaN score's: it adds nothing)
+            dw = gemm.mm_tn(_rows_operand(e, pairs[1:]) * gz, _rows_operand(e, pairs[:1]))
+        return dh, None, dw
+
+
+def pair_bilinear(h, pairs, weight, return_status=False):
+    """fp32 [S]: sum_j (weight @ h[u_e])_j h[v_e, j] — `BilinearPredictor.forward(h[u], h[v])` (layer.py:201-203), sum(bilin(x_i) * x_j, -1), without
+    the gathered matrices and without bilin(x_i): the dot against row v_e is taken in the epilogue of the indexed-row GEMM over u
+    (cb_rows_bilinear_f32), so under torch.no_grad() nothing of size S x D is allocated.  weight: float32 [D, D].  The backward saves nothing of
+    size S x D either: it RECOMPUTES the two products with the indexed-row GEMM (g * (h[v] @ W) goes into row u, g * (h[u] @ W^T) into row v,
+    through pair_scatter_rows) and forms dW = (g * h[v])^T @ h[u] on mm_tn over gathers materialised there.  A pair's score does not depend on its
+    place in the batch.  Where the fused form does not exist (pair_bilinear_supported: D % 4, alignment) the same value is composed from the rows
+    GEMM and a torch reduction.  Unusable pairs: as pair_dot."""
+    pairs = _pair_args('pair_bilinear', h, pairs)
+    _lib.require_device(weight)
+    if not torch.is_tensor(weight) or weight.dim() != 2 or weight.dtype != torch.float32 or tuple(weight.shape) != (h.shape[1], h.shape[1]):
+        raise ValueError(f'pair_bilinear: weight must be a float32 [{h.shape[1]}, {h.shape[1]}] matrix')
+    scores, status = _PairBilinearFn.apply(h, pairs, weight)
+    _pair_bad.add(status)
+    return (scores, status) if return_status else scores
+
+
+pair_dot.check = pair_linear.check = rank_loss.check = rows_linear.check = pair_bilinear.check = pair_check
 
 
 # ---------------------------------------------------------------------------------------------

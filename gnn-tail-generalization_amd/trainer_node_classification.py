@@ -716,20 +716,28 @@ class trainer:
         return results_arr2D
 
     # -- the link predictors and ranking losses of Link_prediction_model (layer.py, loss.py; BaseModel.train / test, model.py:121-169, 187-266) ----
-    # The teacher GNN is the encoder; the decoder is `--predictor DOT | MLP`, the objective `--loss_func` over `--batch_size` sampled positives and
+    # The teacher GNN is the encoder; the decoder is `--predictor DOT | MLP | BIL | MLPDOT | MLPBIL | MLPCAT`, the objective `--loss_func` over `--batch_size` sampled positives and
     # `--num_neg` negatives each.  Next to the *_linkp entry points above, which keep their BCE on the raw dot product.
     def setup_teacherGNN_linkpred(self):
         """Teacher, predictor and one fused Adam over both parameter sets (model.py:82-88).  DOT has no parameters; MLP is
         MLPPredictor(dim_commonEmb, mlp_hidden_channels, 1, mlp_num_layers, dropout): the reference's create_predictor_layer uses one width for
-        both, here the input width is the teacher's embedding width."""
-        from .Link_prediction_model import MLPPredictor, create_predictor_layer
+        both, here the input width is the teacher's embedding width (likewise BIL / MLPDOT / MLPBIL / MLPCAT: _linkpred_predictor)."""
         a = self.args
         self.setup_teacherGNN()
-        if a.predictor.upper() == 'MLP':
-            self.predictor = MLPPredictor(a.dim_commonEmb, a.mlp_hidden_channels, 1, a.mlp_num_layers, a.dropout).to(self.device)
-        else:
-            self.predictor = create_predictor_layer(a.mlp_hidden_channels, a.mlp_num_layers, a.dropout, a.predictor).to(self.device)
+        self.predictor = self._linkpred_predictor(a.dim_commonEmb)
         self.optimizer = self.optfun(list(self.teacherGNN.parameters()) + list(self.predictor.parameters()), lr=a.lr, weight_decay=self.weight_decay)
+
+    def _linkpred_predictor(self, in_width):
+        """`--predictor` over embeddings of width in_width.  DOT has no parameters.  MLP, MLPDOT, MLPBIL and MLPCAT take in_width as their input width and
+        --mlp_hidden_channels as their hidden width (the reference's create_predictor_layer passes one width for both, and for MLPDOT / MLPBIL a
+        hidden width of one: the documented deviation); BIL is a bilinear form of width in_width."""
+        from .Link_prediction_model import MLPPredictor, create_predictor_layer, pair_predictor as pp
+        a = self.args
+        name, hid, n, p = a.predictor.upper(), a.mlp_hidden_channels, a.mlp_num_layers, a.dropout
+        make = {'MLP': lambda: MLPPredictor(in_width, hid, 1, n, p), 'BIL': lambda: pp.BilinearPairPredictor(in_width),
+                'MLPDOT': lambda: pp.MLPDotPairPredictor(in_width, hid, n, p), 'MLPBIL': lambda: pp.MLPBilPairPredictor(in_width, hid, n, p),
+                'MLPCAT': lambda: pp.MLPCatPairPredictor(in_width, hid, 1, n, p)}.get(name)
+        return (make() if make is not None else create_predictor_layer(hid, n, p, a.predictor)).to(self.device)
 
     def gen_linkpred_edge_index(self, mode):
         """(pos [2, P], neg [2, P * num_neg]): P = --batch_size positives of `mode` and --num_neg negatives for each, read as [P, num_neg] by the
@@ -818,7 +826,7 @@ class trainer:
         from data.edge_index (the whole graph on this device) and the link sampler on it."""
         from . import optim as cb_optim
         from .graph import CSRGraph, build_graph
-        from .Link_prediction_model import MLPPredictor, create_encoder_layer, create_input_layer, create_predictor_layer
+        from .Link_prediction_model import create_encoder_layer, create_input_layer
         from .Link_prediction_model.model import reset_input_layer
         a = self.args
         if str(a.optimizer) != 'Adam':
@@ -839,10 +847,7 @@ class trainer:
             self.encoder = TransformerEncoder(input_dim, a.gnn_hidden_channels, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout).to(self.device)
         else:
             self.encoder = create_encoder_layer(input_dim, a.gnn_hidden_channels, a.gnn_num_layers, a.dropout, a.encoder).to(self.device)
-        if a.predictor.upper() == 'MLP':
-            self.predictor = MLPPredictor(a.gnn_hidden_channels, a.mlp_hidden_channels, 1, a.mlp_num_layers, a.dropout).to(self.device)
-        else:
-            self.predictor = create_predictor_layer(a.mlp_hidden_channels, a.mlp_num_layers, a.dropout, a.predictor).to(self.device)
+        self.predictor = self._linkpred_predictor(a.gnn_hidden_channels)
         params = (list(self.emb.parameters()) if self.emb is not None else []) + list(self.encoder.parameters()) + list(self.predictor.parameters())
         self.optimizer = cb_optim.Adam(params, lr=a.lr, weight_decay=self.weight_decay)
 

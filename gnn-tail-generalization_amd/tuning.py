@@ -75,6 +75,10 @@ class Tuning:
     # predictor.score_pairs(h, pairs) scores the index pairs in place (True) or gathers h[u], h[v] and runs predictor.forward on them (False): the
     # same numbers either way (bit for bit for the MLP without dropout).  S = 262 144 pairs, D = 256, profiles/linkpred.md
     score_pairs_fused: bool = True
+    # BIL / MLPDOT / MLPBIL (Link_prediction_model.pair_predictor): with no dropout active the per-node part (the Linear stack; nothing for BIL) can be
+    # applied to the N rows of h once instead of to the 2 S endpoint rows, bit-identically.  None: where 2 S >= N (a row count, not a measurement);
+    # True / False: forced (tests, tools/bench_pairpred.py)
+    pair_predictor_per_node: object = None
 
     # ---- encoder layers of the link-prediction experiment (ops.sage_layer, cb_sage.hip) -----------------------------------------------------------
     # a 256 -> 256 layer of SAGEEncoder / WSAGEEncoder / GCNEncoder runs as ONE kernel (aggregation into an on-chip tile, [agg | x] @ [W_n ; W_s] on the

@@ -929,6 +929,42 @@ int cb_rank_loss_bwd_f32(int32_t kind, const float* pos, int64_t P, const float*
                          float* dneg, void* stream);
 
 /* ----------------------------------------------------------------------------------
+ * The device pieces of the predictors that take their endpoint rows one at a time (Link_prediction_model/layer.py:108-180 `MLPCatPredictor`,
+ * `MLPDotPredictor`, `MLPBilPredictor`, :193-203 `BilinearPredictor`); cb_pairpred.hip.  h [N, D] fp32 (ld >= D).  An index outside [0, N) is never
+ * used as an index; status [1] (zeroed by the call) counts the rows / pairs that hold one (one integer atomic each, on that path only).  No float
+ * atomics; no host synchronisation; two calls with the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+
+/* C [R, Nout] = act(A @ B + bias), B [nseg * D, Nout], A[r, s * D + k] = h[idx[s * R + r], k] for s < nseg (idx int32 [nseg, R], nseg 1 or 2): the
+ * gather h[idx] or the concatenation [h[idx0] | h[idx1]], formed while the three-limb NN kernel stages it and never written.  K loop, epilogue and
+ * tile order are those of cb_gemm_nn_f32: C has the bits cb_gemm_nn_f32 gives on the materialised A.  drop_p, seed, seed_dev, row0, C2: the dropped
+ * copy exactly as cb_pair_gemm_nn_f32 has it (the bits of cb_gemm_nn_drop2_f32; the two-kernel form for Nout <= 64 or outputs without float4
+ * alignment needs ldc == ldc2 == Nout).  A row with an unusable index is NaN in C and in C2 and counts once.
+ * Exists (cb_rows_gemm_nn_supported) where cb_pair_gemm_nn_f32 does for K = nseg * D, with D % 4 == 0 for nseg == 1 and D % 16 == 0 for nseg == 2
+ * (no K step of 16 straddles the seam); elsewhere the caller composes the gather and cb_gemm_nn_f32. */
+int cb_rows_gemm_nn_supported(const float* h, int64_t ld, int64_t D, int32_t nseg, const float* B, int64_t ldb, int64_t Nout);
+int cb_rows_gemm_nn_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* idx, int32_t nseg, int64_t R, const float* B, int64_t ldb,
+                        float* C, int64_t ldc, float* C2, int64_t ldc2, int64_t Nout, const float* bias, int relu, float drop_p, uint64_t seed,
+                        const uint64_t* seed_dev, int64_t row0, int32_t* status, void* stream);
+
+/* scores [S]: s_e = sum_j (sum_k W[j, k] h[u_e, k]) h[v_e, j] for pairs int32 [2, S]; Wt [D, D] (ldw >= D) is W TRANSPOSED (Wt[k][j] = W[j][k], the
+ * B operand of the rows GEMM over u).  The dot against row v_e is taken in the GEMM's epilogue: no [S, D] matrix is written.  A row's columns inside
+ * a tile are reduced in one fixed order and the column blocks' partials (workspace [S, column blocks] floats) are added in ascending block order by
+ * a finishing pass, so a pair's score does not depend on where in the batch it sits.  NaN and one count for an unusable pair.  Exists where
+ * cb_rows_gemm_nn_supported(h, ld, D, 1, Wt, ldw, D) holds. */
+int cb_rows_bilinear_supported(const float* h, int64_t ld, int64_t D, const float* Wt, int64_t ldw);
+size_t cb_rows_bilinear_workspace_bytes(int64_t S, int64_t D);
+int cb_rows_bilinear_f32(const float* h, int64_t ld, int64_t N, int64_t D, const int32_t* pairs, int64_t S, const float* Wt, int64_t ldw, float* scores,
+                         int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* dh [N, D] (ldd >= D) = sum_e (G0[e, :] into row u_e, G1[e, :] into row v_e): the backward of both gathers.  G0 [S, ld0] and G1 [S, ld1] have
+ * leading dimensions of their own (the two halves of one [2 S, D] matrix or the two column halves of one [S, 2 D] matrix pass without a copy).
+ * The machinery of cb_pair_scatter_f32 with a row contributed as it stands: sorted keys, float64 sums in ascending contribution number (2 e for
+ * u_e, 2 e + 1 for v_e) rounded once, untouched rows zero, unusable pairs skipped.  Workspace: cb_pair_scatter_workspace_bytes(S). */
+int cb_rows_scatter_f32(int64_t N, int64_t D, const int32_t* pairs, int64_t S, const float* G0, int64_t ld0, const float* G1, int64_t ld1, float* dh,
+                             int64_t ldd, void* ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------
  * One layer of the link-prediction encoders (Link_prediction_model/layer.py:8-35: SAGEConv with mean aggregation, GraphConv with add,
  * GCNConv(normalize=False)) in one launch; cb_sage.hip.  Widths 256 -> 256, fp32 rows, 16-byte aligned, ld >= 256 and a multiple of 4:
  *     agg[v, :] = row_scale[v] * sum_{j in row v} col_scale[col[j]] * h[col[j], :]            (row_scale / col_scale may be NULL)

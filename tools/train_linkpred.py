@@ -1,4 +1,4 @@
-"""Trains the teacher GNN as the encoder of the reference's link-prediction experiment (Link_prediction_model/: `--predictor DOT | MLP`,
+"""Trains the teacher GNN as the encoder of the reference's link-prediction experiment (Link_prediction_model/: `--predictor DOT | MLP | BIL | MLPDOT | MLPBIL | MLPCAT`,
 `--loss_func AUC | ce_loss | log_rank_loss | info_nce_loss`, `--num_neg`, `--batch_size`, `--grad_clip_norm`) on the HIP path
 (trainer.train_teacherGNN_linkpred; main.py does not route there):
     python tools/train_linkpred.py --dataset=S-tiny --predictor=MLP --loss_func=log_rank_loss --num_neg=3 --epochs=20

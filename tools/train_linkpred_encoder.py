@@ -1,5 +1,5 @@
 """Trains the reference's link-prediction model (Link_prediction_model/model.py:37-169: a trainable node embedding, `--encoder SAGE | MLP` of
-`--gnn_num_layers` layers and `--gnn_hidden_channels` width, `--predictor DOT | MLP`, `--loss_func AUC | ce_loss | log_rank_loss | info_nce_loss`,
+`--gnn_num_layers` layers and `--gnn_hidden_channels` width, `--predictor DOT | MLP | BIL | MLPDOT | MLPBIL | MLPCAT`, `--loss_func AUC | ce_loss | log_rank_loss | info_nce_loss`,
 `--num_neg`, `--batch_size`, `--grad_clip_norm`) on the HIP path (trainer.train_linkpred_encoder; main.py does not route there):
     python tools/train_linkpred_encoder.py --dataset=S-tiny --encoder=SAGE --predictor=MLP --loss_func=log_rank_loss --num_neg=3 --epochs=20
 Every step runs the encoder over the whole graph (one fused aggregation + GEMM kernel per 256 -> 256 layer where tuning.T.sage_fused is on, the
