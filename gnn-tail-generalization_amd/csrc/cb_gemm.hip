@@ -166,13 +166,6 @@ static inline int tn_splits(int64_t M, int tiles) {
   return (int)s;
 }
 
-// CB_GEMM_PLAIN_F32=1 keeps every contraction on the fp32-input MFMA (v_mfma_f32_32x32x2_f32) instead of the
-// three-limb bf16 path of cb_gemm_limb.hip
-static inline bool use_limb3() {
-  static const bool on = getenv("CB_GEMM_PLAIN_F32") == nullptr;
-  return on;
-}
-
 // fp32 outputs too large to stay cached (> 256 MiB: the Infinity Cache) leave with the streaming policy: measured -1.5 % per launch
 // on 10M x 256 outputs (7.96 -> 7.84 ms)
 static inline int gemm_nt_store(int64_t M, int64_t N) { return M * N * 4 > ((int64_t)256 << 20); }
@@ -261,9 +254,9 @@ static int launch_tn(const float* A, int64_t lda, const float* G, int64_t ldg, c
   rows_per_split = (rows_per_split + 31) / 32 * 32;   // whole K steps of either kernel family
   const bool aligned = aligned16(A) && aligned16(G) && lda % 4 == 0 && ldg % 4 == 0;
   const dim3 grid((unsigned)(tiles_i * tiles_j), (unsigned)nsplit);
-  CB_CHECK_ARG(!(gdrop || adrop) || (use_limb3() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)), CB_E_INVALID,
+  CB_CHECK_ARG(!(gdrop || adrop) || (limb3_on() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)), CB_E_INVALID,
                "TN contraction with operand dropout: three-limb path only (check cb_gemm_tn_gdrop_supported first)");
-  if (use_limb3() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)) {
+  if (limb3_on() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)) {
     const int rc = launch_tn_limb3(A, lda, G, ldg, rowscale, ws, M, K1, K2, T::BM, nsplit, rows_per_split, st, gdrop, adrop);
     if (rc != CB_OK) return rc;
     const int64_t n = K1 * K2;
@@ -310,7 +303,7 @@ extern "C" int cb_gemm_nn_f32(const float* A, int64_t lda, const float* B, int64
                "cb_gemm_nn_f32: null pointer or leading dimension too small");
   GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
   hipStream_t st = (hipStream_t)stream;
-  if (use_limb3() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, st, ws, ws_bytes);
+  if (limb3_on() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, st, ws, ws_bytes);
   if (N <= 64) return launch_nn<4, 1>(A, lda, B, ldb, C, ldc, M, N, K, ep, st, ws, ws_bytes);
   return launch_nn<2, 2>(A, lda, B, ldb, C, ldc, M, N, K, ep, st, ws, ws_bytes);
 }
@@ -330,7 +323,7 @@ extern "C" int cb_gemm_nn_drop2_f32(const float* A, int64_t lda, const float* B,
                "cb_gemm_nn_drop2_f32: null pointer or leading dimension too small");
   GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
   hipStream_t st = (hipStream_t)stream;
-  if (use_limb3() && drop_p > 0.f && limb3_nn_dual_eligible(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K, ep)) {
+  if (limb3_on() && drop_p > 0.f && limb3_nn_dual_eligible(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K, ep)) {
     ep.out2 = C2; ep.ld_out2 = ldc2; ep.thresh = dropout_threshold(drop_p); ep.keep_scale = 1.f / (1.f - drop_p);
     ep.seed = seed; ep.seed_dev = seed_dev; ep.row0 = row0;
     return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, st, ws, ws_bytes);
@@ -347,7 +340,7 @@ extern "C" int cb_gemm_nn_drop2_f32(const float* A, int64_t lda, const float* B,
 extern "C" int cb_gemm_nn_indrop_supported(const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, const float* C2,
                                            int64_t ldc2, int64_t M, int64_t N, int64_t K) {
   GemmEpilogue ep{};
-  return use_limb3() && K % 4 == 0 && limb3_nn_dual_eligible(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K, ep) ? 1 : 0;
+  return limb3_on() && K % 4 == 0 && limb3_nn_dual_eligible(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K, ep) ? 1 : 0;
 }
 
 extern "C" int cb_gemm_nn_indrop_drop2_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, float* C2, int64_t ldc2,
@@ -381,7 +374,7 @@ extern "C" int cb_gemm_nn_bf16out_f32(const float* A, int64_t lda, const float* 
                "cb_gemm_nn_bf16out_f32: null pointer or leading dimension too small");
   GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
   hipStream_t st = (hipStream_t)stream;
-  if (use_limb3() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, true, st, ws, ws_bytes);
+  if (limb3_on() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, true, st, ws, ws_bytes);
   if (N <= 64) return launch_nn<4, 1, true>(A, lda, B, ldb, C, ldc, M, N, K, ep, st);
   return launch_nn<2, 2, true>(A, lda, B, ldb, C, ldc, M, N, K, ep, st);
 }
@@ -401,7 +394,7 @@ extern "C" size_t cb_gemm_tn_workspace_bytes(int64_t M, int64_t K1, int64_t K2) 
 // by cb_trunk_store_rows_f32, whose results this reproduces bit for bit).
 extern "C" int cb_gemm_nn_store_rows_supported(const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, int64_t M, int64_t N,
                                                int64_t K) {
-  return use_limb3() && N == 256 && M > 0 && limb3_nn_eligible(A, lda, B, ldb, N, K) && aligned16(C) && ldc % 4 == 0 ? 1 : 0;
+  return limb3_on() && N == 256 && M > 0 && limb3_nn_eligible(A, lda, B, ldb, N, K) && aligned16(C) && ldc % 4 == 0 ? 1 : 0;
 }
 
 extern "C" int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
@@ -443,7 +436,7 @@ extern "C" int cb_gemm_tn_f32(const float* A, int64_t lda, const float* G, int64
 // C = A^T @ dropout_{g_seed}(G): the weight gradient of the input Linear from the UNdropped features (mask regenerated while G is
 // staged; the forward's cb_gemm_nn_indrop_drop2_f32 drew the same one).  Three-limb path only: cb_gemm_tn_gdrop_supported.
 extern "C" int cb_gemm_tn_gdrop_supported(const float* A, int64_t lda, const float* G, int64_t ldg, int64_t K1, int64_t K2) {
-  return use_limb3() && K2 % 4 == 0 && limb3_tn_eligible(A, lda, G, ldg, K1, K2) ? 1 : 0;
+  return limb3_on() && K2 % 4 == 0 && limb3_tn_eligible(A, lda, G, ldg, K1, K2) ? 1 : 0;
 }
 
 extern "C" int cb_gemm_tn_gdrop_f32(const float* A, int64_t lda, const float* G, int64_t ldg, float* C, int64_t M, int64_t K1, int64_t K2,
@@ -479,7 +472,7 @@ extern "C" int cb_gemm_tn_gdrop_f32(const float* A, int64_t lda, const float* G,
 static inline int instage_splits(int64_t M) { return tn_splits(M, 2); }
 
 extern "C" int cb_gemm_tn_instage_supported(const float* g, const float* mfold, const float* X, int64_t ldx, int64_t M, int64_t K2) {
-  return use_limb3() && K2 > 64 && K2 <= 128 && K2 % 4 == 0 && ldx % 4 == 0 && ldx >= K2 && ldx < (1 << 22) && aligned16(g) && aligned16(mfold) && aligned16(X) && M > 0 &&
+  return limb3_on() && K2 > 64 && K2 <= 128 && K2 % 4 == 0 && ldx % 4 == 0 && ldx >= K2 && ldx < (1 << 22) && aligned16(g) && aligned16(mfold) && aligned16(X) && M > 0 &&
                  instage_splits(M) >= 256
              ? 1
              : 0;
@@ -543,7 +536,7 @@ extern "C" int cb_gemm_nn_indrop_f32(const float* A, int64_t lda, const float* B
 extern "C" int cb_gemm_tn_adrop_supported(const float* A, int64_t lda, const float* G, int64_t ldg, int64_t K1, int64_t K2) {
   int bm, bn;
   tn_tile(K1, K2, bm, bn);
-  return use_limb3() && K1 % 4 == 0 && bm == 128 && limb3_tn_eligible(A, lda, G, ldg, K1, K2) ? 1 : 0;
+  return limb3_on() && K1 % 4 == 0 && bm == 128 && limb3_tn_eligible(A, lda, G, ldg, K1, K2) ? 1 : 0;
 }
 
 extern "C" int cb_gemm_tn_adrop_f32(const float* A, int64_t lda, const float* G, int64_t ldg, const float* rowscale, float* C, int64_t M, int64_t K1,

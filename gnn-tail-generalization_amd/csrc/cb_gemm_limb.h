@@ -4,6 +4,9 @@
 
 namespace cb {
 
+// The library's one switch, read once per process: CB_GEMM_PLAIN_F32=1 keeps every contraction on the fp32-input MFMA (v_mfma_f32_32x32x2_f32)
+// instead of the three-limb bf16 path; the gathered-operand GEMMs (cb_gather_gemm.h) then report "not supported".
+bool limb3_on();
 // operands 16-byte aligned with leading dimensions, K and N multiples of 4 (float4 access); any M
 bool limb3_nn_eligible(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t N, int64_t K);
 size_t limb3_nn_workspace_bytes(int64_t N, int64_t K);

@@ -34,6 +34,8 @@
 // memory pipeline are therefore all busy at any instant instead of taking turns (thread blocks that share a CU fall
 // into lock step, so phases that use only one of these units are not hidden by the neighbours).
 // Addressing inside the K loop: a wave-uniform base pointer (scalar registers) per K step plus lane offsets that never change.
+#include <stdlib.h>
+
 #include <utility>
 
 #include "cb_common.h"
@@ -252,6 +254,11 @@ static int launch_nn_l3_t(const float* A, int64_t lda, const float* B, int64_t l
                      c_vec_ok);
   CB_LAUNCH_CHECK();
   return CB_OK;
+}
+
+bool limb3_on() {
+  static const bool on = getenv("CB_GEMM_PLAIN_F32") == nullptr;
+  return on;
 }
 
 // float4 access to both operands, lane offsets in 32 bits

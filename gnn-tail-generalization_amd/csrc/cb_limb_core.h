@@ -1,6 +1,6 @@
 // Building blocks of the three-limb bf16-MFMA contractions: exact fp32 -> 3 x bf16 split, LDS operand images with their
 // fragment reads, the per-wavefront software pipeline.  Design notes: cb_gemm_limb.hip.  Used by cb_gemm_limb.hip (NN / TN
-// GEMMs) and cb_topk.hip (teacher-embedding scores + running top-K).
+// GEMMs), cb_topk.hip (teacher-embedding scores + running top-K) and cb_gather_gemm.h (the link predictors' gathered-operand GEMMs).
 #pragma once
 #include <utility>
 
@@ -114,54 +114,51 @@ struct RowOperand {
   }
 };
 
-// ---- "row" operand that is the Hadamard product of two GATHERED rows: value[r][k] = h[u_r][k] * h[v_r][k] (the link predictors' x_i * x_j,
-// Link_prediction_model/layer.py:100) — the gathered matrices and their product are never written.  Same LDS image and fragment reads as
-// RowOperand<R>.  `base` of load() is &h[0][k0] (uniform); the lane adds node * ld in 64 bits (N = 10^8 rows of 256 floats overflow 32).  A row whose
-// pair has an endpoint outside [0, N) addresses node 0 and stages zeros (the kernel overwrites its row of C).  Each product is rounded to
-// fp32 once, as a value of its own, before the split (mul_rounded): the limbs are those of the materialised h[u] * h[v].  The second row's quads live
-// in the operand, so the K loop must run at register prefetch depth 1.
-template <int R>
-struct PairRowOperand {
+// ---- "row" operands whose rows are GATHERED through an index array idx [NIDX][Rn] (the link predictors' decoders, cb_gather_gemm.h) ----------------
+// One interface, so that a kernel is written once over the operand OA:
+//   OA::NIDX       rows of idx that a tile row reads          OA::A_STEP     the K loop's advance of the A base per K step
+//   OA::WIDE_TILE  the 128 x 256 tile may be used             OA::ktot(D)    length of the reduction axis for rows of h of length D
+//   init(idx, Rn, rows_left, N, D, t)    idx = &idx[0][tile row 0], Rn = its row length, rows_left = Rn - tile row 0, N = rows of h
+//   row_of(idx, Rn, rows_left, N, row, n, in)    tile row `row` lies inside the matrix (in) and all its indices n lie in [0, N)
+// A tile row with an index outside [0, N) (or outside the matrix) addresses node 0 and stages zeros: the kernel overwrites its row of C.
+
+// What the gathered operands share: the LDS image and fragment reads of RowOperand<R>, the nodes of this lane's tile rows, and the predicate
+// row_of() that init() and the kernel's NaN-rows tail both ask.
+template <int R, int NIDX>
+struct GatheredRows {
   static constexpr int PLANE = R * 32, BYTES = 3 * PLANE, NV = R / 64;
   static_assert(NV >= 1, "tile rows");
-  int32_t nu[NV], nv[NV];      // the two nodes of tile row t/4 + 64 j; nu < 0: the row stages zeros (outside the matrix, or an unusable pair)
-  uint32_t woff;
+  int32_t nd[NIDX][NV];        // the nodes of tile row t/4 + 64 j; nd[0][j] < 0: the row stages zeros (outside the matrix, or an unusable index)
+  uint32_t woff;               // as RowOperand::woff
   static constexpr bool HAS_SC = false;
-  float sc[1];
-  float4 fv[NV];               // the second row's quads of the loaded step
-  // usable pair of tile row `row` (pairs = &pairs[0][tile row 0], S = its row length, rows_left = S - tile row 0, N = number of nodes);
-  // in: the row lies inside the matrix
-  static __device__ __forceinline__ bool pair_of(const int32_t* __restrict__ pairs, int64_t S, int64_t rows_left, int64_t N, int row, int& u, int& v, bool& in) {
+  float sc[1];                 // (interface shared with ColOperand: no per-k scale here)
+  // usable tile row `row`: it lies inside the matrix (in) and all its NIDX indices lie in [0, N)
+  static __device__ __forceinline__ bool row_of(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int row, int (&n)[NIDX], bool& in) {
     in = row < rows_left;
-    u = in ? pairs[row] : 0;
-    v = in ? pairs[S + row] : 0;
-    return in && u >= 0 && u < N && v >= 0 && v < N;
+    bool ok = in;
+#pragma unroll
+    for (int s = 0; s < NIDX; ++s) {
+      n[s] = in ? idx[s * Rn + row] : 0;
+      ok = ok && n[s] >= 0 && n[s] < N;
+    }
+    return ok;
   }
-  __device__ __forceinline__ void init(const int32_t* __restrict__ pairs, int64_t S, int64_t rows_left, int64_t N, int t) {
+  template <class OA>      // (the operand itself: its row_of)
+  __device__ __forceinline__ void init_rows(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int t) {
     const int row = t >> 2, kq = t & 3;
     woff = row * 32 + (((kq >> 1) ^ ((row >> 3) & 1)) << 4) + ((kq & 1) << 3);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      int u, v;
+      int n[NIDX];
       bool in;
-      const bool ok = pair_of(pairs, S, rows_left, N, row + 64 * j, u, v, in);
-      nu[j] = ok ? u : -1;
-      nv[j] = ok ? v : 0;
+      const bool ok = OA::row_of(idx, Rn, rows_left, N, row + 64 * j, n, in);
+#pragma unroll
+      for (int s = 0; s < NIDX; ++s) nd[s][j] = ok ? n[s] : (s == 0 ? -1 : 0);
     }
   }
+  // split v and write this lane's J-th 8-byte piece of the three planes
   template <int J>
-  __device__ __forceinline__ void load(float4 (&f)[NV], const float* __restrict__ base, int64_t ld, int64_t k_left, const float*, int t) {
-    const int kq4 = (t & 3) * 4 < k_left ? (t & 3) * 4 : 0;
-    f[J] = *reinterpret_cast<const float4*>(base + ((int64_t)(nu[J] < 0 ? 0 : nu[J]) * ld + kq4));
-    fv[J] = *reinterpret_cast<const float4*>(base + ((int64_t)nv[J] * ld + kq4));
-  }
-  template <int J>
-  __device__ __forceinline__ void stage(const float4 (&f)[NV], char* __restrict__ S, int64_t k_left, int t) const {
-    const bool live = nu[J] >= 0 && (t & 3) * 4 < k_left;
-    const float a[4] = {f[J].x, f[J].y, f[J].z, f[J].w}, b[4] = {fv[J].x, fv[J].y, fv[J].z, fv[J].w};
-    float v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = live ? mul_rounded(a[i], b[i]) : 0.f;
+  __device__ __forceinline__ void store(const float (&v)[4], char* __restrict__ S) const {
     uint2 pl[3];
     split4(v, pl);
 #pragma unroll
@@ -171,46 +168,69 @@ struct PairRowOperand {
   static __device__ __forceinline__ bf16x8 frag(const char* __restrict__ S, uint32_t addr, int plane) { return RowOperand<R>::frag(S, addr, plane); }
 };
 
-// ---- "row" operand whose rows are GATHERED (NSEG == 1: value[r][k] = h[i0_r][k]) or CONCATENATED from two gathered rows (NSEG == 2:
-// value[r][s D + k] = h[is_r][k]; the link predictors' x_i / [x_i | x_j], Link_prediction_model/layer.py:124, 151) — the gathered matrix is never
-// written.  Same LDS image and fragment reads as RowOperand<R>; the values are staged as they stand, so the limbs are those of the materialised matrix.
-// `base` of load() is &h[0][0] for EVERY K step (the K loop is run with a step advance of 0): the operand finds the step's first column
-// k0 = Ktot - k_left itself, and from it the segment and the column inside the row of h, both wave-uniform.  NSEG == 2 needs D % KS == 0 (no K step
-// straddles the seam); NSEG == 1 needs D % 4 == 0 like RowOperand.  A row with an index outside [0, N) addresses node 0 and stages zeros (the kernel
-// overwrites its row of C).  One stream of loads per K step: nothing but the indices lives in the operand.
-template <int R, int NSEG>
-struct IndexedRowOperand {
-  static constexpr int PLANE = R * 32, BYTES = 3 * PLANE, NV = R / 64;
-  static_assert(NV >= 1 && (NSEG == 1 || NSEG == 2), "tile rows; one or two segments");
-  int32_t nd[NSEG][NV];        // the nodes of tile row t/4 + 64 j; nd[0][j] < 0: the row stages zeros (outside the matrix, or an unusable index)
-  uint32_t woff;
-  int32_t D, Ktot;             // row length of h; NSEG * D
-  static constexpr bool HAS_SC = false;
-  float sc[1];
-  // usable row `row` (idx = &idx[0][tile row 0], Rn = its row length, rows_left = Rn - tile row 0); in: the row lies inside the matrix
-  static __device__ __forceinline__ bool row_of(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int row, int (&n)[NSEG], bool& in) {
+// The Hadamard product of two gathered rows: value[r][k] = h[u_r][k] * h[v_r][k], (u_r, v_r) = idx[0..1][r] (the link predictors' x_i * x_j,
+// Link_prediction_model/layer.py:100) — the gathered matrices and their product are never written.  `base` of load() is &h[0][k0] (uniform); the
+// lane adds node * ld in 64 bits (N = 10^8 rows of 256 floats overflow 32).  Each product is rounded to fp32 once, as a value of its own, before
+// the split (mul_rounded): the limbs are those of the materialised h[u] * h[v].  The second row's quads live in the operand, so the K loop must run
+// at register prefetch depth 1, and the 128 x 256 tile is left out: it sits at the 256-register cap with the plain row operand, and the second
+// stream of loads (8 registers per lane) would spill.
+template <int R>
+struct PairRowOperand : GatheredRows<R, 2> {
+  using Rows = GatheredRows<R, 2>;
+  using Rows::nd;
+  static constexpr int NV = Rows::NV, NIDX = 2, A_STEP = KS;
+  static constexpr bool WIDE_TILE = false;
+  template <class I>
+  static constexpr I ktot(I D) { return D; }
+  float4 fv[NV];               // the second row's quads of the loaded step
+  // The base's predicate without its loop over the index rows.  The 128 x 128 tile sits at its register cap of 168: with the loop, which is unrolled
+  // late, the same values reach the register allocator in another order and two to four registers spill (profiles/gather_gemm.md).
+  static __device__ __forceinline__ bool row_of(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int row, int (&n)[2], bool& in) {
     in = row < rows_left;
-    bool ok = in;
-#pragma unroll
-    for (int s = 0; s < NSEG; ++s) {
-      n[s] = in ? idx[s * Rn + row] : 0;
-      ok = ok && n[s] >= 0 && n[s] < N;
-    }
-    return ok;
+    n[0] = in ? idx[row] : 0;
+    n[1] = in ? idx[Rn + row] : 0;
+    return in && n[0] >= 0 && n[0] < N && n[1] >= 0 && n[1] < N;
   }
+  __device__ __forceinline__ void init(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int /*D*/, int t) {
+    this->template init_rows<PairRowOperand>(idx, Rn, rows_left, N, t);
+  }
+  template <int J>
+  __device__ __forceinline__ void load(float4 (&f)[NV], const float* __restrict__ base, int64_t ld, int64_t k_left, const float*, int t) {
+    const int kq4 = (t & 3) * 4 < k_left ? (t & 3) * 4 : 0;
+    f[J] = *reinterpret_cast<const float4*>(base + ((int64_t)(nd[0][J] < 0 ? 0 : nd[0][J]) * ld + kq4));
+    fv[J] = *reinterpret_cast<const float4*>(base + ((int64_t)nd[1][J] * ld + kq4));
+  }
+  template <int J>
+  __device__ __forceinline__ void stage(const float4 (&f)[NV], char* __restrict__ S, int64_t k_left, int t) const {
+    const bool live = nd[0][J] >= 0 && (t & 3) * 4 < k_left;
+    const float a[4] = {f[J].x, f[J].y, f[J].z, f[J].w}, b[4] = {fv[J].x, fv[J].y, fv[J].z, fv[J].w};
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = live ? mul_rounded(a[i], b[i]) : 0.f;
+    this->template store<J>(v, S);
+  }
+};
+
+// Rows gathered (NSEG == 1: value[r][k] = h[i0_r][k]) or concatenated from two gathered rows (NSEG == 2: value[r][s D + k] = h[is_r][k]; the
+// link predictors' x_i / [x_i | x_j], Link_prediction_model/layer.py:124, 151) — the gathered matrix is never written.  The values are staged as
+// they stand, so the limbs are those of the materialised matrix.  `base` of load() is &h[0][0] for EVERY K step (A_STEP == 0): the operand finds
+// the step's first column k0 = Ktot - k_left itself, and from it the segment and the column inside the row of h, both wave-uniform.  NSEG == 2
+// needs D % KS == 0 (no K step straddles the seam); NSEG == 1 needs D % 4 == 0 like RowOperand.  One stream of loads per K step (a K step lies in
+// one segment) and nothing but the indices in the operand: the 128 x 256 tile fits (246 VGPRs for one segment, 250 for two, no scratch, no spill).
+template <int R, int NSEG>
+struct IndexedRowOperand : GatheredRows<R, NSEG> {
+  static_assert(NSEG == 1 || NSEG == 2, "one or two segments");
+  using Rows = GatheredRows<R, NSEG>;
+  using Rows::nd;
+  static constexpr int NV = Rows::NV, NIDX = NSEG, A_STEP = 0;
+  static constexpr bool WIDE_TILE = true;
+  template <class I>
+  static constexpr I ktot(I D) { return NSEG * D; }
+  int32_t D, Ktot;             // row length of h; NSEG * D
   __device__ __forceinline__ void init(const int32_t* __restrict__ idx, int64_t Rn, int64_t rows_left, int64_t N, int d, int t) {
-    const int row = t >> 2, kq = t & 3;
-    woff = row * 32 + (((kq >> 1) ^ ((row >> 3) & 1)) << 4) + ((kq & 1) << 3);
     D = d;
     Ktot = NSEG * d;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      int n[NSEG];
-      bool in;
-      const bool ok = row_of(idx, Rn, rows_left, N, row + 64 * j, n, in);
-#pragma unroll
-      for (int s = 0; s < NSEG; ++s) nd[s][j] = ok ? n[s] : (s == 0 ? -1 : 0);
-    }
+    this->template init_rows<IndexedRowOperand>(idx, Rn, rows_left, N, t);
   }
   template <int J>
   __device__ __forceinline__ void load(float4 (&f)[NV], const float* __restrict__ base, int64_t ld, int64_t k_left, const float*, int t) const {
@@ -229,13 +249,8 @@ struct IndexedRowOperand {
   __device__ __forceinline__ void stage(const float4 (&f)[NV], char* __restrict__ S, int64_t k_left, int t) const {
     const bool live = nd[0][J] >= 0 && (t & 3) * 4 < k_left;
     const float v[4] = {live ? f[J].x : 0.f, live ? f[J].y : 0.f, live ? f[J].z : 0.f, live ? f[J].w : 0.f};
-    uint2 pl[3];
-    split4(v, pl);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(S + p * PLANE + woff + J * (64 * 32)) = pl[p];
+    this->template store<J>(v, S);
   }
-  static __device__ __forceinline__ uint32_t frag_addr(int r0, int lane) { return RowOperand<R>::frag_addr(r0, lane); }
-  static __device__ __forceinline__ bf16x8 frag(const char* __restrict__ S, uint32_t addr, int plane) { return RowOperand<R>::frag(S, addr, plane); }
 };
 
 // ---- "col" operand: global [k][cols] (cols contiguous) -> LDS planes [16 k][C cols] ------------------

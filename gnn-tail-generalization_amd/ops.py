@@ -1622,11 +1622,24 @@ RANK_KINDS = {'auc_loss': 0, 'adaptive_auc_loss': 1, 'log_rank_loss': 2, 'ce_los
 _pair_bad = _Ledger()      # unusable pairs since the last pair_check()
 
 
-def _pair_args(who, h, pairs):
+def _embedding_arg(who, h):
     if not torch.is_tensor(h) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[0] < 1 or h.shape[1] < 1:
         raise ValueError(f'{who} expects a float32 [N, D] embedding matrix')
+
+
+def _pair_args(who, h, pairs):
+    _embedding_arg(who, h)
     _lib.require_device(h)
     return _pairs_arg(f'{who}: pairs', pairs, h.device, 'S')
+
+
+def _scatter_out(who, out, N, D, S, dev, of):
+    """(dH, workspace, its size) of the two scatters: out validated, or a fresh [N, D]."""
+    dh = torch.empty((N, D), dtype=torch.float32, device=dev) if out is None else out
+    if tuple(dh.shape) != (N, D) or dh.dtype != torch.float32 or dh.stride(1) != 1 or dh.stride(0) < D or dh.device != dev:
+        raise ValueError(f'{who}: out must be a float32 [{N}, {D}] matrix with contiguous rows on the device of {of}')
+    wsb = _lib.load().cb_pair_scatter_workspace_bytes(S)
+    return dh, _ws(wsb, dev), wsb
 
 
 def pair_check():
@@ -1646,11 +1659,7 @@ def _pair_scatter_raw(h, pairs, coef, out=None):
     S = pairs.shape[1]
     coef = _pair_rows(coef) if coef.dim() == 2 else _c(coef)
     ldcoef = 0 if coef.dim() == 1 else (coef.stride(0) if S > 1 else D)
-    dh = torch.empty((N, D), dtype=torch.float32, device=h.device) if out is None else out
-    if tuple(dh.shape) != (N, D) or dh.dtype != torch.float32 or dh.stride(1) != 1 or dh.stride(0) < D or dh.device != h.device:
-        raise ValueError(f'pair scatter: out must be a float32 [{N}, {D}] matrix with contiguous rows on the device of h')
-    wsb = lib.cb_pair_scatter_workspace_bytes(S)
-    ws = _ws(wsb, h.device)
+    dh, ws, wsb = _scatter_out('pair scatter', out, N, D, S, h.device, 'h')
     with torch.cuda.device(h.device):
         _lib.check(lib.cb_pair_scatter_f32(_lib.ptr(h), h.stride(0), N, D, _lib.ptr(pairs), S, _lib.ptr(coef), ldcoef, _lib.ptr(dh), dh.stride(0) if N > 1 else D, _lib.ptr(ws), wsb,
                                            _lib.stream_ptr()), 'cb_pair_scatter_f32')
@@ -1691,105 +1700,12 @@ def pair_dot(h, pairs, return_status=False):
     return (scores, status) if return_status else scores
 
 
-def pair_linear_supported(h, weight):
-    """The fused first layer exists for this shape (cb_pair_gemm_nn_supported): in and out widths multiples of 4, 16-byte aligned rows."""
-    lib = _lib.load()
-    e, b = _pair_rows(h), weight.t().contiguous()
-    K, Nout = b.shape
-    return e.shape[1] == K and bool(lib.cb_pair_gemm_nn_supported(_lib.ptr(e), e.stride(0), _lib.ptr(b), Nout, Nout, K))
-
-
 def _pair_product(h, pairs):
     """h[u] * h[v] materialised; the row of an unusable pair is zero (its endpoints are never used as indices: they are replaced by node 0 first)."""
     N = h.shape[0]
     ok = ((pairs >= 0) & (pairs < N)).all(0)
     u, v = torch.where(ok, pairs[0], 0).long(), torch.where(ok, pairs[1], 0).long()
     return (h[u] * h[v]) * ok[:, None].to(h.dtype)
-
-
-def _pair_linear_raw(e, pairs, b, bias, relu, p, seed, row0):
-    """(y, dropout_p(y) | None, status) of cb_pair_gemm_nn_f32: y = act((e[u] * e[v]) @ b + bias), b [K, Nout] contiguous."""
-    lib = _lib.load()
-    N, K = e.shape
-    S, Nout = pairs.shape[1], b.shape[1]
-    dev = e.device
-    y = torch.empty((S, Nout), dtype=torch.float32, device=dev)
-    yd = torch.empty((S, Nout), dtype=torch.float32, device=dev) if p > 0.0 else None
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.cb_pair_gemm_nn_f32(_lib.ptr(e), e.stride(0), N, _lib.ptr(pairs), S, _lib.ptr(b), Nout, _lib.ptr(y), Nout, _lib.ptr(yd), Nout,
-                                           Nout, K, _lib.ptr(bias), int(bool(relu)), float(p), ctypes.c_uint64(seed), seed_dev_ptr(), int(row0),
-                                           _lib.ptr(status), _lib.stream_ptr()), 'cb_pair_gemm_nn_f32')
-    return y, yd, status
-
-
-class _PairLinearFn(torch.autograd.Function):
-    """Y = act((h[u] * h[v]) @ W^T + b), nn.Linear's weight layout [out, in]; returns dropout_p(Y) when p > 0."""
-
-    @staticmethod
-    def forward(ctx, h, pairs, weight, bias, relu, p, seed, row0, fused):
-        from . import gemm
-        lib = _lib.load()
-        e = _pair_rows(h)
-        N, K = e.shape
-        S, Nout = pairs.shape[1], weight.shape[0]
-        b = weight.t().contiguous()
-        can = S > 0 and bool(lib.cb_pair_gemm_nn_supported(_lib.ptr(e), e.stride(0), _lib.ptr(b), Nout, Nout, K))
-        if fused and not can:
-            raise _lib.HipExtensionError('pair_linear: the fused form does not exist for this shape (pair_linear_supported)')
-        if can and fused is not False:
-            y, yd, status = _pair_linear_raw(e, pairs, b, bias, relu, p, seed, row0)
-        else:      # the shape is outside the fused form: the same operators one after the other
-            x = _pair_product(e, pairs)
-            y = gemm.mm_nn(x, b, bias=bias, relu=relu)
-            ok = (pairs >= 0).all(0) & (pairs < N).all(0)
-            y = torch.where(ok[:, None], y, torch.full_like(y, float('nan')))
-            status = (~ok).sum().to(torch.int32).reshape(1)
-            yd = _dropout_raw(y, p, seed, row0 * Nout) if p > 0.0 else None
-        ctx.relu, ctx.p, ctx.seed, ctx.row0, ctx.has_bias = bool(relu), float(p), int(seed), int(row0), bias is not None
-        ctx.save_for_backward(e, pairs, weight, y if relu else None)
-        ctx.mark_non_differentiable(status)
-        return (yd if p > 0.0 else y), status
-
-    @staticmethod
-    def backward(ctx, g, _unused):
-        from . import gemm
-        e, pairs, weight, y = ctx.saved_tensors
-        Nout = weight.shape[0]
-        g = _c(g)
-        if ctx.p > 0.0:
-            g = _dropout_raw(g, ctx.p, ctx.seed, ctx.row0 * Nout)
-        need_b = ctx.has_bias and ctx.needs_input_grad[3]
-        if ctx.relu or need_b:
-            gm, db = act_bwd(g, y if ctx.relu else None, None, want_out=ctx.relu, want_colsum=need_b)
-            if gm is None:
-                gm = g
-        else:
-            gm, db = g, None
-        dh = _pair_scatter_raw(e, pairs, gemm.mm_nn(gm, weight)) if ctx.needs_input_grad[0] else None      # dX = gm @ W, scattered with row coefficients
-        dw = gemm.mm_tn(gm, _pair_product(e, pairs)) if ctx.needs_input_grad[2] else None                  # the product matrix exists here only
-        return dh, None, dw, db, None, None, None, None, None
-
-
-def pair_linear(h, pairs, weight, bias=None, relu=False, p=0.0, seed=None, row0=0, return_status=False, fused=None):
-    """act((h[u] * h[v]) @ weight^T + bias), then F.dropout(p) when p > 0: the first Linear of `MLPPredictor.forward(h[u], h[v])` (layer.py:99-104)
-    on index pairs.  The product is formed while the three-limb GEMM stages its A operand (cb_pair_gemm_nn_f32): neither gathered matrix nor the
-    product is written in the forward, and the output has the bits of gemm.mm_nn(h[u] * h[v], weight.t(), bias, relu) — with p > 0 those of
-    gemm.mm_nn_drop2 for (seed, row0).  Backward: act_bwd, dX = gm @ W on mm_nn, dH through the sorted inverted index with row coefficients (no
-    atomics), dW = gm^T @ (h[u] * h[v]) on mm_tn over a product matrix materialised there.  Where the fused form does not exist for the shape
-    (pair_linear_supported) the same operators run one after the other; fused=False asks for that.  Unusable pairs: as pair_dot."""
-    pairs = _pair_args('pair_linear', h, pairs)
-    _lib.require_device(weight, bias)
-    if weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[1] != h.shape[1]:
-        raise ValueError(f'pair_linear: weight must be a float32 [out, {h.shape[1]}] matrix')
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError('pair_linear: 0 <= p < 1 required')
-    if p > 0.0 and seed is None:
-        seed = next_seed()
-    y, status = _PairLinearFn.apply(h, pairs, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
-    _pair_bad.add(status)
-    return (y, status) if return_status else y
 
 
 class _RankLossFn(torch.autograd.Function):
@@ -1864,11 +1780,7 @@ def pair_scatter_rows(pairs, g0, g1, n_rows, out=None):
         raise ValueError(f'pair_scatter_rows: {pairs.shape[1]} pairs for {S} rows, or n_rows < 1, or an empty row')
     lib = _lib.load()
     g0, g1 = _pair_rows(g0), _pair_rows(g1)
-    dh = torch.empty((N, D), dtype=torch.float32, device=g0.device) if out is None else out
-    if tuple(dh.shape) != (N, D) or dh.dtype != torch.float32 or dh.stride(1) != 1 or dh.stride(0) < D or dh.device != g0.device:
-        raise ValueError(f'pair_scatter_rows: out must be a float32 [{N}, {D}] matrix with contiguous rows on the device of the rows')
-    wsb = lib.cb_pair_scatter_workspace_bytes(S)
-    ws = _ws(wsb, g0.device)
+    dh, ws, wsb = _scatter_out('pair_scatter_rows', out, N, D, S, g0.device, 'the rows')
     with torch.cuda.device(g0.device):
         _lib.check(lib.cb_rows_scatter_f32(N, D, _lib.ptr(pairs), S, _lib.ptr(g0), g0.stride(0) if S > 1 else D, _lib.ptr(g1), g1.stride(0) if S > 1 else D,
                                                 _lib.ptr(dh), dh.stride(0) if N > 1 else D, _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_rows_scatter_f32')
@@ -1876,8 +1788,7 @@ def pair_scatter_rows(pairs, g0, g1, n_rows, out=None):
 
 
 def _rows_idx_arg(who, h, idx):
-    if not torch.is_tensor(h) or h.dim() != 2 or h.dtype != torch.float32 or h.shape[0] < 1 or h.shape[1] < 1:
-        raise ValueError(f'{who} expects a float32 [N, D] embedding matrix')
+    _embedding_arg(who, h)
     _lib.require_device(h, idx)
     if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[0] not in (1, 2) or idx.dtype not in (torch.int32, torch.int64):
         raise ValueError(f'{who}: idx must be an int32 / int64 [nseg, R] tensor, nseg 1 or 2')
@@ -1898,49 +1809,6 @@ def _rows_operand(h, idx):
     return torch.cat([h[safe[s]] for s in range(idx.shape[0])], dim=1) * ok[:, None].to(h.dtype)
 
 
-def rows_linear_supported(h, idx, weight):
-    """The fused form exists for this shape (cb_rows_gemm_nn_supported): out width a multiple of 4, row length a multiple of 4 (one segment) or of 16
-    (two segments: no K step straddles the seam), 16-byte aligned rows."""
-    lib = _lib.load()
-    e, b = _pair_rows(h), weight.t().contiguous()
-    K, Nout = b.shape
-    nseg = idx.shape[0]
-    return nseg * e.shape[1] == K and bool(lib.cb_rows_gemm_nn_supported(_lib.ptr(e), e.stride(0), e.shape[1], nseg, _lib.ptr(b), Nout, Nout))
-
-
-def _rows_linear_raw(e, idx, b, bias, relu, p, seed, row0):
-    """(y, dropout_p(y) | None, status) of cb_rows_gemm_nn_f32: y = act([e[idx[0]] | ...] @ b + bias), b [nseg * D, Nout] contiguous."""
-    lib = _lib.load()
-    N, D = e.shape
-    (nseg, R), Nout = idx.shape, b.shape[1]
-    dev = e.device
-    y = torch.empty((R, Nout), dtype=torch.float32, device=dev)
-    yd = torch.empty((R, Nout), dtype=torch.float32, device=dev) if p > 0.0 else None
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.cb_rows_gemm_nn_f32(_lib.ptr(e), e.stride(0), N, D, _lib.ptr(idx), nseg, R, _lib.ptr(b), Nout, _lib.ptr(y), Nout, _lib.ptr(yd), Nout,
-                                           Nout, _lib.ptr(bias), int(bool(relu)), float(p), ctypes.c_uint64(seed), seed_dev_ptr(), int(row0),
-                                           _lib.ptr(status), _lib.stream_ptr()), 'cb_rows_gemm_nn_f32')
-    return y, yd, status
-
-
-def _rows_linear_any(e, idx, b, bias=None, relu=False, p=0.0, seed=0, row0=0, fused=None):
-    """_rows_linear_raw where the fused form exists (and fused is not False), else the same operators one after the other; no autograd."""
-    from . import gemm
-    lib = _lib.load()
-    (nseg, R), Nout = idx.shape, b.shape[1]
-    can = R > 0 and bool(lib.cb_rows_gemm_nn_supported(_lib.ptr(e), e.stride(0), e.shape[1], nseg, _lib.ptr(b), Nout, Nout))
-    if fused and not can:
-        raise _lib.HipExtensionError('rows_linear: the fused form does not exist for this shape (rows_linear_supported)')
-    if can and fused is not False:
-        return _rows_linear_raw(e, idx, b, bias, relu, p, seed, row0)
-    ok = _rows_ok(e, idx)
-    y = gemm.mm_nn(_rows_operand(e, idx), b, bias=bias, relu=relu)
-    y = torch.where(ok[:, None], y, torch.full_like(y, float('nan')))
-    status = (~ok).sum().to(torch.int32).reshape(1)
-    return y, (_dropout_raw(y, p, seed, row0 * Nout) if p > 0.0 else None), status
-
-
 def _scatter_segments(idx, dx, D, n_rows):
     """dH of a rows GEMM from dX [R, nseg * D].  Two segments: the column halves of dX go to idx[0] and idx[1].  One segment: rows r < R / 2 and
     r >= R / 2 are the two sides of R / 2 pairs (an odd R gets one zero row with the last index once more)."""
@@ -1954,14 +1822,86 @@ def _scatter_segments(idx, dx, D, n_rows):
     return pair_scatter_rows(idx.reshape(2, R // 2), dx[:R // 2], dx[R // 2:], n_rows)
 
 
-class _RowsLinearFn(torch.autograd.Function):
-    """Y = act([h[idx[0]] | h[idx[1]]] @ W^T + b), nn.Linear's weight layout [out, in]; returns dropout_p(Y) when p > 0."""
+class _GatherForm:
+    """What differs between the two linears whose A operand is gathered while the GEMM stages it (csrc/cb_gather_gemm.h): the product form
+    (h[u] * h[v], cb_pair_gemm_nn_f32) and the rows form (h[i] or [h[i] | h[j]], cb_rows_gemm_nn_f32)."""
+
+    def __init__(self, who, entry, args, query, idx_arg, ktot, operand, scatter):
+        self.who, self.entry = who, entry      # the public function's name (messages); the C entry
+        self.args = args                       # (e, idx, out) -> the entry's arguments up to bias, out = (b, ldb, y, ldc, yd, ldc2, Nout)
+        self.query = query                     # (lib, e, idx, b) -> the entry's *_supported answer
+        self.idx_arg = idx_arg                 # (who, h, idx) -> the validated int32 index tensor
+        self.ktot = ktot                       # (h, idx) -> columns of A
+        self.operand = operand                 # (e, idx) -> A materialised (zero rows for unusable indices)
+        self.scatter = scatter                 # (e, idx, dX) -> dH
+
+    def supported(self, e, idx, b):
+        return bool(self.query(_lib.load(), e, idx, b))
+
+    def raw(self, e, idx, b, bias, relu, p, seed, row0):
+        """(y, dropout_p(y) | None, status) of the fused entry: y = act(A @ b + bias), b [Ktot, Nout] contiguous, idx int32 and contiguous."""
+        lib = _lib.load()
+        R, Nout = idx.shape[1], b.shape[1]
+        dev = e.device
+        y = torch.empty((R, Nout), dtype=torch.float32, device=dev)
+        yd = torch.empty((R, Nout), dtype=torch.float32, device=dev) if p > 0.0 else None
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        out = (_lib.ptr(b), Nout, _lib.ptr(y), Nout, _lib.ptr(yd), Nout, Nout)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, self.entry)(*self.args(e, idx, out), _lib.ptr(bias), int(bool(relu)), float(p), ctypes.c_uint64(seed), seed_dev_ptr(),
+                                                int(row0), _lib.ptr(status), _lib.stream_ptr()), self.entry)
+        return y, yd, status
+
+    def any(self, e, idx, b, bias=None, relu=False, p=0.0, seed=0, row0=0, fused=None):
+        """raw() where the fused form exists (and fused is not False), else the same operators one after the other; no autograd."""
+        from . import gemm
+        Nout = b.shape[1]
+        can = idx.shape[1] > 0 and self.supported(e, idx, b)
+        if fused and not can:
+            raise _lib.HipExtensionError(f'{self.who}: the fused form does not exist for this shape ({self.who}_supported)')
+        if can and fused is not False:
+            return self.raw(e, idx, b, bias, relu, p, seed, row0)
+        ok = _rows_ok(e, idx)
+        y = gemm.mm_nn(self.operand(e, idx), b, bias=bias, relu=relu)
+        y = torch.where(ok[:, None], y, torch.full_like(y, float('nan')))
+        status = (~ok).sum().to(torch.int32).reshape(1)
+        return y, (_dropout_raw(y, p, seed, row0 * Nout) if p > 0.0 else None), status
+
+
+_PRODUCT = _GatherForm(
+    'pair_linear', 'cb_pair_gemm_nn_f32',
+    lambda e, pairs, out: (_lib.ptr(e), e.stride(0), e.shape[0], _lib.ptr(pairs), pairs.shape[1], *out, e.shape[1]),
+    lambda lib, e, pairs, b: lib.cb_pair_gemm_nn_supported(_lib.ptr(e), e.stride(0), _lib.ptr(b), b.shape[1], b.shape[1], b.shape[0]),
+    _pair_args, lambda h, pairs: h.shape[1], _pair_product, lambda e, pairs, dx: _pair_scatter_raw(e, pairs, dx))
+_ROWS = _GatherForm(
+    'rows_linear', 'cb_rows_gemm_nn_f32',
+    lambda e, idx, out: (_lib.ptr(e), e.stride(0), e.shape[0], e.shape[1], _lib.ptr(idx), idx.shape[0], idx.shape[1], *out),
+    lambda lib, e, idx, b: lib.cb_rows_gemm_nn_supported(_lib.ptr(e), e.stride(0), e.shape[1], idx.shape[0], _lib.ptr(b), b.shape[1], b.shape[1]),
+    _rows_idx_arg, lambda h, idx: idx.shape[0] * h.shape[1], _rows_operand, lambda e, idx, dx: _scatter_segments(idx, dx, e.shape[1], e.shape[0]))
+_pair_linear_raw, _rows_linear_raw, _rows_linear_any = _PRODUCT.raw, _ROWS.raw, _ROWS.any
+
+
+def pair_linear_supported(h, weight):
+    """The fused first layer exists for this shape (cb_pair_gemm_nn_supported): in and out widths multiples of 4, 16-byte aligned rows."""
+    e, b = _pair_rows(h), weight.t().contiguous()
+    return e.shape[1] == b.shape[0] and _PRODUCT.supported(e, None, b)
+
+
+def rows_linear_supported(h, idx, weight):
+    """The fused form exists for this shape (cb_rows_gemm_nn_supported): out width a multiple of 4, row length a multiple of 4 (one segment) or of 16
+    (two segments: no K step straddles the seam), 16-byte aligned rows."""
+    e, b = _pair_rows(h), weight.t().contiguous()
+    return _ROWS.ktot(e, idx) == b.shape[0] and _ROWS.supported(e, idx, b)
+
+
+class _GatherLinearFn(torch.autograd.Function):
+    """Y = act(A @ W^T + b) with A the form's gathered operand, nn.Linear's weight layout [out, in]; returns dropout_p(Y) when p > 0."""
 
     @staticmethod
-    def forward(ctx, h, idx, weight, bias, relu, p, seed, row0, fused):
+    def forward(ctx, form, h, idx, weight, bias, relu, p, seed, row0, fused):
         e = _pair_rows(h)
-        y, yd, status = _rows_linear_any(e, idx, weight.t().contiguous(), bias, relu, p, seed, row0, fused)
-        ctx.relu, ctx.p, ctx.seed, ctx.row0, ctx.has_bias = bool(relu), float(p), int(seed), int(row0), bias is not None
+        y, yd, status = form.any(e, idx, weight.t().contiguous(), bias, relu, p, seed, row0, fused)
+        ctx.form, ctx.relu, ctx.p, ctx.seed, ctx.row0, ctx.has_bias = form, bool(relu), float(p), int(seed), int(row0), bias is not None
         ctx.save_for_backward(e, idx, weight, y if relu else None)
         ctx.mark_non_differentiable(status)
         return (yd if p > 0.0 else y), status
@@ -1974,16 +1914,41 @@ class _RowsLinearFn(torch.autograd.Function):
         g = _c(g)
         if ctx.p > 0.0:
             g = _dropout_raw(g, ctx.p, ctx.seed, ctx.row0 * Nout)
-        need_b = ctx.has_bias and ctx.needs_input_grad[3]
+        need_b = ctx.has_bias and ctx.needs_input_grad[4]
         if ctx.relu or need_b:
             gm, db = act_bwd(g, y if ctx.relu else None, None, want_out=ctx.relu, want_colsum=need_b)
             if gm is None:
                 gm = g
         else:
             gm, db = g, None
-        dh = _scatter_segments(idx, gemm.mm_nn(gm, weight), e.shape[1], e.shape[0]) if ctx.needs_input_grad[0] else None      # dX = gm @ W
-        dw = gemm.mm_tn(gm, _rows_operand(e, idx)) if ctx.needs_input_grad[2] else None                                      # A exists here only
-        return dh, None, dw, db, None, None, None, None, None
+        dh = ctx.form.scatter(e, idx, gemm.mm_nn(gm, weight)) if ctx.needs_input_grad[1] else None      # dX = gm @ W, scattered by the form
+        dw = gemm.mm_tn(gm, ctx.form.operand(e, idx)) if ctx.needs_input_grad[3] else None             # A exists here only
+        return None, dh, None, dw, db, None, None, None, None, None
+
+
+def _gather_linear(form, h, idx, weight, bias, relu, p, seed, row0, return_status, fused):
+    idx = form.idx_arg(form.who, h, idx)
+    _lib.require_device(weight, bias)
+    if weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[1] != form.ktot(h, idx):
+        raise ValueError(f'{form.who}: weight must be a float32 [out, {form.ktot(h, idx)}] matrix')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'{form.who}: 0 <= p < 1 required')
+    if p > 0.0 and seed is None:
+        seed = next_seed()
+    y, status = _GatherLinearFn.apply(form, h, idx, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
+    _pair_bad.add(status)
+    return (y, status) if return_status else y
+
+
+def pair_linear(h, pairs, weight, bias=None, relu=False, p=0.0, seed=None, row0=0, return_status=False, fused=None):
+    """act((h[u] * h[v]) @ weight^T + bias), then F.dropout(p) when p > 0: the first Linear of `MLPPredictor.forward(h[u], h[v])` (layer.py:99-104)
+    on index pairs.  The product is formed while the three-limb GEMM stages its A operand (cb_pair_gemm_nn_f32): neither gathered matrix nor the
+    product is written in the forward, and the output has the bits of gemm.mm_nn(h[u] * h[v], weight.t(), bias, relu) — with p > 0 those of
+    gemm.mm_nn_drop2 for (seed, row0).  Backward: act_bwd, dX = gm @ W on mm_nn, dH through the sorted inverted index with row coefficients (no
+    atomics), dW = gm^T @ (h[u] * h[v]) on mm_tn over a product matrix materialised there.  Where the fused form does not exist for the shape
+    (pair_linear_supported) the same operators run one after the other; fused=False asks for that.  Unusable pairs: as pair_dot."""
+    return _gather_linear(_PRODUCT, h, pairs, weight, bias, relu, p, seed, row0, return_status, fused)
 
 
 def rows_linear(h, idx, weight, bias=None, relu=False, p=0.0, seed=None, row0=0, return_status=False, fused=None):
@@ -1994,18 +1959,7 @@ def rows_linear(h, idx, weight, bias=None, relu=False, p=0.0, seed=None, row0=0,
     an unusable index drops that pair's two rows), dW = gm^T @ A on mm_tn over an A materialised there.  Where the fused form does not exist for
     the shape (rows_linear_supported) the same operators run one after the other; fused=False asks for that, fused=True raises there.  A row with
     an index outside [0, N) is NaN and counts in the status that pair_check() reads."""
-    idx = _rows_idx_arg('rows_linear', h, idx)
-    _lib.require_device(weight, bias)
-    if weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[1] != idx.shape[0] * h.shape[1]:
-        raise ValueError(f'rows_linear: weight must be a float32 [out, {idx.shape[0] * h.shape[1]}] matrix')
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError('rows_linear: 0 <= p < 1 required')
-    if p > 0.0 and seed is None:
-        seed = next_seed()
-    y, status = _RowsLinearFn.apply(h, idx, weight, bias, bool(relu), p, int(seed or 0), int(row0), None if fused is None else bool(fused))
-    _pair_bad.add(status)
-    return (y, status) if return_status else y
+    return _gather_linear(_ROWS, h, idx, weight, bias, relu, p, seed, row0, return_status, fused)
 
 
 def pair_bilinear_supported(h, weight):

@@ -231,9 +231,10 @@ def test_the_new_hip_file_compiles_clean_under_wall_without_scratch(name, tmp_pa
     assert len(names) == len(scratch) == len(occ) >= 1
     assert not any(scratch), dict(zip(names, scratch))
     if name == 'cb_linkpred':
-        assert len(names) >= 12 and sum('k_pair_gemm_nn_l3' in n for n in names) == 3
+        pair = [n for n in names if 'k_gather_gemm_nn_l3' in n and 'PairRowOperand' in n]      # (the kernel template of cb_gather_gemm.h over the pair operand)
+        assert len(names) >= 12 and len(pair) == 3 and sum('k_gather_gemm_nn_l3' in n for n in names) == 3
         for n, o in zip(names, occ):
-            if 'k_pair_gemm_nn_l3ILi2ELi2ELi2E' in n:
+            if 'k_gather_gemm_nn_l3ILi2ELi2ELi2E' in n:
                 assert o >= 3, (n, o)
 
 

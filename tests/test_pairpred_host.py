@@ -221,10 +221,11 @@ def test_the_new_hip_file_compiles_clean_under_wall_without_scratch(tmp_path):
     occ = [int(v) for v in re.findall(r'Occupancy \[waves/SIMD\]: (\d+)', r.stderr)]
     assert len(names) == len(scratch) == len(spill) == len(occ) >= 1
     assert not any(scratch) and not any(spill), dict(zip(names, zip(scratch, spill)))
-    assert sum('k_rows_gemm_nn_l3' in n for n in names) == 10 and sum('k_pair_bilinear_l3' in n for n in names) == 2      # 2 segment counts x (256x64, two 128-row tiles x 2 epilogues)
-    assert sum('k_rows_gemm_nn_l3ILi2ELi2ELi4E' in n for n in names) == 4
+    rows = [n for n in names if 'k_gather_gemm_nn_l3' in n and 'IndexedRowOperand' in n]      # (the kernel template of cb_gather_gemm.h over the indexed operand)
+    assert len(rows) == 10 and sum('k_gather_gemm_nn_l3' in n for n in names) == 10 and sum('k_pair_bilinear_l3' in n for n in names) == 2      # 2 segment counts x (256x64, two 128-row tiles x 2 epilogues)
+    assert sum('k_gather_gemm_nn_l3ILi2ELi2ELi4E' in n for n in rows) == 4
     for n, o in zip(names, occ):
-        if 'k_rows_gemm_nn_l3ILi2ELi2ELi2E' in n or 'k_pair_bilinear_l3ILi2ELi2ELi2E' in n:
+        if 'k_gather_gemm_nn_l3ILi2ELi2ELi2E' in n or 'k_pair_bilinear_l3ILi2ELi2ELi2E' in n:
             assert o >= 3, (n, o)
-        elif 'k_rows_gemm_nn_l3' in n or 'k_pair_bilinear_l3' in n:
+        elif 'k_gather_gemm_nn_l3' in n or 'k_pair_bilinear_l3' in n:
             assert o >= 2, (n, o)
