@@ -90,14 +90,24 @@ __global__ void __launch_bounds__(kBlock) k_nll_fused(const float* __restrict__ 
     }
     float mx = -INFINITY;
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, zr[c]);
+    // se in partial sums of 64 columns, then their sum: one chain of C additions loses about sqrt(C) roundings (at C = 4096 the gradient was nine
+    // times further from float64 than a pairwise float32 sum).  C <= 64 is a single chain, 0 + it: the bits of before and of the vector kernels.
     float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(zr[c] - mx);
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      const int c1 = c0 + 64 < C ? c0 + 64 : C;
+      float part = 0.f;
+      for (int c = c0; c < c1; ++c) part += expf(zr[c] - mx);
+      se += part;
+    }
     const float lse = mx + logf(se);
     const int64_t t = y[r];
-    local += lse - zr[t];
+    const bool ok = t >= 0 && t < C;      // a label outside [0, C) is never an index: the row's loss term and gradient row are NaN
+    const float zt = zr[ok ? t : 0];
+    local += ok ? lse - zt : NAN;
     if (gr) {
       const float inv = 1.f / se;
-      for (int c = 0; c < C; ++c) gr[c] = (expf(zr[c] - mx) * inv - (c == t ? 1.f : 0.f)) * inv_count;
+      const float ic = ok ? inv_count : NAN;      // x * NaN is NaN for every x: the whole row
+      for (int c = 0; c < C; ++c) gr[c] = (expf(zr[c] - mx) * inv - (c == t ? 1.f : 0.f)) * ic;
     }
   }
   local = wave_sum(local);
@@ -138,7 +148,9 @@ __global__ void __launch_bounds__(kBlock) k_nll_fused_v4(const float* __restrict
     float mx = -INFINITY;
 #pragma unroll
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, v[c]);
-    const int t = (int)y[r];
+    const int64_t t64 = y[r];
+    const bool ok = t64 >= 0 && t64 < C;      // checked as int64, before the narrowing: out of range -> NaN row, as in k_nll_fused
+    const int t = ok ? (int)t64 : -1;
     float se = 0.f, zt = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -147,14 +159,15 @@ __global__ void __launch_bounds__(kBlock) k_nll_fused_v4(const float* __restrict
       se += v[c];
     }
     const float lse = mx + logf(se);
-    local += lse - zt;
+    local += ok ? lse - zt : NAN;
     if (gr) {
       const float inv = 1.f / se;
+      const float ic = ok ? inv_count : NAN;
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
         float o[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (v[4 * q + k] * inv - (4 * q + k == t ? 1.f : 0.f)) * inv_count;
+        for (int k = 0; k < 4; ++k) o[k] = (v[4 * q + k] * inv - (4 * q + k == t ? 1.f : 0.f)) * ic;
         gr[q] = make_float4(o[0], o[1], o[2], o[3]);
       }
     }
@@ -236,9 +249,11 @@ struct AdamTable {
 
 __global__ void __launch_bounds__(kBlock) k_adam_multi(AdamTable t, float lr, float b1, float b2, float eps, float wd, float bc1,
                                                        float bc2_sqrt, const int64_t* __restrict__ step_dev, const int32_t* __restrict__ guard) {
-  // a gradient check of this step failed (cb_rows_zero_outside_mask_f32 set the word): parameters and moments stay as they are
-  if (guard && *guard != 0) return;
+  // a gradient check of this step failed (cb_rows_zero_outside_mask_f32 set the word): parameters and moments stay as they are, and a
+  // tensor whose norm is wanted gets the partials of its UNCHANGED values (the workspace holds whatever it held before)
+  const bool skip = guard && *guard != 0;
   const int ti = blockIdx.y;
+  if (skip && !t.sq[ti]) return;
   float* __restrict__ p = t.p[ti];
   const float* __restrict__ g = t.g[ti];
   float* __restrict__ m = t.m[ti];
@@ -259,6 +274,16 @@ __global__ void __launch_bounds__(kBlock) k_adam_multi(AdamTable t, float lr, fl
   float ssq = 0.f;      // sum of squares of the updated values this thread wrote: k_sumsq's thread-to-element map and summation order
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i = q * 4;
+    if (skip) {      // (uniform over the launch) read p only, store nothing
+      if (vec_ok && i + 4 <= n) {
+        const float4 a = *reinterpret_cast<const float4*>(p + i);
+        ssq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+      } else {
+        for (int k = 0; k < 4; ++k)
+          if (i + k < n) ssq += p[i + k] * p[i + k];
+      }
+      continue;
+    }
     float pv[4], gv[4], mv[4], vv[4];
     const bool full = vec_ok && i + 4 <= n;
     if (full) {

@@ -192,7 +192,9 @@ int cb_frobenius_norm_f32(const float* x, int64_t n, float* out2, void* ws, size
 /* Fused `F.nll_loss(F.log_softmax(logits[mask], 1), y[mask])` (trainer_node_classification.py:390-391)
  * and its gradient: loss[0] = mean over the `count` rows with mask != 0 (mask NULL: all rows);
  * grad [rows, C] contiguous (NULL to skip) = (softmax - onehot) / count on masked rows, 0 elsewhere.
- * mask is one byte per row (torch.bool). */
+ * mask is one byte per row (torch.bool).  The label of a row that counts is range-checked as int64 before any use: outside [0, C) it is
+ * never an index and never narrowed — the loss is NaN and so is that row of grad (the rule of the gathering kernels: a bad index is a NaN
+ * row, not a read elsewhere).  Labels of rows with mask == 0 are not read (unlabeled nodes carry -1).  No ABI change. */
 int cb_nll_logsoftmax_f32(const float* logits, int64_t ld, const int64_t* y, const uint8_t* mask, int64_t rows, int64_t C,
                           int64_t count, float* loss, float* grad, void* ws, size_t ws_bytes, void* stream);
 
@@ -211,7 +213,8 @@ int cb_adam_multi_f32(int32_t n_tensors, float* const* p, const float* const* g,
                       const float* const* extra_decay, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                       const int64_t* step_dev, const int32_t* guard, void* stream);
 /* step_dev (may be NULL): the step count read from device memory instead of `step` (hipGraph replay).
- * guard (may be NULL): int32 in device memory; while it is non-zero the launch writes nothing (see cb_rows_zero_outside_mask_f32). */
+ * guard (may be NULL): int32 in device memory; while it is non-zero the launch leaves parameters and moments as they are (see
+ * cb_rows_zero_outside_mask_f32); a norm requested from cb_adam_multi_norm_f32 is then the norm of those unchanged values. */
 /* The same, and for every tensor with norm_out[i] != NULL also norm_out[i][0] = ||p_i||_F, [1] = ||p_i||_F^2 of the UPDATED tensor
  * (cb_frobenius_norm_f32's pair, same thread-to-element map and summation order when the tensor is the largest of its launch): the
  * next forward's `th.norm(self.le)` (GCN.py:232) costs no pass of its own over the table.  ws: cb_adam_norm_workspace_bytes(number of

@@ -253,6 +253,11 @@ def test_fused_adam_leaves_the_norm_of_what_it_wrote():
             if i != 3:                                                   # largest tensors of the launch: k_sumsq's own thread map, bit for bit
                 assert torch.equal(known, alone)
             torch.testing.assert_close(known, alone, rtol=1e-6, atol=0)
+            if i == 3:                                                   # not the largest: another thread map — held to the float64 sum of squares
+                import adam_nll_ref as ar                                # of the values it wrote, by the bound for the grid of THIS launch
+                b_n, b_sq = ar.norm_rel_bounds(p.numel(), ar.grid_for(-(-max(q.numel() for q in with_norm) // 4)))
+                sq64 = float((p.detach().double() ** 2).sum())
+                assert abs(float(known[1]) - sq64) <= b_sq * sq64 and abs(float(known[0]) - sq64 ** 0.5) <= b_n * sq64 ** 0.5
             assert torch.equal(ops.frobenius_norm(p).detach(), known[0])
     p = with_norm[0]
     with torch.no_grad():
