@@ -185,6 +185,15 @@ SIGNATURES = {
     'cb_heur_pair_scores_width_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P]),
     'cb_rank_counts_workspace_bytes': (_SZ, [_I64, _I64]),
     'cb_rank_counts_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    # samplers, epoch shuffle and ranking metrics of the link-prediction experiment (cb_lpx.hip)
+    'cb_lpx_max_tries': (ctypes.c_int, []),
+    'cb_lpx_neg_global_i32': (ctypes.c_int, [_P, _I64, ctypes.c_uint64, _P, _P, _P]),
+    'cb_lpx_neg_local_i32': (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_uint64, _P, _P]),
+    'cb_lpx_permutation_workspace_bytes': (_SZ, [_I64]),
+    'cb_lpx_permutation_i32': (ctypes.c_int, [_I64, ctypes.c_uint64, _P, _P, _SZ, _P]),
+    'cb_lpx_row_ranks_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P]),
+    'cb_lpx_recall_topk_workspace_bytes': (_SZ, [_I64, _I64]),
+    'cb_lpx_recall_topk_f32': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _SZ, _P]),
     # the link predictors and ranking losses on index pairs (cb_linkpred.hip)
     'cb_pair_gemm_nn_supported': (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64]),
     'cb_pair_gemm_nn_f32': (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, ctypes.c_int, ctypes.c_float,

@@ -18,19 +18,11 @@
 // No float atomics, no host synchronisation inside an entry, two calls with the same inputs give the same bits.
 #include "cb_common.h"
 #include "cb_pair_core.h"
-#include "cb_philox.h"
+#include "cb_draw.h"      // lp_draw2, lp_row_has: shared with cb_lpx.hip
 
 namespace cb {
 
 __device__ __forceinline__ bool lp_node_ok(const uint8_t* __restrict__ mask, int v, int mode) { return (mask[v] != 0) == (mode == 0); }
-
-// the two integers of draw `ctr` in [0, n): multiply-high of 64 random bits (a 32-bit multiply-high is biased by up to n / 2^32)
-__device__ __forceinline__ void lp_draw2(uint64_t seed, uint64_t ctr, uint64_t n, uint64_t& a, uint64_t& b) {
-  uint32_t r[4];
-  philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-  a = __umul64hi(((uint64_t)r[0] << 32) | r[1], n);
-  b = __umul64hi(((uint64_t)r[2] << 32) | r[3], n);
-}
 
 // ---- positives ------------------------------------------------------------------------------------------------------------------------
 // counts[v] = number of entries of row v whose column is valid, 0 for a row that is not valid itself.  One wavefront per row.
@@ -95,18 +87,6 @@ __global__ void __launch_bounds__(256) k_linkp_positives(const int32_t* __restri
 }
 
 // ---- negatives ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool lp_row_has(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int row, int x) {
-  int lo = rowptr[row], hi = rowptr[row + 1];
-  while (lo < hi) {
-    const int mid = (int)(((int64_t)lo + hi) >> 1);
-    const int c = col[mid];
-    if (c == x) return true;
-    if (c < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return false;
-}
-
 // One thread per slot: the tries of a slot are a chain of dependent searches, and the slots are independent.
 __global__ void __launch_bounds__(256) k_linkp_negatives(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t N,
                                                          const uint8_t* __restrict__ mask, int mode, const int32_t* __restrict__ train_nodes,

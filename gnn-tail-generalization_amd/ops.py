@@ -34,6 +34,11 @@ Link predictors and ranking losses (Link_prediction_model/layer.py:85-106, 182-1
 Encoders of the link-prediction experiment (Link_prediction_model/layer.py:19-75; model.py:290-304):
   sage_layer        act((s * (A X)) W_n^T + X W_s^T + b): one SAGEConv / GraphConv / GCNConv(normalize=False) layer with the ReLU and dropout after it; one
                     kernel per direction at 256 -> 256 (aggregation into an on-chip tile, the GEMM from there), the composed kernels elsewhere
+The link-prediction experiment's protocol (Link_prediction_model/negative_sample.py:5-57; model.py:121-266; utils.py:568-586):
+  NegativeSampler   global / local / permuted-global negatives on the device CSR (a binary search in the destination's row, counter-based tries)
+  seeded_permutation  a permutation that is a pure function of (n, seed): the epoch shuffle and the permuted copies
+  row_rank_counts   per positive, the entries of ITS row of negatives above it and equal to it; mrr_from_counts: the OGB rule on those counts
+  recall_at_topk    `cal_recall` exactly: the positives among the top k of [positives above 0 | negatives], positives first among equals
 """
 import collections
 import ctypes
@@ -2319,3 +2324,212 @@ def transformer_conv(graph, x, W_key, b_key, W_query, b_query, W_value, b_value,
     if x.shape[1] > 1 and x.stride(1) != 1:
         x = x.contiguous()
     return _TransformerConvFn.apply(graph, x, torch.cat(params[0::2]), torch.cat(params[1::2]), bool(relu))
+
+
+# ---------------------------------------------------------------------------------------------
+# the link-prediction experiment's samplers, epoch shuffle and ranking metrics: Link_prediction_model/negative_sample.py:5-57; model.py:121-266;
+# utils.py:568-586; Link_prediction_model/utils.py:61-91  (cb_lpx.hip)
+# ---------------------------------------------------------------------------------------------
+def _seed64(seed):
+    return ctypes.c_uint64((next_seed() if seed is None else int(seed)) % 2 ** 64)
+
+
+def seeded_permutation(n, seed=None, device=None):
+    """int32 [n]: the permutation of range(n) that sorts the keys (first Philox word of draw i) << 32 | i — a pure function of (n, seed), restated in
+    tests/lpx_ref.py.  The epoch shuffle of the link-prediction experiment (where the reference's DataLoader draws a host randperm) and the copies of
+    `sample_perm_copy`.  n < 2^31."""
+    n = int(n)
+    if n < 0:
+        raise ValueError('seeded_permutation: n >= 0 required')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.HipExtensionError('seeded_permutation draws on an MI355X device; there is no CPU fallback')
+    lib = _lib.load()
+    seed = _seed64(seed)
+    perm = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return perm
+    wsb = lib.cb_lpx_permutation_workspace_bytes(n)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_lpx_permutation_i32(n, seed, _lib.ptr(perm), _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_lpx_permutation_i32')
+    return perm
+
+
+def local_negatives(pos, num_nodes, num_neg, seed=None):
+    """int32 [2, P * num_neg] of `local_neg_sample(random_src=False)` (negative_sample.py:28-40): column i * num_neg + j = (pos[0, i], a uniform node of
+    [0, num_nodes)), no rejection.  pos: int32 / int64 [2, P] on the device."""
+    if not torch.is_tensor(pos):
+        raise ValueError('local_negatives: pos must be an int32 / int64 [2, P] tensor')
+    _lib.require_device(pos)
+    p32 = _pairs_arg('local_negatives: pos', pos, pos.device)
+    P, num_neg = NegativeSampler._count('local', p32.shape[1], num_neg)
+    seed = _seed64(seed)
+    out = torch.empty((2, P * num_neg), dtype=torch.int32, device=p32.device)
+    with torch.cuda.device(p32.device):
+        _lib.check(_lib.load().cb_lpx_neg_local_i32(_lib.ptr(p32), P, num_neg, int(num_nodes), seed, _lib.ptr(out), _lib.stream_ptr()),
+                   'cb_lpx_neg_local_i32')
+    return out
+
+
+def perm_copies(base, num_copies, seed):
+    """[2, n * num_copies] from base [2, n] (`sample_perm_copy`, negative_sample.py:50-57): copy 0 = base, copy j >= 1 = base permuted by
+    seeded_permutation(n, seed + j); column i * num_copies + j = copy j's column i = base column perm_j[i]."""
+    _lib.require_device(base)
+    n, k = int(base.shape[1]), int(num_copies)
+    if k < 0:
+        raise ValueError('perm_copies: num_copies >= 0 required')
+    if k == 0:
+        return base[:, :0].contiguous()
+    if k == 1:
+        return base
+    cols = [torch.arange(n, dtype=torch.int32, device=base.device)] + [seeded_permutation(n, int(seed) + j, base.device) for j in range(1, k)]
+    return base[:, torch.stack(cols, dim=1).reshape(-1).long()].contiguous()
+
+
+class NegativeSampler:
+    """The negative samplers of Link_prediction_model/negative_sample.py on the device CSR.  Every method returns int32 [2, S], S = num_samples *
+    num_neg, row 0 = source, row 1 = destination; column i * num_neg + j is negative j of positive i (the reference's [num_samples, num_neg, 2] is
+    `out.t().view(num_samples, num_neg, 2)`).  Every draw is a pure function of (seed, slot, try), restated in tests/lpx_ref.py.
+      global_       `global_neg_sample`: uniform pairs (u, v), u != v, u -> v not an edge of the graph (the directed pair only, as PyG's negative_sampling
+                    tests it after add_self_loops).  Deviation: the reference asks PyG for the count and pads a short result with repeats; here every
+                    slot tries up to 64 times, and a slot that found nothing holds -1 and counts in `failed` (check()).
+      local         `local_neg_sample(random_src=False)`: the positive's source with a uniform destination, no rejection.
+      global_perm   `global_perm_neg_sample`: copy 0 = global_(num_samples, 1, seed); copy j >= 1 = copy 0 permuted by
+                    seeded_permutation(num_samples, seed + j)."""
+
+    def __init__(self, graph):
+        from .graph import CSRGraph
+        if type(graph) is not CSRGraph or graph.n_cols != graph.N or graph.row_offset != 0:
+            raise ValueError('NegativeSampler needs a whole square graph.CSRGraph (segmented and node-sharded graphs are out of scope)')
+        _lib.require_device(graph.rowptr, graph.col)
+        self._lib = _lib.load()
+        self.graph = graph
+        self.failed = torch.zeros(1, dtype=torch.int32, device=graph.device)
+
+    @staticmethod
+    def _count(who, num_samples, num_neg):
+        num_samples, num_neg = int(num_samples), int(num_neg)
+        if num_samples < 0 or num_neg < 0:
+            raise ValueError(f'NegativeSampler.{who}: num_samples >= 0 and num_neg >= 0 required')
+        return num_samples, num_neg
+
+    def global_(self, num_samples, num_neg, seed=None):
+        num_samples, num_neg = self._count('global_', num_samples, num_neg)
+        g, S = self.graph, num_samples * num_neg
+        seed = _seed64(seed)
+        out = torch.empty((2, S), dtype=torch.int32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(self._lib.cb_lpx_neg_global_i32(ctypes.byref(_linkp_view(g)), S, seed, _lib.ptr(out), _lib.ptr(self.failed), _lib.stream_ptr()),
+                       'cb_lpx_neg_global_i32')
+        return out
+
+    def local(self, pos, num_neg, seed=None):
+        """pos: int32 / int64 [2, P] positives (row 0 = source) on the graph's device."""
+        if not torch.is_tensor(pos) or pos.device != self.graph.device:
+            _lib.require_device(pos)
+            raise ValueError('NegativeSampler.local: pos must live on the device of the graph')
+        return local_negatives(pos, self.graph.N, num_neg, seed)
+
+    def global_perm(self, num_samples, num_neg, seed=None):
+        num_samples, num_neg = self._count('global_perm', num_samples, num_neg)
+        seed = next_seed() if seed is None else int(seed)
+        return perm_copies(self.global_(num_samples, 1, seed), num_neg, seed)
+
+    def check(self):
+        """Reads the counter of failed slots (a host synchronisation: call it where the loss is read anyway), clears it, and raises RuntimeError if a
+        slot of the draws since the last check found no non-edge in its tries."""
+        n = int(self.failed.item())
+        if n:
+            self.failed.zero_()
+            raise RuntimeError(f'NegativeSampler: {n} negative slot(s) found no non-edge in {int(self._lib.cb_lpx_max_tries())} tries (their columns hold -1)')
+
+
+def row_rank_counts(pos, neg2d, return_status=False):
+    """(gt, eq) int32 [P] for pos [P] and neg2d [P, K] (rows may be strided, elements contiguous): gt[i] = #{j : neg2d[i, j] > pos[i]},
+    eq[i] = #{j : neg2d[i, j] == pos[i]}; -0.0 equals +0.0, +-inf compare as numbers.  A NaN in pos[i] or in row i gives gt[i] = eq[i] = -1 and counts
+    in the int32 [1] status (return_status); mrr_from_counts raises on it.  rank_counts() with each positive ranked among its own negatives."""
+    _lib.require_device(pos, neg2d)
+    if (not torch.is_tensor(pos) or not torch.is_tensor(neg2d) or pos.dtype != torch.float32 or neg2d.dtype != torch.float32 or pos.device != neg2d.device
+            or pos.dim() != 1 or neg2d.dim() != 2 or neg2d.shape[0] != pos.shape[0]):
+        raise ValueError('row_rank_counts expects float32 pos [P] and neg [P, K] on one device')
+    lib = _lib.load()
+    ps = _c(pos.detach())
+    ns = neg2d.detach()
+    P, K = ns.shape
+    if K > 1 and ns.stride(1) != 1 or (P > 1 and ns.stride(0) < K):
+        ns = ns.contiguous()
+    ld = ns.stride(0) if P > 1 else max(K, 1)
+    dev = ps.device
+    gt = torch.empty(P, dtype=torch.int32, device=dev)
+    eq = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_lpx_row_ranks_f32(_lib.ptr(ps) if P else None, P, _lib.ptr(ns) if P * K else None, max(ld, K), K, _lib.ptr(gt) if P else None,
+                                            _lib.ptr(eq) if P else None, _lib.ptr(status), _lib.stream_ptr()), 'cb_lpx_row_ranks_f32')
+    return (gt, eq, status) if return_status else (gt, eq)
+
+
+def mrr_from_counts(gt, eq, status=None):
+    """The OGB evaluator's rule on counts: rank = 1 + gt + eq / 2 (the mean of the optimistic and the pessimistic rank); {'MRR': mean(1 / rank) in
+    float64, 'hits@1' | 'hits@3' | 'hits@10': the share with rank <= K}.  Raises ValueError on a non-zero NaN status (given, or read off the -1 of
+    the counts)."""
+    if gt.numel() == 0:
+        raise ValueError('the MRR is a mean over the positives: at least one is required')
+    bad = int(status.item()) if status is not None else int((gt < 0).sum().item())
+    if bad:
+        raise ValueError(f'mrr_from_counts: {bad} NaN score(s) / row(s) with a NaN: a NaN has no rank')
+    rank = 1.0 + gt.to(torch.float64) + eq.to(torch.float64) / 2
+    out = {'MRR': float((1.0 / rank).mean().item())}
+    for k in (1, 3, 10):
+        out[f'hits@{k}'] = float((rank <= k).to(torch.float64).mean().item())
+    return out
+
+
+def recall_k(topk, P):
+    """The cut of `cal_recall` (utils.py:569-574): None for 'the threshold 0' (topk None or 0), int(topk) above 5, else int(float(topk) * P)."""
+    if topk is None or float(topk) == 0:
+        return None
+    return int(topk) if float(topk) > 5 else int(float(topk) * P)
+
+
+def recall_numerator(pos, neg, k):
+    """The integer numerator of `cal_recall` as an int64 [1] device tensor (-1 on a NaN) and the int32 [1] NaN status: the positives among the first
+    min(k, |M|) of M = {pos > 0} + neg by descending score, positives first among equals.  k None: all of M (= #{pos > 0})."""
+    _lib.require_device(pos, neg)
+    if not torch.is_tensor(pos) or not torch.is_tensor(neg) or pos.dtype != torch.float32 or neg.dtype != torch.float32 or pos.device != neg.device:
+        raise ValueError('recall_at_topk expects float32 scores on one device')
+    lib = _lib.load()
+    ps, ns = _c(pos.detach().reshape(-1)), _c(neg.detach().reshape(-1))
+    P, Nn, dev = ps.numel(), ns.numel(), ps.device
+    k = P + Nn if k is None else int(k)
+    if k < 0:
+        raise ValueError('recall_at_topk: the cut must not be negative')
+    result = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = lib.cb_lpx_recall_topk_workspace_bytes(P, Nn)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cb_lpx_recall_topk_f32(_lib.ptr(ps) if P else None, P, _lib.ptr(ns) if Nn else None, Nn, k, _lib.ptr(result), _lib.ptr(status),
+                                              _lib.ptr(ws), wsb, _lib.stream_ptr()), 'cb_lpx_recall_topk_f32')
+    return result, status
+
+
+def recall_at_topk(pos, neg, topk):
+    """`cal_recall` (utils.py:568-586) as a Python float: numerator / P with P counted before the `> 0` filter.  topk None or 0: mean(pos > 0);
+    float(topk) > 5: k = int(topk); otherwise k = int(float(topk) * P).  Where the reference's host sort leaves the order of equal scores to the
+    order of its concatenation (positives first, a stable sort), the device order states it: a positive before a negative among equals.  An empty M
+    (no positive above 0 and no negative) under a cut raises ValueError, as the reference's indexing of an empty array does; so does a NaN."""
+    P = int(pos.numel())
+    if P == 0:
+        raise ValueError('recall_at_topk: at least one positive is required (the recall is a share of the positives)')
+    k = recall_k(topk, P)
+    result, status = recall_numerator(pos, neg, k)
+    num = int(result.item())
+    if num < 0:
+        raise ValueError(f'recall_at_topk: {int(status.item())} NaN score(s): a NaN has no rank')
+    if k is not None and neg.numel() == 0:
+        m, _ = recall_numerator(pos, neg, None)
+        if int(m.item()) == 0:
+            raise ValueError('recall_at_topk: no positive above 0 and no negative: nothing to rank')
+    return num / P

@@ -482,3 +482,49 @@ def linkp_loss_eva(h_emb, t_emb, nh_emb, nt_emb):
 def cal_MRR(pos_score, neg_score):
     from . import ops
     return ops.cal_MRR(pos_score, neg_score)
+
+
+def split_edges(edge_index, num_nodes, target_node_mask=None, target_edge_mask=None, probs=(0.2, 0.4), seed=0):
+    """`init_split_edge_unified_impl` (utils.py:62-145) on the device: {'train' | 'valid' | 'test': {'edge': [*, 2], 'edge_neg': [*, 2]}} (int64).
+    An edge is a *target* edge where target_edge_mask says so, else where an endpoint is a target node (target_node_mask); every other edge is
+    train, and a target edge is train / valid / test with probability probs[0] / probs[1] / the rest (0.2 / 0.4 / 0.4).  Self pairs are left out.
+    Negatives: num_edges pairs of ops.NegativeSampler.global_ (one each) on the graph of edge_index; negative j is classed by the rule of positive j
+    with a draw of its own.  The draws come from a torch generator on the device under `seed`.
+    Deviations from the reference: (1) both orientations of an unordered pair share one draw, so u -> v and v -> u land in the same part (the
+    reference draws per directed edge, which puts the reverse of a held-out edge into the training set); (2) the reference's second loop appends
+    the POSITIVE edge to its negative lists — a defect; the sampled negatives are what is returned here; (3) the reference drops a draw that
+    equals probs[0] + probs[1] exactly; here it is test."""
+    from . import ops
+    from .graph import CSRGraph
+    ei = edge_index.to(torch.int64)
+    dev, N, E = ei.device, int(num_nodes), int(ei.shape[1])
+    if target_edge_mask is not None:
+        target = torch.as_tensor(target_edge_mask, device=dev).to(torch.bool).reshape(-1)
+        if target.numel() != E:
+            raise ValueError(f'split_edges: target_edge_mask has {target.numel()} entries for {E} edges')
+    elif target_node_mask is not None:
+        node = torch.as_tensor(target_node_mask, device=dev).to(torch.bool).reshape(-1)
+        if node.numel() != N:
+            raise ValueError(f'split_edges: target_node_mask has {node.numel()} entries for {N} nodes')
+        target = node[ei[0]] | node[ei[1]]
+    else:
+        raise ValueError('split_edges needs target_node_mask or target_edge_mask')
+    p_train, p_valid = float(probs[0]), float(probs[1])
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    lo, hi = torch.minimum(ei[0], ei[1]), torch.maximum(ei[0], ei[1])
+    _, pair_of = torch.unique(lo * N + hi, return_inverse=True)
+    n_pairs = int(pair_of.max().item()) + 1 if E else 0
+    draw_p = torch.rand(n_pairs, generator=gen, device=dev, dtype=torch.float64)[pair_of]
+    draw_n = torch.rand(E, generator=gen, device=dev, dtype=torch.float64)
+
+    def parts(draw):
+        train = ~target | (draw < p_train)
+        valid = ~train & (draw < p_train + p_valid)
+        return {'train': train, 'valid': valid, 'test': ~train & ~valid}
+    sampler = ops.NegativeSampler(CSRGraph(ei, N))
+    neg = sampler.global_(E, 1, seed=int(seed)).t().to(torch.int64)
+    sampler.check()
+    not_self = ei[0] != ei[1]
+    pos_part, neg_part = parts(draw_p), parts(draw_n)
+    pos = ei.t()
+    return {s: {'edge': pos[pos_part[s] & not_self].contiguous(), 'edge_neg': neg[neg_part[s]].contiguous()} for s in ('train', 'valid', 'test')}

@@ -876,6 +876,45 @@ int cb_rank_counts_f32(const float* pos, int64_t P, const float* neg, int64_t Nn
                        size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------
+ * The link-prediction experiment's samplers, epoch shuffle and ranking metrics (Link_prediction_model/negative_sample.py:5-57; model.py:121-266;
+ * utils.py:568-586 `cal_recall`; Link_prediction_model/utils.py:61-91); cb_lpx.hip.  Draws are those of the samplers above: Philox4x32-10 under the
+ * 64-bit seed, draw number d -> words r0..r3, the integers hi64((r0 << 32 | r1) * n) and hi64((r2 << 32 | r3) * n) of [0, n).
+ * No float atomics; no host synchronisation; two calls with the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+#define CB_LPX_MAX_TRIES 64
+int cb_lpx_max_tries(void);
+
+/* `global_neg_sample` (negative_sample.py:5-19).  g: the by-dst view (rowptr / col / n_rows / n_edges read; square, col_flags == 0, N >= 2).
+ * out int32 [2, S].  Slot s, try t: (u, v) = the two integers of draw s * CB_LPX_MAX_TRIES + t in [0, N); accepted iff u != v and u is not a
+ * column of row v (binary search; only the directed pair u -> v is tested, as `negative_sampling` does after `add_self_loops`).  The first accepted
+ * try goes to out[0, s], out[1, s]; a slot without one holds -1 in both cells and adds 1 to *n_failed (int32, integer atomic; the caller zeroes
+ * and reads it). */
+int cb_lpx_neg_global_i32(const cb_csr_view* g, int64_t S, uint64_t seed, int32_t* out, int32_t* n_failed, void* stream);
+
+/* `local_neg_sample`, random_src=False (negative_sample.py:28-40).  pos_src int32 [P]: the sources of the positives; out int32 [2, P k]:
+ * out[0, s] = pos_src[s / k] as it stands, out[1, s] = the first integer of draw s * CB_LPX_MAX_TRIES in [0, N).  No rejection.  N >= 2. */
+int cb_lpx_neg_local_i32(const int32_t* pos_src, int64_t P, int64_t k, int64_t N, uint64_t seed, int32_t* out, void* stream);
+
+/* perm int32 [n]: perm[j] = the low 32 bits of the j-th smallest key (r0(draw i) << 32) | i, i in [0, n), sorted over all 64 bits (cb_sort.hip).
+ * The keys are distinct: a pure function of (n, seed).  n < 2^31; n == 0 launches nothing. */
+size_t cb_lpx_permutation_workspace_bytes(int64_t n);
+int cb_lpx_permutation_i32(int64_t n, uint64_t seed, int32_t* perm, void* workspace, size_t workspace_bytes, void* stream);
+
+/* cb_rank_counts_f32's contract per row: pos [P], neg [P, K] with row stride ld >= K (elements); gt[i] = #{j : neg[i, j] > pos[i]},
+ * eq[i] = #{j : neg[i, j] == pos[i]}, int32.  -0.0 == +0.0, the infinities compare as numbers.  A NaN in pos[i] or in row i gives
+ * gt[i] = eq[i] = -1; status [1] (zeroed by the call) counts the NaNs (integer atomic, on that path only).  16 lanes per row for K <= 64, one
+ * wavefront per row above; float4 loads from the row's first 16-byte boundary, scalar head and tail. */
+int cb_lpx_row_ranks_f32(const float* pos, int64_t P, const float* neg, int64_t ld, int64_t K, int32_t* gt, int32_t* eq, int32_t* status,
+                         void* stream);
+
+/* The integer numerator of `cal_recall` (utils.py:576-585).  M = the positives with score > 0 and all Nn negatives, ordered by descending score,
+ * a positive before a negative among equal scores, -0.0 taken as +0.0; result [1] int64 = the number of positives among the first min(k, |M|).
+ * P + Nn < 2^32.  status [1] (zeroed by the call) counts the NaNs of pos and neg; the result is then -1. */
+size_t cb_lpx_recall_topk_workspace_bytes(int64_t P, int64_t Nn);
+int cb_lpx_recall_topk_f32(const float* pos, int64_t P, const float* neg, int64_t Nn, int64_t k, int64_t* result, int32_t* status,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------
  * The decoder of the link-prediction experiment on index pairs (Link_prediction_model/layer.py:85-106 `MLPPredictor`, :182-191 `DotPredictor`;
  * loss.py:4-30; model.py:108-119, 152-158); cb_linkpred.hip.  h [N, K] fp32 (ld >= K): the encoder's embeddings; pairs int32 [2, S]: row 0 = u,
  * row 1 = v.  Where the reference gathers h[u] and h[v] into two [S, K] matrices and multiplies them, these entries read the rows in place.
