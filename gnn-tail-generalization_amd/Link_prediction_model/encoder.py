@@ -13,7 +13,10 @@ next to the refusing `layer.SAGE` / `GCN` / `WSAGE` / `MLP` (which keep raising:
                    subtracted); heads > 1, edge_dim and beta are not built.
 
 ReLU then dropout after every layer but the last (layer.py:29-35).  forward(x, graph) takes a graph.CSRGraph where the reference takes PyG's adj_t; every
-SAGE / WSAGE / GCN layer is one ops.sage_layer call (csrc/cb_sage.hip where the widths are 256 -> 256, the composed kernels elsewhere).
+SAGE / WSAGE / GCN layer is one ops.sage_layer call (csrc/cb_sage.hip where the widths are 256 -> 256, the composed kernels elsewhere).  `graph` may also
+be a graph.WeightedAdj — an adj_t with values (real edge weights, gcn_normalization / adj_normalization of Link_prediction_model/utils.py): GraphConv and
+GCNConv then multiply each gathered row by its edge's value, agg[v] = sum_e w_e x[u_e] (csrc/cb_ewlayer.hip); SAGEConv, TransformerConv and the MLP read
+the structure alone and give the same bits with or without values.
 
 Constructor arguments, parameter names and shapes ([out, in]) are PyG's, created layer by layer in PyG's order.  Initial values: every weight and bias
 is drawn by torch.nn.Linear's reset_parameters (kaiming_uniform with a = sqrt(5); GCN's bias likewise from its Linear).  torch_geometric is not
@@ -22,6 +25,12 @@ some of these)."""
 import torch
 
 from .. import _lib, gemm, ops
+
+
+def structure(graph):
+    """The CSRGraph of what an encoder was handed: a graph.WeightedAdj's .graph, anything else as it is.  The layers that do not read edge values
+    (SAGEConv: PyG drops them; TransformerConv: the reference strips them, trainer_link_prediction.py:340-342) see the structure alone."""
+    return getattr(graph, 'graph', graph)
 
 
 class _Conv(torch.nn.Module):
@@ -53,6 +62,9 @@ class _Conv(torch.nn.Module):
 
 class SAGEConv(_Conv):
     mode, names = 'SAGE', ('lin_l', 'lin_r')
+
+    def forward(self, x, graph, relu=False, p=0.0):
+        return super().forward(x, structure(graph), relu=relu, p=p)
 
 
 class GraphConv(_Conv):
@@ -97,7 +109,7 @@ class TransformerConv(torch.nn.Module):
             lin.reset_parameters()
 
     def forward(self, x, graph, relu=False, p=0.0):
-        y = ops.transformer_conv(graph, x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias, self.lin_value.weight,
+        y = ops.transformer_conv(structure(graph), x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias, self.lin_value.weight,
                                  self.lin_value.bias, self.lin_skip.weight, self.lin_skip.bias, relu=relu)
         return ops.dropout(y, p, training=True) if p else y
 
@@ -132,7 +144,7 @@ class SAGEEncoder(_Encoder):
 
 
 class WSAGEEncoder(_Encoder):
-    """layer.py:69-75 `WSAGE` (no edge weights)."""
+    """layer.py:69-75 `WSAGE` (edge values where the graph is a WeightedAdj)."""
     conv = GraphConv
 
 

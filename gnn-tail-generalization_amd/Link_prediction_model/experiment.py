@@ -9,18 +9,21 @@ train()   model.py:121-169.  One draw of negatives for ALL train positives per e
           clip_grad_norm_ calls, a step.  Returns sum(loss_b n_b) / sum(n_b), accumulated on the device in float64 and read ONCE per epoch; the
           sampler's, the pair operators' and the device status words are read there too, never per batch.
 test()    model.py:187-266.  Eval-mode embeddings once; train negatives always 'global'; six batch_predict calls; 'hits' | 'mrr' | 'recall_my@...'.
-The message graph is a graph.CSRGraph of data.edge_index as given: edge weights and the gcn / adj normalisations of the reference's GCN / WSAGE
-runs are not applied.  edge_LP.py (`--edge_lp_mode`) is not built."""
+The message graph is a graph.CSRGraph of data.edge_index.  data.edge_weight (a float tensor, one value per column of edge_index) makes it an adjacency
+with values (graph.WeightedAdj), which the GCN / WSAGE layers multiply by and SAGE / Transformer / MLP ignore.  args.normalize_adj (default 0) applies
+the reference's gcn_normalization for GCN and adj_normalization for WSAGE (trainer_link_prediction.py:333-338) once, in the constructor; the
+reference normalises unconditionally — here it is a switch, so that the default stays the adjacency as given.  The samplers and the CN / AA scores
+read the structure.  split_edge['train']['weight'] (the per-edge margins) stays refused.  edge_LP.py (`--edge_lp_mode`) is not built."""
 import types
 
 import torch
 
 from .. import _lib, ops
 from .. import optim as cb_optim
-from ..graph import CSRGraph, build_graph
+from ..graph import INT32_EDGE_LIMIT, CSRGraph, WeightedAdj, build_graph
 from . import negative_sample
 from .model import calculate_loss, create_encoder_layer, create_input_feat, create_input_layer, reset_input_layer
-from .utils import evaluate_hits, evaluate_mrr, evaluate_recall_my, get_pos_neg_edges
+from .utils import adj_normalization, evaluate_hits, evaluate_mrr, evaluate_recall_my, gcn_normalization, get_pos_neg_edges
 
 HEURISTICS = ('CN', 'AA', 'PPR')
 
@@ -32,6 +35,35 @@ def refuse_edge_lp(args):
             f"--edge_lp_mode={mode} is not built: the reference's edge_LP.py builds its edge graph from positions inside a node's edge set, not from edge "
             'ids (mutual_intermix), and its size does not match the score vector it propagates, so there is no defined result to reproduce; '
             "pass --edge_lp_mode=''")
+
+
+def message_adjacency(args, data, num_nodes, device):
+    """(graph, adj): the CSRGraph of data.edge_index (samplers, heuristics) and what the encoder is handed in place of the reference's data.adj_t — the
+    graph itself, or a graph.WeightedAdj: data.edge_weight as given, or, under args.normalize_adj, gcn_normalization of it for `GCN` and
+    adj_normalization for `WSAGE` (trainer_link_prediction.py:333-338; unit values where the data carries none), applied once, here."""
+    encoder_name = str(args.encoder)
+    if getattr(data, 'edge_attr', None) is not None:
+        raise NotImplementedError('data.edge_attr: edge features are not built for the link-prediction experiment (one real value per edge: data.edge_weight)')
+    edge_weight = getattr(data, 'edge_weight', None)
+    if edge_weight is not None and encoder_name in HEURISTICS:
+        raise NotImplementedError('data.edge_weight: the CN / AA / PPR scores count neighbours and read no edge values')
+    normalize = int(getattr(args, 'normalize_adj', 0) or 0) and encoder_name.upper() in ('GCN', 'WSAGE')
+    valued = edge_weight is not None or normalize
+    if valued and int(data.edge_index.shape[1]) < INT32_EDGE_LIMIT:      # (edge values are looked up through the kept edge order)
+        graph = CSRGraph(data.edge_index, num_nodes, keep_edge_order=True)
+    else:
+        graph = build_graph(data.edge_index, num_nodes)
+    if not isinstance(graph, CSRGraph):
+        raise NotImplementedError('the experiment needs the whole int32-indexed graph on this device; segmented and node-sharded graphs are not built for it')
+    if not valued:
+        return graph, graph
+    if edge_weight is not None and (not torch.is_tensor(edge_weight) or not edge_weight.is_floating_point() or edge_weight.numel() != graph.E):
+        raise ValueError(f'data.edge_weight: a float tensor of {graph.E} elements (one per column of edge_index) expected')
+    w = edge_weight.to(device) if edge_weight is not None else torch.ones(graph.E, dtype=torch.float32, device=device)
+    adj = WeightedAdj(graph, w)
+    if normalize:
+        adj = (gcn_normalization if encoder_name.upper() == 'GCN' else adj_normalization)(adj)
+    return graph, adj
 
 
 class LinkPredictionModel(object):
@@ -47,12 +79,7 @@ class LinkPredictionModel(object):
             raise NotImplementedError(f'--optimizer {a.optimizer} is not built on the HIP path: optim.py has the fused Adam only')
         if getattr(a, 'linkpred_baseline', '') in ('EGI', 'DGI'):
             raise NotImplementedError(f'--linkpred_baseline {a.linkpred_baseline} is not built')
-        for name in ('edge_weight', 'edge_attr'):
-            if getattr(data, name, None) is not None:
-                raise NotImplementedError(f'data.{name}: real-valued edge weights are not built for the link-prediction experiment')
-        self.graph = build_graph(data.edge_index, self.num_nodes)
-        if not isinstance(self.graph, CSRGraph):
-            raise NotImplementedError('the experiment needs the whole int32-indexed graph on this device; segmented and node-sharded graphs are not built for it')
+        self.graph, self.adj = message_adjacency(a, data, self.num_nodes, self.device)
         self.sampler = negative_sample.sampler_of(self.graph)
         self.emb = self.encoder = self.predictor = self.optimizer = None
         self.para_list = []
@@ -93,7 +120,7 @@ class LinkPredictionModel(object):
         return create_input_feat(self.emb, data.x, self.use_node_feats)
 
     def embeddings(self, data):
-        return self.encoder(self.create_input_feat(data), self.graph)
+        return self.encoder(self.create_input_feat(data), self.adj)
 
     def train(self, data, split_edge, batch_size, neg_sampler_name, num_neg):
         if self.encoder_name in HEURISTICS:

@@ -1,8 +1,8 @@
 """The reference's Link_prediction_model/utils.py:7-91 — `get_pos_neg_edges` and the three `evaluate_*` — over the device samplers and the tie-safe
 counts of csrc/cb_heur.hip / cb_lpx.hip.  Result keys are the reference's ('Hits@20' | 'Hits@50' | 'Hits@100', 'MRR', 'recall@100%').  Where the
 reference takes an OGB `evaluator`, the argument is kept (None) and ignored: Hits@K is ops.hits_at_k (the OGB rule on counts), the MRR is the current
-OGB evaluator's rule rank = 1 + #above + #equal / 2 (ops.mrr_from_counts).  `gcn_normalization` / `adj_normalization` / `generate_neg_dist_table` are
-not built: the GCN / WSAGE encoders run on the adjacency as given."""
+OGB evaluator's rule rank = 1 + #above + #equal / 2 (ops.mrr_from_counts).  `gcn_normalization` / `adj_normalization` (utils.py:93-106) take and return
+a graph.WeightedAdj where the reference takes a torch_sparse adj_t (ops.adj_normalize, csrc/cb_adjnorm.hip).  `generate_neg_dist_table` is not built."""
 import torch
 
 from .. import ops
@@ -35,6 +35,16 @@ def get_pos_neg_edges(split, split_edge, graph=None, num_nodes=None, neg_sampler
         target_neg = split_edge[split]['target_node_neg']
         neg_edge = torch.stack([source.repeat_interleave(target_neg.size(1)), target_neg.reshape(-1)]).t()
     return pos_edge, neg_edge
+
+
+def gcn_normalization(adj_t):
+    """utils.py:93-99: D^-1/2 (A with its diagonal set to 1) D^-1/2 of a graph.WeightedAdj, as a new one (ops.adj_normalize 'gcn')."""
+    return ops.adj_normalize(adj_t, 'gcn')
+
+
+def adj_normalization(adj_t):
+    """utils.py:101-106: D^-1 A of a graph.WeightedAdj, as a new one (ops.adj_normalize 'adj')."""
+    return ops.adj_normalize(adj_t, 'adj')
 
 
 def _f32(t):

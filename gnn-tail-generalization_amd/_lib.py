@@ -220,6 +220,11 @@ SIGNATURES = {
     'cb_sage_layer_supported': (ctypes.c_int, [_I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64]),
     'cb_sage_layer_f32': (ctypes.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I64, _I32,
                                          _P, _I64, _P]),
+    # the adjacency with values (cb_spmm.hip, cb_ewlayer.hip, cb_adjnorm.hip): views as plain pointers like cb_sage_layer_f32's; tests/test_ew_host.py
+    'cb_spmm_csr_ew_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P]),
+    'cb_ewlayer_f32': (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _P, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, _P, _I64, _P, _I64, _I32, _P, _I64, _P]),
+    'cb_adjnorm_rowsum_f64': (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _P]),
+    'cb_adjnorm_scale_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     # attention over CSR rows (cb_attn.hip): the view as a plain pointer like cb_sage_layer_f32's; its checks are exercised by tests/test_attn_host.py
     'cb_attn_supported': (ctypes.c_int, [_I64, _P, _I64]),
     'cb_attn_workspace_bytes': (_SZ, [_I64, _I64]),

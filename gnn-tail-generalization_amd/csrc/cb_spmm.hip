@@ -126,6 +126,34 @@ extern "C" int cb_spmm_csr_f32(const cb_csr_view* g, const void* h, int32_t h_bf
   return launch_spmm<1, false, bf16_t>(v, hb, ld_h, d, ep, out, ld_out, st);
 }
 
+// out[v] = sum_j w_csr[j] * h[col[j]] over fp32 rows with d % 256 == 0: the adjacency with one value per stored edge (w_csr in the order of the view's
+// col array), on the kernels of cb_spmm_csr_f32 — the same walk, hub plan and gather policy; acc += w * x edge by edge, a hub row's chunk partials summed
+// in chunk order.  No scale / bias / ReLU: the layers that take values (GraphConv, GCNConv(normalize=False)) have none before their GEMM.
+extern "C" int cb_spmm_csr_ew_f32(const cb_csr_view* g, const float* w_csr, const float* h, int64_t ld_h, int64_t d, float* out, int64_t ld_out,
+                                  void* stream) {
+  const char* who = "cb_spmm_csr_ew_f32";
+  cb_csr_view v;
+  const int rc = check_csr_view(who, g, d, v);
+  if (rc != CB_OK || v.n_rows == 0 || d == 0) return rc;
+  CB_CHECK_ARG(h && out && (v.n_edges == 0 || w_csr), CB_E_INVALID, "%s: null pointer", who);
+  CB_CHECK_ARG(ld_h >= d && ld_out >= d, CB_E_INVALID, "%s: leading dimension smaller than d", who);
+  CB_CHECK_ARG(d % 256 == 0 && aligned16(h) && aligned16(out) && ld_h % 4 == 0 && ld_out % 4 == 0, CB_E_INVALID,
+               "%s: 16-byte aligned fp32 rows with d %% 256 == 0 required (other widths: cb_spmm_csr_weighted_f32)", who);
+  Epilogue ep{};
+  ep.col_flags = v.col_flags;
+  ep.edge_w = w_csr;
+  hipStream_t st = (hipStream_t)stream;
+  constexpr int RPW = 16, wpb = 4;      // (launch_spmm's shape)
+  const int64_t n_waves = (v.n_rows + RPW - 1) / RPW;
+  const dim3 grid((unsigned)((n_waves + wpb - 1) / wpb), (unsigned)(d / 256));
+  dispatch_gp_cs<true, false>(v.col_flags ? 2 : 0, false, [&](auto GP, auto) {
+    hipLaunchKernelGGL((k_spmm_rows<4, RPW, 8, true, false, float, false, decltype(GP)::value, false, false, true>), grid, dim3(kWave * wpb), 0, st, v.rowptr,
+                       v.col, h, ld_h, out, ld_out, (int)v.n_rows, (int)d, ep, v.hub_threshold, FusedEpi{});
+  });
+  CB_LAUNCH_CHECK();
+  return launch_hub_rows<4, float, false, false, true>(v, h, ld_h, d, out, ld_out, ep, FusedEpi{}, st);
+}
+
 // One propagation step with its elementwise passes folded into the store (Label_propagation_model/outcome_correlation.py:128-145):
 //     out[v, :] = post_scale[v] * fix_v(clamp(row_scale[v] * sum_{u in row v} h[u, :] + c_mix * mix[v, :], lo, hi))
 // Narrow rows (d = number of classes): one lane per column (the VEC = 1 instantiation of k_spmm_rows + hub kernels).

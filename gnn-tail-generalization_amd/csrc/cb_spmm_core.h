@@ -1,5 +1,6 @@
 // The core of the CSR sum-aggregation (design notes: cb_spmm.hip), shared by cb_spmm.hip (the aggregation entry points), cb_agg_gemm.hip (aggregation +
-// next dense transform in one kernel), cb_sage.hip (the encoder layer) and, for the row block's head, cb_spmm_small.hip.
+// next dense transform in one kernel), cb_sage_core.h (the encoder layer: cb_sage.hip, cb_ewlayer.hip) and, for the row block's head, cb_spmm_small.hip.
+// EW (stream_rows, k_spmm_rows, k_spmm_hub_chunks, launch_hub_rows; default off): one factor per stored EDGE, Epilogue::edge_w — the adjacency with values.
 //   device: vector helpers and the epilogues; RowBlock + load_row_block (the head of a wavefront's row block), tile_row_cut / zero_tile_rows (a 64-row
 //           tile among the gathering wavefronts), stream_rows (the edge-stream walk), the row / hub kernels;
 //   host:   check_csr_view, partial_ld, dispatch_bool / dispatch_gp_cs (run-time flags as compile-time constants) and launch_hub_rows.
@@ -141,6 +142,9 @@ struct Epilogue {
   int lp_clamp;
   float lp_lo, lp_hi;
   const uint8_t* lp_fix;
+  // EW kernels (d % 256 == 0, fp32 rows, plain store): out[v] = row_scale[v] * sum_j edge_w[j] * h[col[j]] — one factor per stored EDGE, in the order of
+  // this CSR's col array (an adjacency with values: cb_spmm_csr_ew_f32, cb_ewlayer_f32); read by the lane that reads col[j], at the same absolute index
+  const float* edge_w;      // [n_edges] or null
 };
 
 template <int VEC>
@@ -343,7 +347,7 @@ __device__ __forceinline__ void gather_pol(float (&v)[VEC], const HT* __restrict
 // P65 (64-row blocks, cb_agg_gemm.hip): lane i holds rowptr[r0 + i] for i < 64 and ptr_hi = rowptr[r0 + 64].
 // TILE_ONLY (cb_sage.hip, TLD > 0): the finished row goes to the LDS tile alone — nothing is written through out_lane (may be null).
 template <int VEC, int U, bool FULL, bool FUSED, bool ACC, typename HT, int GP = 0, int TLD = 0, bool P65 = false, bool CS = false, bool MIXB = false,
-          bool TILE_ONLY = false>
+          bool TILE_ONLY = false, bool EW = false>
 __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr_v, float my_scale, int r0, const int* __restrict__ col,
                                             const HT* __restrict__ h_lane, int64_t ld_h, float* __restrict__ out_lane,
                                             int64_t ld_out, bool active_in, int relu, const float (&bvec)[VEC], const FusedEpi& fe,
@@ -356,6 +360,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
   static_assert(TLD == 0 || (VEC == 4 && FULL), "on-chip row tile: d == 256, float4 lanes");
   static_assert(!TILE_ONLY || (TLD > 0 && !FUSED && !ACC), "tile-only rows: the plain aggregation into an on-chip tile");
   static_assert(!CS || (!FUSED && !ACC && sizeof(HT) == 4), "source-row factor: plain fp32 aggregation only");
+  static_assert(!EW || (!CS && !FUSED && !ACC && sizeof(HT) == 4), "per-edge factor: plain fp32 aggregation only, no source-row factor beside it");
   struct PtrAt {      // rowptr of local row i (wave-uniform i)
     int v, hi;
     __device__ __forceinline__ int operator()(int i) const {
@@ -471,8 +476,12 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
   // P65 kernels run ONE wavefront per SIMD (cb_agg_gemm.hip): no neighbour hides a dependent load, so the next window's column ids are
   // requested before this window's gathers and the remainder of a window goes out as one predicated batch instead of one load at a time
   int col_next = 0;
+  float ew_next = 0.f;                         // EW: the factors of the next window's edges, requested with their column ids
   if constexpr (P65) {
-    if (e_begin + lane < e_end) col_next = __builtin_nontemporal_load(col + e_begin + lane);
+    if (e_begin + lane < e_end) {
+      col_next = __builtin_nontemporal_load(col + e_begin + lane);
+      if constexpr (EW) ew_next = __builtin_nontemporal_load(ep.edge_w + e_begin + lane);
+    }
   }
   for (int base = e_begin; base < e_end; base += kWave) {
     const int cnt = min(kWave, e_end - base);
@@ -483,9 +492,17 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
     } else {
       if (lane < cnt) my_col = __builtin_nontemporal_load(col + base + lane);
     }
-    float my_cs = 0.f;                         // CS: lane i holds the factor of the window's i-th source row
+    float my_cs = 0.f;                         // CS: lane i holds the factor of the window's i-th source row; EW: of the window's i-th edge
     if constexpr (CS) {
       if (lane < cnt) my_cs = ep.col_scale[my_col & kColMask];
+    }
+    if constexpr (EW) {
+      if constexpr (P65) {
+        my_cs = ew_next;
+        if (base + kWave + lane < e_end) ew_next = __builtin_nontemporal_load(ep.edge_w + base + kWave + lane);
+      } else {
+        if (lane < cnt) my_cs = __builtin_nontemporal_load(ep.edge_w + base + lane);
+      }
     }
     int k = 0;
     for (; k + U <= cnt; k += U) {
@@ -500,7 +517,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
       for (int u = 0; u < U; ++u) {
         const int e = base + k + u;
         while (e == cur_end) flush();
-        if constexpr (CS) {
+        if constexpr (CS || EW) {
           const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k + u));
 #pragma unroll
           for (int i = 0; i < VEC; ++i) acc[i] += cs * v[u][i];
@@ -523,7 +540,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
           if (u < nb) {
             const int e = base + k + u;
             while (e == cur_end) flush();
-            if constexpr (CS) {
+            if constexpr (CS || EW) {
               const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k + u));
 #pragma unroll
               for (int i = 0; i < VEC; ++i) acc[i] += cs * v[u][i];
@@ -543,7 +560,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
       else zero<VEC>(v);
       const int e = base + k;
       while (e == cur_end) flush();
-      if constexpr (CS) {
+      if constexpr (CS || EW) {
         const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k));
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[i] += cs * v[i];
@@ -570,7 +587,8 @@ __device__ __forceinline__ void block_colsum_store(const float (&cs)[4], float* 
   }
 }
 
-template <int VEC, int RPW, int U, bool FULL, bool FUSED, typename HT, bool ACC = false, int GP = 0, bool CS = false, bool MIXB = false>
+template <int VEC, int RPW, int U, bool FULL, bool FUSED, typename HT, bool ACC = false, int GP = 0, bool CS = false, bool MIXB = false,
+          bool EW = false>
 __global__ void __launch_bounds__(256) k_spmm_rows(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                    const HT* __restrict__ h, int64_t ld_h, float* __restrict__ out,
                                                    int64_t ld_out, int n_rows, int d, Epilogue ep, int hub_T, FusedEpi fe) {
@@ -618,7 +636,7 @@ __global__ void __launch_bounds__(256) k_spmm_rows(const int* __restrict__ rowpt
   const float* init_lane = ACC ? ep.acc_init + c0 : nullptr;
 
   if (hubmask == 0) {
-    stream_rows<VEC, U, FULL, FUSED, ACC, HT, GP, 0, false, CS, MIXB>(0, nr, nr, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, active, ep.relu, bvec, fe, c0,
+    stream_rows<VEC, U, FULL, FUSED, ACC, HT, GP, 0, false, CS, MIXB, false, EW>(0, nr, nr, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, active, ep.relu, bvec, fe, c0,
                                                     init_lane, ep.ld_init, ep, nullptr, 0, my_gid, my_xp0, my_xp1, cs_acc);
   } else {
     int r = 0;
@@ -626,7 +644,7 @@ __global__ void __launch_bounds__(256) k_spmm_rows(const int* __restrict__ rowpt
       unsigned long long m = hubmask >> r;
       int nh = m ? r + (__ffsll((long long)m) - 1) : nr;
       if (nh > r)
-        stream_rows<VEC, U, FULL, FUSED, ACC, HT, GP, 0, false, CS, MIXB>(r, nh, nr, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, active, ep.relu, bvec, fe,
+        stream_rows<VEC, U, FULL, FUSED, ACC, HT, GP, 0, false, CS, MIXB, false, EW>(r, nh, nr, my_ptr, my_scale, r0, col, h_lane, ld_h, out_lane, ld_out, active, ep.relu, bvec, fe,
                                                         c0, init_lane, ep.ld_init, ep, nullptr, 0, my_gid, my_xp0, my_xp1, cs_acc);
       r = nh + 1;
     }
@@ -637,12 +655,13 @@ __global__ void __launch_bounds__(256) k_spmm_rows(const int* __restrict__ rowpt
 }
 
 // One wavefront per chunk of T edges of a hub row -> one partial row in `partial`.
-template <int VEC, int U, typename HT, int GP = 0, bool CS = false>
+template <int VEC, int U, typename HT, int GP = 0, bool CS = false, bool EW = false>
 __global__ void __launch_bounds__(256) k_spmm_hub_chunks(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                          const HT* __restrict__ h, int64_t ld_h, int d, int hub_T,
                                                          int n_hubs, int n_chunks, const int* __restrict__ hub_rows,
                                                          const int* __restrict__ hub_chunk_ptr, float* __restrict__ partial,
                                                          int64_t ld_p, Epilogue ep) {
+  static_assert(!EW || (!CS && sizeof(HT) == 4), "per-edge factor: fp32 rows, no source-row factor beside it");
   const int lane = lane_id();
   const int chunk = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   if (chunk >= n_chunks) return;
@@ -669,6 +688,9 @@ __global__ void __launch_bounds__(256) k_spmm_hub_chunks(const int* __restrict__
     if constexpr (CS) {
       if (lane < cnt) my_cs = ep.col_scale[my_col & kColMask];
     }
+    if constexpr (EW) {      // (base is an absolute edge index, rowptr[row] + j * hub_T + a multiple of 64: the index col is read at)
+      if (lane < cnt) my_cs = __builtin_nontemporal_load(ep.edge_w + base + lane);
+    }
     int k = 0;
     for (; k + U <= cnt; k += U) {
       float v[U][VEC];
@@ -680,7 +702,7 @@ __global__ void __launch_bounds__(256) k_spmm_hub_chunks(const int* __restrict__
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        if constexpr (CS) {
+        if constexpr (CS || EW) {
           const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k + u));
 #pragma unroll
           for (int i = 0; i < VEC; ++i) acc[i] += cs * v[u][i];
@@ -695,7 +717,7 @@ __global__ void __launch_bounds__(256) k_spmm_hub_chunks(const int* __restrict__
       float v[VEC];
       if (active) gather_pol<VEC, HT, GP>(v, h_lane, ld_h, c);
       else zero<VEC>(v);
-      if constexpr (CS) {
+      if constexpr (CS || EW) {
         const float cs = __int_as_float(bcast_lane(__float_as_int(my_cs), k));
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[i] += cs * v[i];
@@ -841,8 +863,8 @@ static inline void dispatch_gp_cs(int gp, bool cs, F&& f) {
 
 // The hub rows of a view: one wavefront per chunk of hub_threshold edges -> a partial row in the view's workspace, then one wavefront per hub row sums
 // its partials in chunk order and applies the epilogue (k_spmm_hub_chunks, k_spmm_hub_finish).  ep.col_flags chooses the gather policy (float4 lanes);
-// ep.col_scale the source-row factor (float4 lanes, fp32 rows, plain epilogue: a fused epilogue never takes one).
-template <int VEC, typename HT, bool FUSED, bool MIXB = false>
+// ep.col_scale the source-row factor (float4 lanes, fp32 rows, plain epilogue: a fused epilogue never takes one).  EW: ep.edge_w, the per-edge factor.
+template <int VEC, typename HT, bool FUSED, bool MIXB = false, bool EW = false>
 static int launch_hub_rows(const cb_csr_view& g, const HT* h, int64_t ld_h, int64_t d, float* out, int64_t ld_out, const Epilogue& ep, const FusedEpi& fe,
                            hipStream_t st) {
   if (g.n_hubs <= 0) return CB_OK;
@@ -850,8 +872,9 @@ static int launch_hub_rows(const cb_csr_view& g, const HT* h, int64_t ld_h, int6
   const int64_t ld_p = partial_ld(d);
   float* partial = (float*)g.ws;
   const dim3 blk(kWave * wpb), gridc((unsigned)((g.n_chunks + wpb - 1) / wpb), ny), gridf((unsigned)((g.n_hubs + wpb - 1) / wpb), ny);
-  dispatch_gp_cs<VEC == 4, VEC == 4 && !FUSED && sizeof(HT) == 4>(ep.col_flags ? 2 : 0, ep.col_scale != nullptr, [&](auto GP, auto CS) {
-    hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, decltype(GP)::value, decltype(CS)::value>), gridc, blk, 0, st, g.rowptr, g.col, h, ld_h, (int)d,
+  static_assert(!EW || (VEC == 4 && !FUSED && sizeof(HT) == 4), "per-edge factor: the d % 256 == 0 fp32 kernels with the plain epilogue");
+  dispatch_gp_cs<VEC == 4, VEC == 4 && !FUSED && !EW && sizeof(HT) == 4>(ep.col_flags ? 2 : 0, !EW && ep.col_scale != nullptr, [&](auto GP, auto CS) {
+    hipLaunchKernelGGL((k_spmm_hub_chunks<VEC, 8, HT, decltype(GP)::value, decltype(CS)::value, EW>), gridc, blk, 0, st, g.rowptr, g.col, h, ld_h, (int)d,
                        g.hub_threshold, g.n_hubs, g.n_chunks, g.hub_rows, g.hub_chunk_ptr, partial, ld_p, ep);
   });
   CB_LAUNCH_CHECK();

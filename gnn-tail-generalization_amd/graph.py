@@ -6,6 +6,7 @@ and the hub plan, all built once on the GPU through the C ABI (include/coldbrew_
 The DGL-like query surface that GCNConv.forward touches is kept: in_degrees(),
 out_degrees(), number_of_edges(), number_of_nodes().
 """
+import ctypes
 import math
 import typing
 
@@ -791,6 +792,78 @@ class RowSupportPlan:
     @property
     def fwd0(self):
         return self.fwd[0] if self.fwd else None
+
+
+class WeightedAdj:
+    """An adjacency WITH VALUES — what the reference's GCN / WSAGE runs hand their layers as `adj_t` (trainer_link_prediction.py:276-342): a CSRGraph
+    built with keep_edge_order=True and one float32 value per stored edge.  Repeated edges stay separate entries (their sum is what coalesce(reduce='add')
+    gives).  Holds the values three times, made once through CSRGraph.edge_perm: `edge_weight` (edge-list order), `val` (by-dst CSR order, the forward)
+    and `val_t` (by-src CSR order, the backward).  The values are data: nothing differentiates them (ops.aggregate(edge_weight=...) does, elsewhere).
+    `deg` / `factor` are set by ops.adj_normalize on its result (the row sums and 1 / deg or deg^-1/2 it used)."""
+
+    def __init__(self, graph, edge_weight):
+        _lib.require_device(edge_weight)
+        if not isinstance(graph, CSRGraph) or graph.n_cols != graph.N or graph.row_offset or graph.rowptr_t is None:
+            raise ValueError('WeightedAdj: the whole square graph on this device (a CSRGraph with both orientations) is required; node-sharded and '
+                             'segmented graphs carry no edge values')
+        w = edge_weight.detach().reshape(-1)
+        if not w.is_floating_point() or w.numel() != graph.E:
+            raise ValueError(f'WeightedAdj: {graph.E} floating-point edge values expected (one per column of edge_index), got {tuple(edge_weight.shape)} '
+                             f'{edge_weight.dtype}')
+        self.graph, self.N, self.E, self.device = graph, graph.N, graph.E, graph.device
+        self.edge_weight = w.to(torch.float32).contiguous()
+        self.val = self.edge_weight[graph.edge_perm(False)].contiguous()
+        self.val_t = self.edge_weight[graph.edge_perm(True)].contiguous()
+        self.deg = self.factor = None
+
+    @classmethod
+    def from_edges(cls, edge_index, edge_weight=None, num_nodes=None, hub_threshold=None):
+        """The CSRGraph of edge_index (with its edge order kept) and the values on it; edge_weight None: every value 1."""
+        g = CSRGraph(edge_index, num_nodes, hub_threshold=hub_threshold, keep_edge_order=True)
+        if edge_weight is None:
+            edge_weight = torch.ones(g.E, dtype=torch.float32, device=g.device)
+        return cls(g, edge_weight)
+
+    @classmethod
+    def from_csr_values(cls, graph, val):
+        """The adjacency over `graph` whose by-dst CSR position j holds val[j]."""
+        w = torch.empty(graph.E, dtype=torch.float32, device=graph.device)
+        w[graph.edge_perm(False)] = val
+        return cls(graph, w)
+
+    def number_of_nodes(self):
+        return self.N
+
+    def number_of_edges(self):
+        return self.E
+
+    def spmm_ew(self, h, transpose=False, out=None):
+        """out[v] = sum_j w[j] * h[col[j]] over the by-dst CSR (transpose: by-src, i.e. A_w^T h): acc += w * x edge by edge in fp32, a hub row in chunks of
+        hub_threshold edges merged in chunk order.  fp32 rows with d % 256 == 0 and 16-byte alignment run on the tuned aggregation (cb_spmm_csr_ew_f32);
+        other widths on CSRGraph.spmm_weighted's one-wavefront-per-row kernel."""
+        lib = _lib.load()
+        _lib.require_device(h, out)
+        g = self.graph
+        if h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != g.n_cols:
+            raise ValueError(f'spmm_ew: float32 [{g.n_cols}, d] rows expected, got {tuple(h.shape)} {h.dtype}')
+        if h.stride(1) != 1 and h.shape[1] > 1:
+            h = h.contiguous()
+        d = h.shape[1]
+        if out is None:
+            out = torch.empty((g.N, d), dtype=torch.float32, device=h.device)
+        elif tuple(out.shape) != (g.N, d) or out.dtype != torch.float32 or (d > 1 and out.stride(1) != 1):
+            raise ValueError(f'spmm_ew: out must be a float32 [{g.N}, {d}] matrix with contiguous rows')
+        w = self.val_t if transpose else self.val
+        ld_h = h.stride(0) if h.shape[0] > 1 else d
+        ld_o = out.stride(0) if out.shape[0] > 1 else d
+        tuned = d > 0 and d % 256 == 0 and h.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and ld_h % 4 == 0 and ld_o % 4 == 0
+        if not tuned:
+            out.copy_(g.spmm_weighted(h, w, transpose=transpose))
+            return out
+        view = g._view(d, transpose, use_flags=True)
+        with torch.cuda.device(h.device):
+            _lib.check(lib.cb_spmm_csr_ew_f32(ctypes.byref(view), _lib.ptr(w), _lib.ptr(h), ld_h, d, _lib.ptr(out), ld_o, _lib.stream_ptr()), 'cb_spmm_csr_ew_f32')
+        return out
 
 
 def build_graph(edge_index, num_nodes=None):

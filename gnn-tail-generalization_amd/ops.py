@@ -2076,12 +2076,19 @@ def sage_layer_raw(graph, h, W_n, W_s=None, bias=None, scale=None, relu=False, p
     out = epi([agg | h] @ [W_n^T ; W_s^T] + bias).  backward=True: by-src CSR, agg = A^T (scale * h) by source row, out = [agg | h] @ [W_n ; W_s].
     W_s None: no self block.  fused (None: tuning.T.sage_fused): the one-kernel layer where cb_sage_layer_supported allows, else — and for
     fused=False — the composed path: graph.spmm, the materialised [agg | h], one cb_gemm_nn_f32 with K = 2 d, ops.dropout's kernel.  The two give the
-    same bits.  out: optional [N, d_out] float32 destination with contiguous rows."""
+    same bits.  out: optional [N, d_out] float32 destination with contiguous rows.
+    graph may be a graph.WeightedAdj (an adjacency with one value per stored edge; scale must be None): agg = A_w h, resp. A_w^T h — the fused path is
+    cb_ewlayer_f32, the composed one WeightedAdj.spmm_ew + the same GEMM; the same bits again."""
     from . import gemm
-    from .graph import CSRGraph
+    from .graph import CSRGraph, WeightedAdj
     from .tuning import T
     lib = _lib.load()
     _lib.require_device(h, W_n, W_s, bias, scale, out)
+    adj = None
+    if isinstance(graph, WeightedAdj):
+        if scale is not None:
+            raise ValueError('sage_layer: an adjacency with values takes no row / source factor beside them (mode SAGE reads its .graph)')
+        adj, graph = graph, graph.graph
     if not isinstance(graph, CSRGraph) or graph.n_cols != graph.N or (backward and graph.rowptr_t is None):
         raise ValueError('sage_layer: the whole square graph on this device (a CSRGraph with both orientations) is required; node-sharded and segmented '
                          'graphs are not built for the encoders')
@@ -2109,6 +2116,13 @@ def sage_layer_raw(graph, h, W_n, W_s=None, bias=None, scale=None, relu=False, p
         img = _sage_image(W_n, W_s, transpose=not backward)
         view = graph._view(256, backward, use_flags=True)
         with torch.cuda.device(h.device):
+            if adj is not None:
+                _lib.check(lib.cb_ewlayer_f32(ctypes.byref(view), _lib.ptr(adj.val_t if backward else adj.val), _lib.ptr(h), h.stride(0),
+                                              _lib.ptr(h if has_self else None), h.stride(0), _lib.ptr(img), _lib.ptr(bias), int(bool(relu)), float(p),
+                                              ctypes.c_uint64(int(seed)), seed_dev_ptr(), int(row0), _lib.ptr(agg), 256 if agg is not None else 0, hubs_only,
+                                              _lib.ptr(out), out.stride(0), _lib.stream_ptr()), 'cb_ewlayer_f32')
+                sage_paths.append(('bwd' if backward else 'fwd', 'fused'))
+                return out, (agg if want_agg else None), 'fused'
             _lib.check(lib.cb_sage_layer_f32(ctypes.byref(view), _lib.ptr(h), h.stride(0), _lib.ptr(h if has_self else None), h.stride(0),
                                              _lib.ptr(scale if backward else None), _lib.ptr(None if backward else scale), _lib.ptr(img), _lib.ptr(bias),
                                              int(bool(relu)), float(p), ctypes.c_uint64(int(seed)), seed_dev_ptr(), int(row0), _lib.ptr(agg),
@@ -2118,7 +2132,9 @@ def sage_layer_raw(graph, h, W_n, W_s=None, bias=None, scale=None, relu=False, p
     K = 2 * d if has_self else d
     cat = torch.empty((N, K), dtype=torch.float32, device=h.device)
     aggv = cat[:, :d]
-    if backward and scale is not None and d % 256:      # (the source-row factor exists at d % 256 == 0: elsewhere a row-scaled copy of h is gathered)
+    if adj is not None:
+        adj.spmm_ew(h, transpose=backward, out=aggv)
+    elif backward and scale is not None and d % 256:      # (the source-row factor exists at d % 256 == 0: elsewhere a row-scaled copy of h is gathered)
         graph.spmm(act_bwd(h, None, scale)[0], transpose=True, out=aggv)
     else:
         graph.spmm(h, transpose=backward, row_scale=None if backward else scale, col_scale=scale if backward else None, out=aggv)
@@ -2139,10 +2155,12 @@ def sage_layer_raw(graph, h, W_n, W_s=None, bias=None, scale=None, relu=False, p
 class _SageLayerFn(torch.autograd.Function):
     """Y = epi((s * (A X)) W_n^T + X W_s^T + b).  With G = dY * 1[Y > 0] / (1 - p) (the stored activation is the mask: dropout(relu(y)) > 0 exactly where the
     ReLU passed and the mask kept; G = dY on a layer without ReLU) and R = A^T (s * G):  dX = R W_n + G W_s,  dW_n = R^T X,  dW_s = G^T X,  db = colsum(G).
-    The forward stores neither the aggregated matrix nor mask words."""
+    The forward stores neither the aggregated matrix nor mask words.  graph a graph.WeightedAdj (WSAGE / GCN): A is A_w, the values are data (no gradient)."""
 
     @staticmethod
     def forward(ctx, graph, x, W_n, W_s, bias, mode, relu, p, seed, fused):
+        if mode == 'SAGE':
+            graph = getattr(graph, 'graph', graph)      # (PyG's SAGEConv drops the values of adj_t)
         scale = inv_indeg(graph) if mode == 'SAGE' else None
         y, _, _ = sage_layer_raw(graph, x, W_n, W_s, bias, scale, relu, p, seed, False, False, fused)
         ctx.graph, ctx.scale, ctx.relu, ctx.p, ctx.fused, ctx.has_bias = graph, scale, relu, p, fused, bias is not None
@@ -2173,7 +2191,9 @@ def sage_layer(graph, x, W_n, W_s=None, bias=None, mode='SAGE', relu=False, p=0.
     """One layer of the SAGE / WSAGE / GCN encoders with its autograd: act((s * (A X)) W_n^T + X W_s^T + b), A X the sum over the in-neighbours as the
     by-dst CSR lists them; mode 'SAGE': s = 1 / indeg (0 where indeg = 0), 'WSAGE': s = 1, 'GCN': s = 1 and no W_s.  relu: ReLU, then dropout p with
     ops.dropout's keep-mask for `seed` (None: next_seed()).  Weights are [out, in].  fused (None: tuning.T.sage_fused) asks for the one-kernel layer
-    (256 -> 256 fp32 rows); other shapes and fused=False take the composed path — ops.sage_paths records which."""
+    (256 -> 256 fp32 rows); other shapes and fused=False take the composed path — ops.sage_paths records which.
+    graph may be a graph.WeightedAdj: 'WSAGE' and 'GCN' then aggregate with its values, agg[v] = sum over the in-edges e of w_e * x[u_e] (GraphConv /
+    GCNConv(normalize=False) on an adj_t with values); 'SAGE' ignores them, bit for bit."""
     mode = str(mode).upper()
     if mode not in SAGE_MODES:
         raise ValueError(f'sage_layer: mode must be one of {SAGE_MODES}, got {mode!r}')
@@ -2190,6 +2210,48 @@ def sage_layer(graph, x, W_n, W_s=None, bias=None, mode='SAGE', relu=False, p=0.
     if x.shape[1] > 1 and x.stride(1) != 1:
         x = x.contiguous()
     return _SageLayerFn.apply(graph, x, W_n, W_s, bias, mode, bool(relu), p, int(seed or 0), fused)
+
+
+ADJ_NORMALIZATIONS = ('gcn', 'adj')
+
+
+def adj_normalize(adj, kind):
+    """The reference's two normalisations of an adjacency with values (Link_prediction_model/utils.py:93-106) as a new graph.WeightedAdj:
+    'adj': D^-1 A — deg = row sums, f = 1 / deg (inf -> 0), w' = f[v] * w;
+    'gcn': D^-1/2 (A with its diagonal set to 1) D^-1/2 — torch_sparse's set_diag first (every stored (v, v) dropped, one (v, v) of value 1 per node: a new
+           CSRGraph, built with torch and the ingest), then deg = row sums, dis = deg^-1/2 (inf -> 0), w' = (dis[v] * w) * dis[u].  A negative row sum raises.
+    Rows are destinations (adj_t).  deg: float64 sum rounded once to fp32; the factor in float64 from that fp32, rounded once (csrc/cb_adjnorm.hip).  The
+    result carries .deg and .factor.  Runs once per graph; one host read (the status word)."""
+    from .graph import CSRGraph, WeightedAdj
+    lib = _lib.load()
+    if kind not in ADJ_NORMALIZATIONS:
+        raise ValueError(f'adj_normalize: kind must be one of {ADJ_NORMALIZATIONS}, got {kind!r}')
+    if not isinstance(adj, WeightedAdj):
+        raise TypeError('adj_normalize expects a graph.WeightedAdj (graph.WeightedAdj.from_edges(edge_index, edge_weight, num_nodes))')
+    g, w = adj.graph, adj.edge_weight
+    if kind == 'gcn':
+        ei = g._ei
+        keep = ei[0] != ei[1]
+        diag = torch.arange(g.N, dtype=torch.int64, device=g.device)
+        ei = torch.cat([ei[:, keep], torch.stack([diag, diag])], dim=1)
+        w = torch.cat([w[keep], torch.ones(g.N, dtype=torch.float32, device=g.device)])
+        g = CSRGraph(ei, g.N, hub_threshold=g.hub_threshold, keep_edge_order=True)
+    val = w[g.edge_perm(False)].contiguous()
+    deg = torch.empty(g.N, dtype=torch.float32, device=g.device)
+    fac = torch.empty(g.N, dtype=torch.float32, device=g.device)
+    out = torch.empty(g.E, dtype=torch.float32, device=g.device)
+    status = torch.zeros(1, dtype=torch.int32, device=g.device)
+    with torch.cuda.device(g.device):
+        _lib.check(lib.cb_adjnorm_rowsum_f64(_lib.ptr(g.rowptr), _lib.ptr(val), g.N, g.E, int(kind == 'gcn'), _lib.ptr(deg), _lib.ptr(fac), _lib.ptr(status),
+                                             _lib.stream_ptr()), 'cb_adjnorm_rowsum_f64')
+        _lib.check(lib.cb_adjnorm_scale_f32(_lib.ptr(g.rowptr), _lib.ptr(g.col), _lib.ptr(val), g.N, g.E, _lib.ptr(fac), _lib.ptr(fac if kind == 'gcn' else None),
+                                            _lib.ptr(out), _lib.stream_ptr()), 'cb_adjnorm_scale_f32')
+    bad = int(status.item())
+    if bad:
+        raise ValueError(f'adj_normalize: {bad} rows have a negative sum of values: deg^-1/2 is undefined there')
+    res = WeightedAdj.from_csr_values(g, out)
+    res.deg, res.factor = deg, fac
+    return res
 
 
 # ---------------------------------------------------------------------------------------------

@@ -825,8 +825,8 @@ class trainer:
         layers of --gnn_hidden_channels; args.encoder = 'TRANSFORMER' builds the TransformerEncoder here), predictor (input width gnn_hidden_channels) and one fused Adam over all three.  The device graph is built here
         from data.edge_index (the whole graph on this device) and the link sampler on it."""
         from . import optim as cb_optim
-        from .graph import CSRGraph, build_graph
         from .Link_prediction_model import create_encoder_layer, create_input_layer
+        from .Link_prediction_model.experiment import message_adjacency
         from .Link_prediction_model.model import reset_input_layer
         a = self.args
         if str(a.optimizer) != 'Adam':
@@ -834,9 +834,8 @@ class trainer:
         if a.encoder in ('CN', 'AA', 'PPR'):
             raise NotImplementedError(f'--encoder {a.encoder} is a heuristic without parameters: evaluate_linkp_heuristic scores it, there is nothing to train')
         n = self.global_nodes()
-        self.enc_graph = build_graph(self.data.edge_index, n)
-        if not isinstance(self.enc_graph, CSRGraph):
-            raise NotImplementedError('the encoders need the whole int32-indexed graph on this device; segmented and node-sharded graphs are not built for them')
+        # (the experiment's rule: data.edge_weight and args.normalize_adj make enc_adj an adjacency with values for GCN / WSAGE; else it is enc_graph)
+        self.enc_graph, self.enc_adj = message_adjacency(a, self.data, n, self.device)
         self._link_sampler, self._link_sampler_of = ops.LinkSampler(self.enc_graph, self.data.train_mask), self.data.train_mask
         input_dim, self.emb = create_input_layer(n, int(self.data.x.shape[1]), a.emb_hidden_channels, a.use_node_feats, a.train_node_emb, a.pretrain_emb)
         if self.emb is not None:
@@ -853,7 +852,7 @@ class trainer:
 
     def linkpred_encoder_embeddings(self):
         from .Link_prediction_model import create_input_feat
-        return self.encoder(create_input_feat(self.emb, self.data.x, self.args.use_node_feats), self.enc_graph)
+        return self.encoder(create_input_feat(self.emb, self.data.x, self.args.use_node_feats), self.enc_adj)
 
     def training_loss_linkpred_encoder(self):
         """Forward + objective of BaseModel.train's step (model.py:147-157) on the encoder's embeddings.  Returns the 0-dim loss."""

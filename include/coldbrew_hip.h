@@ -1032,6 +1032,30 @@ int cb_sage_layer_f32(const cb_csr_view* g, const float* h, int64_t ld_h, const 
                       int64_t row0, float* agg_out, int64_t ld_agg, int32_t agg_hubs_only, float* out, int64_t ld_out, void* stream);
 
 /* ----------------------------------------------------------------------------------
+ * The adjacency WITH VALUES of the link-prediction encoders: one fp32 value w per stored edge, in the order of the view's col array (the by-dst CSR
+ * for a forward, the by-src CSR for a backward; repeated edges stay separate entries).  Values are data: no entry here differentiates them
+ * (cb_spmm_edge_dot_f32 above does that for the node-classification boundary).
+ *   cb_spmm_csr_ew_f32   out[v] = sum_{j in row v} w_csr[j] * h[col[j]] on the tuned aggregation (cb_spmm_csr_f32's walk, hub plan, gather policy):
+ *                        fp32 rows, d % 256 == 0, 16-byte aligned, ld % 4 == 0; acc += w * x edge by edge in fp32, a hub row's chunk partials merged in
+ *                        chunk order.  Other widths: cb_spmm_csr_weighted_f32.
+ *   cb_ewlayer_f32       cb_sage_layer_f32 with w_csr in place of col_scale / row_scale (GraphConv: self = h; GCNConv(normalize=False): self = null);
+ *                        image, epilogue, agg_out and cb_sage_layer_supported as there.  Bit for bit cb_spmm_csr_ew_f32 + cb_gemm_nn_f32 on [agg | self].
+ *   cb_adjnorm_rowsum_f64  deg[v] = fp32(float64 sum of row v's values, fixed order), fac[v] = fp32(1.0 / deg) (inv_sqrt = 0) or fp32(1.0 / sqrt(deg))
+ *                        (inv_sqrt = 1), computed in float64 from the fp32 deg, an infinite result -> 0.  status (one int32 the caller zeroed) counts
+ *                        the rows with a negative sum under inv_sqrt.
+ *   cb_adjnorm_scale_f32 w_out[j] = (f[row of j] * w_csr[j]) * g[col[j]] (two fp32 roundings in this order); g null: f[row of j] * w_csr[j].  col may
+ *                        carry hot-source flags.  D^-1 A: (f = 1 / deg, g = null); D^-1/2 A D^-1/2: f = g = deg^-1/2.
+ * ---------------------------------------------------------------------------------- */
+int cb_spmm_csr_ew_f32(const cb_csr_view* g, const float* w_csr, const float* h, int64_t ld_h, int64_t d, float* out, int64_t ld_out, void* stream);
+int cb_ewlayer_f32(const cb_csr_view* g, const float* w_csr, const float* h, int64_t ld_h, const float* self, int64_t ld_self, const void* image,
+                   const float* bias, int relu, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, float* agg_out, int64_t ld_agg,
+                   int32_t agg_hubs_only, float* out, int64_t ld_out, void* stream);
+int cb_adjnorm_rowsum_f64(const int32_t* rowptr, const float* w_csr, int64_t N, int64_t E, int32_t inv_sqrt, float* deg, float* fac, int32_t* status,
+                          void* stream);
+int cb_adjnorm_scale_f32(const int32_t* rowptr, const int32_t* col, const float* w_csr, int64_t N, int64_t E, const float* f, const float* g, float* w_out,
+                         void* stream);
+
+/* ----------------------------------------------------------------------------------
  * Attention over the rows of a CSR (PyG TransformerConv with heads = 1, no edge features, no beta: Link_prediction_model/layer.py:77-83);
  * cb_attn.hip.  Q, K, V, S, dO and every result are fp32 rows of D elements with a leading dimension each (column slices of one [N, 4 D]
  * matrix): D % 4 == 0, D <= 512, 16-byte aligned, ld % 4 == 0, ld >= D — cb_attn_supported(D, rows, ld) answers per operand before any
