@@ -346,7 +346,7 @@ __device__ __forceinline__ void ag2_mfma_tile_rows(int t, const float* __restric
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               o[e] = o[e] * rs + ad[e] + bv[e];
-              o[e] = fmaxf(o[e], 0.f);
+              o[e] = relu_nan(o[e]);
             }
             store_keep4(gt.st, seed_eff, gm, kND, n, mk);
           }

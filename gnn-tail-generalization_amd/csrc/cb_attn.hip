@@ -226,7 +226,8 @@ __device__ __forceinline__ void attn_walk(const AttnArgs& a, AttnCtx<NCH>& c, in
   for (; e < e1; ++e) attn_step<MODE, NCH, GP, 1>(a, c, e, cl);
 }
 
-// The finished row (all lanes of the group; scalars by its lane 0)
+// The finished row (all lanes of the group; scalars by its lane 0).  A row is empty where l == 0 (a row with edges has l >= 1: its largest score
+// contributes exp(0)); an l that is not a number — a NaN or +Inf score — is NOT empty: the row and its lse come out NaN, never act(skip) and -inf
 template <int MODE, int NCH>
 __device__ __forceinline__ void attn_store(const AttnArgs& a, AttnCtx<NCH>& c, int row, int cl, int gl) {
   if constexpr (MODE == A_FWD) {
@@ -236,11 +237,11 @@ __device__ __forceinline__ void attn_store(const AttnArgs& a, AttnCtx<NCH>& c, i
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float o = __fadd_rn(c.l > 0.f ? __fdiv_rn(c.acc[i][e], c.l) : 0.f, sk[i][e]);
-        c.acc[i][e] = a.relu ? fmaxf(o, 0.f) : o;
+        const float o = __fadd_rn(c.l == 0.f ? 0.f : __fdiv_rn(c.acc[i][e], c.l), sk[i][e]);
+        c.acc[i][e] = a.relu ? relu_nan(o) : o;
       }
     store_frag<NCH>(a.out + (int64_t)row * a.ld_out, cl, a.d, c.acc);
-    if (a.lse_out && gl == 0) a.lse_out[row] = c.l > 0.f ? __fadd_rn(c.m, logf(c.l)) : -INFINITY;
+    if (a.lse_out && gl == 0) a.lse_out[row] = c.l == 0.f ? -INFINITY : __fadd_rn(c.m, logf(c.l));
   } else if constexpr (MODE == A_DELTA) {
     if (gl == 0) a.delta_out[row] = c.l;
   } else {

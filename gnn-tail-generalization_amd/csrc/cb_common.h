@@ -56,6 +56,13 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float mix2(float a, float x, float b, float y) { return __fmaf_rn(a, x, __fmul_rn(b, y)); }
 __device__ __forceinline__ float scale_add(float x, float s, float b) { return __fmaf_rn(x, s, b); }
 
+// The library's one ReLU.  fmaxf(v, 0.f) compiles to v_max_f32, which in IEEE mode returns the operand that is NOT a NaN: ReLU(NaN) came out 0, and the
+// NaN the HIP path relies on as its loud failure signal (unread rows, bad pair endpoints, a diverged run) left every fused ReLU as a plausible zero.
+// This form returns fmaxf(v, 0.f)'s bits for every v that is not a NaN (+0.0 for -0.0 and for every negative, subnormal or not; v itself above zero) and
+// v itself for a NaN, as torch.relu and the oracle do.  One compare and one select in place of two maxima: profiles/relu_nan.md;
+// tests/test_gpu_nonfinite.py holds every epilogue to it.  fmaxf stays where it is a maximum (running maxima, clamps).
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
+
 // wave-uniform broadcast helpers (values land in SGPRs)
 __device__ __forceinline__ int bcast_first(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int bcast_lane(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }

@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(256, 2) k_front(FrontArgs fa) {
       const float4 v = *reinterpret_cast<const float4*>(tp);
       float o[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = fmaxf(o[i] + bvec[i], 0.f);      // nn_epilogue: o * 1 + 0 + bias, then ReLU
+      for (int i = 0; i < 4; ++i) o[i] = relu_nan(o[i] + bvec[i]);      // nn_epilogue: o * 1 + 0 + bias, then ReLU
       float xd[4] = {o[0], o[1], o[2], o[3]};
       if constexpr (DROP) {
 #pragma unroll

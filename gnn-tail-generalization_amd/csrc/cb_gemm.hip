@@ -206,7 +206,7 @@ __global__ void k_splitk_finish(const float* __restrict__ partial, int nsplit, i
   if (ep.rowscale) s *= ep.rowscale[m];
   if (ep.addend) s += ep.addend[m * ep.ld_add + n];
   if (ep.bias) s += ep.bias[n];
-  if (ep.relu) s = fmaxf(s, 0.f);
+  if (ep.relu) s = relu_nan(s);
   C[m * ldc + n] = s;
 }
 

@@ -293,7 +293,7 @@ __device__ __forceinline__ void nn_epilogue(f32x16 (&acc)[2][WTN], float* __rest
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           o[q] = o[q] * rs + ad[q] + bv[q];
-          if (ep.relu) o[q] = fmaxf(o[q], 0.f);
+          if (ep.relu) o[q] = relu_nan(o[q]);
         }
         if constexpr (OUT_BF16) {   // Z stored as bf16 for the aggregation (build extension, fp32 accumulate downstream)
           bf16_t* cp = (bf16_t*)Cv + m * ldc + n;

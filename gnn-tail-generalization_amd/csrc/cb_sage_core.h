@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(64 * kSG) k_sage_layer(SageArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         o[e] = o[e] * rs + ad + bv[e];
-        if (a.relu) o[e] = fmaxf(o[e], 0.f);
+        if (a.relu) o[e] = relu_nan(o[e]);
       }
       if (a.thresh) {                      // cb_dropout_f32's keep-mask for (seed, flat index (row0 + m) * 256 + n)
         float mk[4];

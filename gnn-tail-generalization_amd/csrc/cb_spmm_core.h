@@ -254,7 +254,7 @@ __device__ __forceinline__ void fused_store(const FusedEpi& fe, int64_t row, int
     return;
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) a[i] = fmaxf(scale_add(acc[i], scale, b[i]), 0.f);
+  for (int i = 0; i < 4; ++i) a[i] = relu_nan(scale_add(acc[i], scale, b[i]));
   store_keep4(st, grow, fe.d, c0, m);
   if (st.bits) store_mask_words(st, st.bits + (grow * (fe.d >> 8) + (c0 >> 8)) * 4, lane_id(), a, m);
   if (st.out_act) store_stream<4>(st.out_act + row * st.ld_act + c0, a);
@@ -268,7 +268,7 @@ __device__ __forceinline__ void write_row(float* __restrict__ out_row, const flo
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const float t = scale_add(acc[i], scale, b[i]);   // rst * norm + bias   (GCN.py:250,253)
-    r[i] = relu ? fmaxf(t, 0.f) : t;
+    r[i] = relu ? relu_nan(t) : t;
   }
   store_stream<VEC>(out_row, r);
 }
@@ -459,7 +459,7 @@ __device__ __forceinline__ void stream_rows(int rlo, int rhi, int nr, int my_ptr
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             const float t = scale_add(acc[i], s, bvec[i]);
-            rv[i] = relu ? fmaxf(t, 0.f) : t;
+            rv[i] = relu ? relu_nan(t) : t;
           }
         } else {
           write_row<VEC>(out_lane + (int64_t)(r0 + cur) * ld_out, acc, s, bvec, relu, rv);

@@ -55,7 +55,7 @@ __device__ __forceinline__ void finish_row(bool on, float* __restrict__ out, int
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const float t = scale_add(acc[i], scale, b[i]);   // rst * norm + bias   (GCN.py:250,253)
-    r[i] = relu ? fmaxf(t, 0.f) : t;
+    r[i] = relu ? relu_nan(t) : t;
   }
   strow<VEC>(out + row * ld_out + c0, r);
 }
@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(256) k_small_hub_finish(int d, int n_hubs, con
   float acc = 0.f;
   for (int k = hub_chunk_ptr[i]; k < hub_chunk_ptr[i + 1]; ++k) acc += partial[(int64_t)k * ld_p + c];
   const float v = scale_add(acc, ep.row_scale ? ep.row_scale[row] : 1.f, ep.bias ? ep.bias[c] : 0.f);
-  out[(int64_t)row * ld_out + c] = ep.relu ? fmaxf(v, 0.f) : v;
+  out[(int64_t)row * ld_out + c] = ep.relu ? relu_nan(v) : v;
 }
 
 template <int G, int VEC>

@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) k_spmm_weighted(const int* __restrict__ r
       const int c = c0 + lane + 64 * j;
       if (c < d) {
         float v = scale_add(acc[j], rs, bias ? bias[c] : 0.f);      // rst * norm + bias (GCN.py:250,253), as cb_spmm_csr_f32
-        out[(int64_t)row * ld_out + c] = relu ? fmaxf(v, 0.f) : v;
+        out[(int64_t)row * ld_out + c] = relu ? relu_nan(v) : v;
       }
     }
   }

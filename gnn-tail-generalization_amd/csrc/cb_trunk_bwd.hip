@@ -293,7 +293,7 @@ __global__ void __launch_bounds__(kBlock) k_trunk_store_rows(const float* __rest
     for (int tile = 0; tile < tiles; ++tile) {
       const int c = tile * 256 + lane * 4;
       const float4 y4 = *reinterpret_cast<const float4*>(y + r * d + c);
-      const float a[4] = {fmaxf(y4.x, 0.f), fmaxf(y4.y, 0.f), fmaxf(y4.z, 0.f), fmaxf(y4.w, 0.f)};
+      const float a[4] = {relu_nan(y4.x), relu_nan(y4.y), relu_nan(y4.z), relu_nan(y4.w)};
       float m[4] = {1.f, 1.f, 1.f, 1.f}, q[4] = {0.f, 0.f, 0.f, 0.f}, x[4];
       store_keep4(st, seed, rr, d, c, m);
       if (st.bits) store_mask_words(st, st.bits + (rr * tiles + tile) * 4, lane, a, m);

@@ -139,7 +139,8 @@ size_t cb_spmm_workspace_bytes(int64_t n_chunks, int64_t d);
  *
  *     out[v, :] = act( row_scale[v] * (acc_init[v, :] + sum_{j in [rowptr[v], rowptr[v+1])} col_scale[col[j]] * h[col[j], :]) + bias[:] )
  *
- * row_scale / bias / col_scale / acc_init may be NULL (factor 1 / no bias / factor 1 / sums start from 0); relu = 0/1.  Called with the
+ * row_scale / bias / col_scale / acc_init may be NULL (factor 1 / no bias / factor 1 / sums start from 0); relu = 0/1 (here and in every
+ * entry of this header the ReLU is torch.relu's function: +0 for every v <= 0, v above, and a NaN stays a NaN).  Called with the
  * by-dst CSR for the forward and with the by-src CSR (no epilogue) for the backward (autograd of gspmm = SpMM on the reverse graph).
  * Deterministic: every row is reduced in CSR order by one wavefront, hub rows in chunk order.
  * h_bf16 != 0: h holds bf16-stored rows (uint16_t, round-to-nearest-even; ld_h in bf16 elements, 8-byte aligned for the vector paths) —
