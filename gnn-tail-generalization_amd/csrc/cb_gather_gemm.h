@@ -169,10 +169,9 @@ static int gather_gemm_entry(const char* who, const float* h, int64_t ld, int64_
                "%s: null pointer or leading dimension too small", who);
   CB_CHECK_ARG(gather_gemm_supported<Form>(h, ld, D, B, ldb, Nout), CB_E_INVALID, "%s: shape / alignment outside the fused form (%.*s_supported)", who,
                (int)strlen(who) - 4, who);      // (the predicate's name: the entry's with _supported for _f32)
-  GemmEpilogue ep{nullptr, nullptr, 0, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, R * Nout * 4 > ((int64_t)256 << 20) ? 1 : 0};
+  GemmEpilogue ep = epilogue(nullptr, nullptr, 0, bias, relu, gemm_nt_store(R, Nout));
   if (drop_p > 0.f && gather_dual_eligible(C, ldc, C2, ldc2, Nout)) {
-    ep.out2 = C2; ep.ld_out2 = ldc2; ep.thresh = dropout_threshold(drop_p); ep.keep_scale = 1.f / (1.f - drop_p);
-    ep.seed = seed; ep.seed_dev = seed_dev; ep.row0 = row0;
+    set_dropped_copy(ep, C2, ldc2, drop_p, seed, seed_dev, row0);
     return launch_gather_nn_limb3<Form>(h, ld, N, D, idx, R, B, ldb, C, ldc, Nout, ep, status, st);
   }
   CB_CHECK_ARG(drop_p == 0.f || (ldc == Nout && ldc2 == Nout), CB_E_INVALID,

@@ -154,6 +154,12 @@ __global__ void k_sum_partials(const float* __restrict__ partial, int nsplit, in
   out[i] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
 }
 
+static int sum_partials(const float* partial, int nsplit, int64_t n, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partial, nsplit, n, out);
+  CB_LAUNCH_CHECK();
+  return CB_OK;
+}
+
 static inline int tn_splits(int64_t M, int tiles) {
   // enough blocks for ~4 per CU, each with at least 8 K-steps of work: a K step of a lone block costs ~1.7 us of load latency,
   // so the Cora / Pubmed-sized reductions (M = 2 708 / 19 717 rows) want many short slabs (64 K-steps per slab left them
@@ -165,10 +171,6 @@ static inline int tn_splits(int64_t M, int tiles) {
   if (s > 1024) s = 1024;
   return (int)s;
 }
-
-// fp32 outputs too large to stay cached (> 256 MiB: the Infinity Cache) leave with the streaming policy: measured -1.5 % per launch
-// on 10M x 256 outputs (7.96 -> 7.84 ms)
-static inline int gemm_nt_store(int64_t M, int64_t N) { return M * N * 4 > ((int64_t)256 << 20); }
 
 // tile shape by output width: 2x2 (128x128) by default; for TN 1x4 (64x256) when K1 <= 64, 4x1 (256x64) when K2 <= 64
 static inline void tn_tile(int64_t K1, int64_t K2, int& bm, int& bn) {
@@ -252,30 +254,112 @@ static int launch_tn(const float* A, int64_t lda, const float* G, int64_t ldg, c
   const int nsplit = tn_splits(M, tiles_i * tiles_j);
   int64_t rows_per_split = (M + nsplit - 1) / nsplit;
   rows_per_split = (rows_per_split + 31) / 32 * 32;   // whole K steps of either kernel family
-  const bool aligned = aligned16(A) && aligned16(G) && lda % 4 == 0 && ldg % 4 == 0;
-  const dim3 grid((unsigned)(tiles_i * tiles_j), (unsigned)nsplit);
-  CB_CHECK_ARG(!(gdrop || adrop) || (limb3_on() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)), CB_E_INVALID,
-               "TN contraction with operand dropout: three-limb path only (check cb_gemm_tn_gdrop_supported first)");
-  if (limb3_on() && limb3_tn_eligible(A, lda, G, ldg, K1, K2)) {
+  const bool limb3 = limb3_on() && limb3_tn_eligible(A, lda, G, ldg, K1, K2);
+  CB_CHECK_ARG(!(gdrop || adrop) || limb3, CB_E_INVALID, "TN contraction with operand dropout: three-limb path only (check cb_gemm_tn_gdrop_supported first)");
+  if (limb3) {
     const int rc = launch_tn_limb3(A, lda, G, ldg, rowscale, ws, M, K1, K2, T::BM, nsplit, rows_per_split, st, gdrop, adrop);
     if (rc != CB_OK) return rc;
-    const int64_t n = K1 * K2;
-    hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)ws, nsplit, n, C);
+  } else {
+    const dim3 grid((unsigned)(tiles_i * tiles_j), (unsigned)nsplit);
+    if (aligned16(A) && aligned16(G) && lda % 4 == 0 && ldg % 4 == 0)
+      hipLaunchKernelGGL((k_gemm_tn<WM, WN, true>), grid, dim3(256), 0, st, A, lda, G, ldg, rowscale, ws, M, (int)K1, (int)K2, rows_per_split, tiles_j);
+    else
+      hipLaunchKernelGGL((k_gemm_tn<WM, WN, false>), grid, dim3(256), 0, st, A, lda, G, ldg, rowscale, ws, M, (int)K1, (int)K2, rows_per_split, tiles_j);
     CB_LAUNCH_CHECK();
+  }
+  return sum_partials(ws, nsplit, K1 * K2, C, st);
+}
+
+// ---- host cores of the extern "C" entries ------------------------------------------------------
+// What an NN entry asks for: C = act(rowscale * (A @ B) + addend + bias) plus the options below.  An entry fills the ones it has by name.
+struct NnCall {
+  const float* A; int64_t lda; const float* B; int64_t ldb; void* C; int64_t ldc; int64_t M, N, K;
+  const float* rowscale = nullptr; const float* addend = nullptr; int64_t ld_add = 0; const float* bias = nullptr; int relu = 0;
+  bool out_bf16 = false;
+  bool dual = false; float* C2 = nullptr; int64_t ldc2 = 0; float drop_p = 0.f; uint64_t seed = 0;      // second output C2 = dropout_p(C)
+  float a_drop_p = 0.f; uint64_t a_seed = 0;               // > 0: dropout of A while it is staged (fused form only: cb_gemm_nn_indrop_supported)
+  const uint64_t* seed_dev = nullptr; int64_t row0 = 0;    // of both dropouts
+  uint64_t* relu_bits = nullptr;                           // [M][4] mask words of (C > 0), or null
+  bool store_rows = false; const int64_t* row_index = nullptr; const cb_trunk_store* store = nullptr;   // the trunk's store on the rows row_index (fused form only)
+  void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
+};
+
+// the arguments every NN entry has, in the ABI's order
+static NnCall nn_call(const float* A, int64_t lda, const float* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const float* rowscale,
+                      const float* addend, int64_t ld_add, const float* bias, int relu, void* ws, size_t ws_bytes, void* stream) {
+  NnCall c{A, lda, B, ldb, C, ldc, M, N, K};
+  c.rowscale = rowscale; c.addend = addend; c.ld_add = ld_add; c.bias = bias; c.relu = relu;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return c;
+}
+
+// The checks of every NN entry in one order (`who`: the entry's name, for the messages), the epilogue, and the path: three-limb kernels where the
+// operands allow them (always for the fused-only forms), else the fp32-input kernel by output width; a second output the epilogue cannot write is
+// cb_dropout_f32 of the first.
+static int nn_entry(const char* who, const NnCall& c) {
+  const float *A = c.A, *B = c.B;
+  const int64_t lda = c.lda, ldb = c.ldb, ldc = c.ldc, M = c.M, N = c.N, K = c.K;
+  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && c.drop_p >= 0.f && c.drop_p < 1.f && c.a_drop_p >= 0.f && c.a_drop_p < 1.f && c.row0 >= 0, CB_E_INVALID,
+               "%s: bad size, p or row offset", who);
+  CB_CHECK_ARG(!c.relu_bits || (N == 256 && c.relu && (uintptr_t)c.relu_bits % 8 == 0), CB_E_INVALID,
+               "%s: mask words of the ReLU exist for N == 256 with relu only", who);
+  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "%s: size out of range", who);
+  if (M == 0 || N == 0) return CB_OK;
+  CB_CHECK_ARG(c.C && (K == 0 || (A && B)) && lda >= K && ldb >= N && ldc >= N && (!c.addend || c.ld_add >= N) && (!c.dual || (c.C2 && c.ldc2 >= N)) &&
+                   (!c.store_rows || c.row_index),
+               CB_E_INVALID, "%s: null pointer or leading dimension too small", who);
+  if (c.store_rows) {
+    const int rc = check_trunk_store(who, c.store, N);
+    if (rc != CB_OK) return rc;
+  }
+  const bool addend_vec = !c.addend || (aligned16(c.addend) && c.ld_add % 4 == 0);
+  CB_CHECK_ARG(!c.store_rows || (cb_gemm_nn_store_rows_supported(A, lda, B, ldb, (const float*)c.C, ldc, M, N, K) && addend_vec), CB_E_INVALID,
+               "%s: shape / alignment outside the fused form (cb_gemm_nn_store_rows_supported)", who);
+  const float* C2 = c.dual ? c.C2 : (const float*)c.C;
+  CB_CHECK_ARG(c.a_drop_p == 0.f || (cb_gemm_nn_indrop_supported(A, lda, B, ldb, (const float*)c.C, ldc, C2, c.dual ? c.ldc2 : ldc, M, N, K) && addend_vec),
+               CB_E_INVALID, "%s: shape / alignment outside the fused form (cb_gemm_nn_indrop_supported)", who);
+  GemmEpilogue ep = epilogue(c.rowscale, c.addend, c.ld_add, c.bias, c.relu, gemm_nt_store(M, N));
+  ep.relu_bits_out = (unsigned long long*)c.relu_bits;
+  if (c.a_drop_p > 0.f) ep.adrop = make_drop_spec(c.a_drop_p, c.a_seed, c.seed_dev, c.row0, K);
+  if (c.store_rows) { ep.row_ids = c.row_index; ep.st = make_trunk_store(*c.store); }
+  if (c.dual && limb3_on() && c.drop_p > 0.f && limb3_nn_dual_eligible(A, lda, B, ldb, (const float*)c.C, ldc, c.C2, c.ldc2, M, N, K, ep))
+    set_dropped_copy(ep, c.C2, c.ldc2, c.drop_p, c.seed, c.seed_dev, c.row0);
+  hipStream_t st = (hipStream_t)c.stream;
+  int rc;
+  if (limb3_on() && limb3_nn_eligible(A, lda, B, ldb, N, K)) rc = launch_nn_limb3(A, lda, B, ldb, c.C, ldc, M, N, K, ep, c.out_bf16, st, c.ws, c.ws_bytes);
+  else if (!c.out_bf16) rc = N <= 64 ? launch_nn<4, 1>(A, lda, B, ldb, c.C, ldc, M, N, K, ep, st, c.ws, c.ws_bytes) : launch_nn<2, 2>(A, lda, B, ldb, c.C, ldc, M, N, K, ep, st, c.ws, c.ws_bytes);
+  else rc = N <= 64 ? launch_nn<4, 1, true>(A, lda, B, ldb, c.C, ldc, M, N, K, ep, st) : launch_nn<2, 2, true>(A, lda, B, ldb, c.C, ldc, M, N, K, ep, st);
+  if (rc != CB_OK || !c.dual || ep.out2) return rc;
+  CB_CHECK_ARG(ldc == N && c.ldc2 == N, CB_E_INVALID, "%s: the two-kernel form needs contiguous outputs", who);
+  return cb_dropout_f32((const float*)c.C, c.C2, M * N, c.drop_p, c.seed, c.seed_dev, c.row0 * N, c.stream);
+}
+
+// The checks of the TN entries, the zero result of M == 0, the workspace and the tile by output width.  gdrop / adrop (at most one): the operand
+// dropped while it is staged, which exists on the three-limb path only.
+static int tn_entry(const char* who, const float* A, int64_t lda, const float* G, int64_t ldg, const float* rowscale, float* C, int64_t M, int64_t K1,
+                    int64_t K2, const DropSpec* gdrop, const DropSpec* adrop, void* ws, size_t ws_bytes, void* stream) {
+  CB_CHECK_ARG(M >= 0 && K1 >= 0 && K2 >= 0, CB_E_INVALID, "%s: negative size", who);
+  CB_CHECK_ARG(K1 < (1 << 20) && K2 < (1 << 20), CB_E_RANGE, "%s: size out of range", who);
+  if (K1 == 0 || K2 == 0) return CB_OK;
+  CB_CHECK_ARG(C && (M == 0 || (A && G)) && lda >= K1 && ldg >= K2, CB_E_INVALID, "%s: null pointer or bad ld", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) {
+    CB_HIP(hipMemsetAsync(C, 0, (size_t)K1 * K2 * sizeof(float), st));
     return CB_OK;
   }
-  if (aligned)
-    hipLaunchKernelGGL((k_gemm_tn<WM, WN, true>), grid, dim3(256), 0, st, A, lda, G, ldg, rowscale, ws, M, (int)K1, (int)K2,
-                       rows_per_split, tiles_j);
-  else
-    hipLaunchKernelGGL((k_gemm_tn<WM, WN, false>), grid, dim3(256), 0, st, A, lda, G, ldg, rowscale, ws, M, (int)K1, (int)K2,
-                       rows_per_split, tiles_j);
-  CB_LAUNCH_CHECK();
-  const int64_t n = K1 * K2;
-  hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)ws, nsplit, n, C);
-  CB_LAUNCH_CHECK();
-  return CB_OK;
+  CB_CHECK_ARG(!gdrop || cb_gemm_tn_gdrop_supported(A, lda, G, ldg, K1, K2), CB_E_INVALID, "%s: operands outside the three-limb path (cb_gemm_tn_gdrop_supported)", who);
+  CB_CHECK_ARG(!adrop || cb_gemm_tn_adrop_supported(A, lda, G, ldg, K1, K2), CB_E_INVALID,
+               "%s: operands outside the three-limb 128-row tile path (cb_gemm_tn_adrop_supported)", who);
+  CB_CHECK_ARG(ws && ws_bytes >= cb_gemm_tn_workspace_bytes(M, K1, K2), CB_E_WORKSPACE, "%s: workspace too small", who);
+  int bm, bn;
+  tn_tile(K1, K2, bm, bn);
+  if (bm == 64) return launch_tn<1, 4>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st, gdrop, adrop);
+  if (bm == 256) return launch_tn<4, 1>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st, gdrop, adrop);
+  return launch_tn<2, 2>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st, gdrop, adrop);
 }
+
+// an operand dropout that is on: 0 < p < 1 (p == 0 is another entry), a row offset
+static inline bool active_drop(float p, int64_t row0) { return p > 0.f && p < 1.f && row0 >= 0; }
 
 }  // namespace cb
 
@@ -296,16 +380,7 @@ extern "C" size_t cb_gemm_nn_splitk_workspace_bytes(int64_t M, int64_t N, int64_
 extern "C" int cb_gemm_nn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N,
                               int64_t K, const float* rowscale, const float* addend, int64_t ld_add, const float* bias, int relu,
                               void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, CB_E_INVALID, "cb_gemm_nn_f32: negative size");
-  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_f32: size out of range");
-  if (M == 0 || N == 0) return CB_OK;
-  CB_CHECK_ARG(C && (K == 0 || (A && B)) && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID,
-               "cb_gemm_nn_f32: null pointer or leading dimension too small");
-  GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
-  hipStream_t st = (hipStream_t)stream;
-  if (limb3_on() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, st, ws, ws_bytes);
-  if (N <= 64) return launch_nn<4, 1>(A, lda, B, ldb, C, ldc, M, N, K, ep, st, ws, ws_bytes);
-  return launch_nn<2, 2>(A, lda, B, ldb, C, ldc, M, N, K, ep, st, ws, ws_bytes);
+  return nn_entry("cb_gemm_nn_f32", nn_call(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, relu, ws, ws_bytes, stream));
 }
 
 // C = act(rowscale * (A @ B) + addend + bias) and C2 = dropout_p(C) from ONE pass: the input Linear + ReLU of the residual
@@ -316,22 +391,9 @@ extern "C" int cb_gemm_nn_drop2_f32(const float* A, int64_t lda, const float* B,
                                     int64_t M, int64_t N, int64_t K, const float* rowscale, const float* addend, int64_t ld_add,
                                     const float* bias, int relu, float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0,
                                     void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && drop_p >= 0.f && drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_gemm_nn_drop2_f32: bad size or p");
-  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_drop2_f32: size out of range");
-  if (M == 0 || N == 0) return CB_OK;
-  CB_CHECK_ARG(C && C2 && (K == 0 || (A && B)) && lda >= K && ldb >= N && ldc >= N && ldc2 >= N && (!addend || ld_add >= N), CB_E_INVALID,
-               "cb_gemm_nn_drop2_f32: null pointer or leading dimension too small");
-  GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
-  hipStream_t st = (hipStream_t)stream;
-  if (limb3_on() && drop_p > 0.f && limb3_nn_dual_eligible(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K, ep)) {
-    ep.out2 = C2; ep.ld_out2 = ldc2; ep.thresh = dropout_threshold(drop_p); ep.keep_scale = 1.f / (1.f - drop_p);
-    ep.seed = seed; ep.seed_dev = seed_dev; ep.row0 = row0;
-    return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, st, ws, ws_bytes);
-  }
-  int rc = cb_gemm_nn_f32(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, relu, ws, ws_bytes, stream);
-  if (rc != CB_OK) return rc;
-  CB_CHECK_ARG(ldc == N && ldc2 == N, CB_E_INVALID, "cb_gemm_nn_drop2_f32: the two-kernel form needs contiguous outputs");
-  return cb_dropout_f32(C, C2, M * N, drop_p, seed, seed_dev, row0 * N, stream);
+  NnCall c = nn_call(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, relu, ws, ws_bytes, stream);
+  c.dual = true; c.C2 = C2; c.ldc2 = ldc2; c.drop_p = drop_p; c.seed = seed; c.seed_dev = seed_dev; c.row0 = row0;
+  return nn_entry("cb_gemm_nn_drop2_f32", c);
 }
 
 // The same with the dropout IN FRONT of the Linear applied to A as it is staged (GCN.py:104: x = F.dropout(x) before layers_MLP[0]):
@@ -347,36 +409,19 @@ extern "C" int cb_gemm_nn_indrop_drop2_f32(const float* A, int64_t lda, const fl
                                            int64_t M, int64_t N, int64_t K, const float* bias, int relu, float a_drop_p, uint64_t a_seed,
                                            float drop_p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits,
                                            void* stream) {
-  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && drop_p > 0.f && drop_p < 1.f && a_drop_p > 0.f && a_drop_p < 1.f && row0 >= 0, CB_E_INVALID,
-               "cb_gemm_nn_indrop_drop2_f32: bad size or p");
-  CB_CHECK_ARG(!relu_bits || (N == 256 && relu && (uintptr_t)relu_bits % 8 == 0), CB_E_INVALID,
-               "cb_gemm_nn_indrop_drop2_f32: mask words of the ReLU exist for N == 256 with relu only");
-  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_indrop_drop2_f32: size out of range");
-  if (M == 0 || N == 0) return CB_OK;
-  CB_CHECK_ARG(C && C2 && A && B && lda >= K && ldb >= N && ldc >= N && ldc2 >= N, CB_E_INVALID, "cb_gemm_nn_indrop_drop2_f32: null pointer or bad ld");
-  CB_CHECK_ARG(cb_gemm_nn_indrop_supported(A, lda, B, ldb, C, ldc, C2, ldc2, M, N, K), CB_E_INVALID,
-               "cb_gemm_nn_indrop_drop2_f32: shape / alignment outside the fused form (cb_gemm_nn_indrop_supported)");
-  GemmEpilogue ep{nullptr, nullptr, 0, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
-  ep.out2 = C2; ep.ld_out2 = ldc2; ep.thresh = dropout_threshold(drop_p); ep.keep_scale = 1.f / (1.f - drop_p);
-  ep.seed = seed; ep.seed_dev = seed_dev; ep.row0 = row0;
-  ep.adrop = DropSpec{dropout_threshold(a_drop_p), 1.f / (1.f - a_drop_p), a_seed, seed_dev, row0, K};
-  ep.relu_bits_out = (unsigned long long*)relu_bits;
-  return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, (hipStream_t)stream, nullptr, 0);
+  CB_CHECK_ARG(active_drop(drop_p, row0) && active_drop(a_drop_p, row0), CB_E_INVALID, "cb_gemm_nn_indrop_drop2_f32: both dropouts must be active (0 < p < 1)");
+  NnCall c = nn_call(A, lda, B, ldb, C, ldc, M, N, K, nullptr, nullptr, 0, bias, relu, nullptr, 0, stream);
+  c.dual = true; c.C2 = C2; c.ldc2 = ldc2; c.drop_p = drop_p; c.seed = seed; c.seed_dev = seed_dev; c.row0 = row0;
+  c.a_drop_p = a_drop_p; c.a_seed = a_seed; c.relu_bits = relu_bits;
+  return nn_entry("cb_gemm_nn_indrop_drop2_f32", c);
 }
 
 extern "C" int cb_gemm_nn_bf16out_f32(const float* A, int64_t lda, const float* B, int64_t ldb, uint16_t* C, int64_t ldc, int64_t M,
                                       int64_t N, int64_t K, const float* rowscale, const float* addend, int64_t ld_add,
                                       const float* bias, int relu, void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, CB_E_INVALID, "cb_gemm_nn_bf16out_f32: negative size");
-  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_bf16out_f32: size out of range");
-  if (M == 0 || N == 0) return CB_OK;
-  CB_CHECK_ARG(C && (K == 0 || (A && B)) && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID,
-               "cb_gemm_nn_bf16out_f32: null pointer or leading dimension too small");
-  GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
-  hipStream_t st = (hipStream_t)stream;
-  if (limb3_on() && limb3_nn_eligible(A, lda, B, ldb, N, K)) return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, true, st, ws, ws_bytes);
-  if (N <= 64) return launch_nn<4, 1, true>(A, lda, B, ldb, C, ldc, M, N, K, ep, st);
-  return launch_nn<2, 2, true>(A, lda, B, ldb, C, ldc, M, N, K, ep, st);
+  NnCall c = nn_call(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, relu, ws, ws_bytes, stream);
+  c.out_bf16 = true;
+  return nn_entry("cb_gemm_nn_bf16out_f32", c);
 }
 
 extern "C" size_t cb_gemm_tn_workspace_bytes(int64_t M, int64_t K1, int64_t K2) {
@@ -400,37 +445,15 @@ extern "C" int cb_gemm_nn_store_rows_supported(const float* A, int64_t lda, cons
 extern "C" int cb_gemm_nn_store_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                                          const float* rowscale, const float* addend, int64_t ld_add, const float* bias, const int64_t* row_index,
                                          const cb_trunk_store* store, void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M >= 0 && N == 256 && K > 0, CB_E_INVALID, "cb_gemm_nn_store_rows_f32: bad size (N must be 256)");
-  CB_CHECK_ARG(K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_store_rows_f32: size out of range");
-  if (M == 0) return CB_OK;
-  CB_CHECK_ARG(A && B && C && row_index && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID,
-               "cb_gemm_nn_store_rows_f32: null pointer or leading dimension too small");
-  const int rcs = check_trunk_store("cb_gemm_nn_store_rows_f32", store, N);
-  if (rcs != CB_OK) return rcs;
-  CB_CHECK_ARG(cb_gemm_nn_store_rows_supported(A, lda, B, ldb, C, ldc, M, N, K) && (!addend || (aligned16(addend) && ld_add % 4 == 0)), CB_E_INVALID,
-               "cb_gemm_nn_store_rows_f32: shape / alignment outside the fused form (cb_gemm_nn_store_rows_supported)");
-  GemmEpilogue ep{rowscale, addend, ld_add, bias, 1, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, 0};
-  ep.row_ids = row_index; ep.st = make_trunk_store(*store);
-  return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, (hipStream_t)stream, ws, ws_bytes);
+  CB_CHECK_ARG(N == 256 && K > 0, CB_E_INVALID, "cb_gemm_nn_store_rows_f32: bad size (N must be 256)");
+  NnCall c = nn_call(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, 1, ws, ws_bytes, stream);
+  c.store_rows = true; c.row_index = row_index; c.store = store;
+  return nn_entry("cb_gemm_nn_store_rows_f32", c);
 }
 
 extern "C" int cb_gemm_tn_f32(const float* A, int64_t lda, const float* G, int64_t ldg, const float* rowscale, float* C, int64_t M,
                               int64_t K1, int64_t K2, void* ws, size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M >= 0 && K1 >= 0 && K2 >= 0, CB_E_INVALID, "cb_gemm_tn_f32: negative size");
-  CB_CHECK_ARG(K1 < (1 << 20) && K2 < (1 << 20), CB_E_RANGE, "cb_gemm_tn_f32: size out of range");
-  if (K1 == 0 || K2 == 0) return CB_OK;
-  CB_CHECK_ARG(C && (M == 0 || (A && G)) && lda >= K1 && ldg >= K2, CB_E_INVALID, "cb_gemm_tn_f32: null pointer or bad ld");
-  hipStream_t st = (hipStream_t)stream;
-  if (M == 0) {
-    CB_HIP(hipMemsetAsync(C, 0, (size_t)K1 * K2 * sizeof(float), st));
-    return CB_OK;
-  }
-  CB_CHECK_ARG(ws && ws_bytes >= cb_gemm_tn_workspace_bytes(M, K1, K2), CB_E_WORKSPACE, "cb_gemm_tn_f32: workspace too small");
-  int bm, bn;
-  tn_tile(K1, K2, bm, bn);
-  if (bm == 64) return launch_tn<1, 4>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st);
-  if (bm == 256) return launch_tn<4, 1>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st);
-  return launch_tn<2, 2>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st);
+  return tn_entry("cb_gemm_tn_f32", A, lda, G, ldg, rowscale, C, M, K1, K2, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 // C = A^T @ dropout_{g_seed}(G): the weight gradient of the input Linear from the UNdropped features (mask regenerated while G is
@@ -442,23 +465,9 @@ extern "C" int cb_gemm_tn_gdrop_supported(const float* A, int64_t lda, const flo
 extern "C" int cb_gemm_tn_gdrop_f32(const float* A, int64_t lda, const float* G, int64_t ldg, float* C, int64_t M, int64_t K1, int64_t K2,
                                     float g_drop_p, uint64_t g_seed, const uint64_t* seed_dev, int64_t row0, void* ws, size_t ws_bytes,
                                     void* stream) {
-  CB_CHECK_ARG(M >= 0 && K1 >= 0 && K2 >= 0 && g_drop_p > 0.f && g_drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_gemm_tn_gdrop_f32: bad size or p");
-  CB_CHECK_ARG(K1 < (1 << 20) && K2 < (1 << 20), CB_E_RANGE, "cb_gemm_tn_gdrop_f32: size out of range");
-  if (K1 == 0 || K2 == 0) return CB_OK;
-  CB_CHECK_ARG(C && (M == 0 || (A && G)) && lda >= K1 && ldg >= K2, CB_E_INVALID, "cb_gemm_tn_gdrop_f32: null pointer or bad ld");
-  hipStream_t st = (hipStream_t)stream;
-  if (M == 0) {
-    CB_HIP(hipMemsetAsync(C, 0, (size_t)K1 * K2 * sizeof(float), st));
-    return CB_OK;
-  }
-  CB_CHECK_ARG(cb_gemm_tn_gdrop_supported(A, lda, G, ldg, K1, K2), CB_E_INVALID, "cb_gemm_tn_gdrop_f32: operands outside the three-limb path");
-  CB_CHECK_ARG(ws && ws_bytes >= cb_gemm_tn_workspace_bytes(M, K1, K2), CB_E_WORKSPACE, "cb_gemm_tn_gdrop_f32: workspace too small");
-  const DropSpec gd{dropout_threshold(g_drop_p), 1.f / (1.f - g_drop_p), g_seed, seed_dev, row0, K2};
-  int bm, bn;
-  tn_tile(K1, K2, bm, bn);
-  if (bm == 64) return launch_tn<1, 4>(A, lda, G, ldg, nullptr, C, M, K1, K2, (float*)ws, st, &gd);
-  if (bm == 256) return launch_tn<4, 1>(A, lda, G, ldg, nullptr, C, M, K1, K2, (float*)ws, st, &gd);
-  return launch_tn<2, 2>(A, lda, G, ldg, nullptr, C, M, K1, K2, (float*)ws, st, &gd);
+  CB_CHECK_ARG(active_drop(g_drop_p, row0), CB_E_INVALID, "cb_gemm_tn_gdrop_f32: the dropout must be active (0 < p < 1)");
+  const DropSpec gd = make_drop_spec(g_drop_p, g_seed, seed_dev, row0, K2);
+  return tn_entry("cb_gemm_tn_gdrop_f32", A, lda, G, ldg, nullptr, C, M, K1, K2, &gd, nullptr, ws, ws_bytes, stream);
 }
 
 // The input stage of the fused trunk's backward INSIDE the input Linear's weight gradient (autograd of GCN.py:104-110 and of the mixes res_tricks.py:23):
@@ -486,7 +495,7 @@ extern "C" size_t cb_gemm_tn_instage_workspace_bytes(int64_t M, int64_t K2) {
 extern "C" int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const uint64_t* x0_bits, const float* X, int64_t ldx, float* C, float* colsum, int64_t M,
                                       int64_t K2, float g_drop_p, uint64_t g_seed, float x_drop_p, uint64_t x_seed, const uint64_t* seed_dev, int64_t row0, void* ws,
                                       size_t ws_bytes, void* stream) {
-  CB_CHECK_ARG(M > 0 && K2 > 0 && g_drop_p > 0.f && g_drop_p < 1.f && x_drop_p > 0.f && x_drop_p < 1.f && row0 >= 0, CB_E_INVALID,
+  CB_CHECK_ARG(M > 0 && K2 > 0 && active_drop(g_drop_p, row0) && active_drop(x_drop_p, row0), CB_E_INVALID,
                "cb_gemm_tn_instage_f32: bad size or p (both dropouts must be active)");
   CB_CHECK_ARG(g && mfold && x0_bits && X && C && colsum && (uintptr_t)x0_bits % 8 == 0, CB_E_INVALID, "cb_gemm_tn_instage_f32: null or misaligned pointer");
   CB_CHECK_ARG(cb_gemm_tn_instage_supported(g, mfold, X, ldx, M, K2), CB_E_INVALID, "cb_gemm_tn_instage_f32: shape / alignment outside the fused form (cb_gemm_tn_instage_supported)");
@@ -495,18 +504,14 @@ extern "C" int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const 
   const int nsplit = instage_splits(M);
   int64_t rows_per_split = (M + nsplit - 1) / nsplit;
   rows_per_split = (rows_per_split + 31) / 32 * 32;
-  const DropSpec xd{dropout_threshold(x_drop_p), 1.f / (1.f - x_drop_p), x_seed, seed_dev, row0, K2};
-  const DropSpec gd{dropout_threshold(g_drop_p), 1.f / (1.f - g_drop_p), g_seed, seed_dev, row0, 256};
+  const DropSpec xd = make_drop_spec(x_drop_p, x_seed, seed_dev, row0, K2);
+  const DropSpec gd = make_drop_spec(g_drop_p, g_seed, seed_dev, row0, 256);
   float* partial = (float*)ws;
   float* cs_partial = partial + (size_t)nsplit * 256 * K2;
-  const int rc = launch_tn_instage(g, mfold, x0_bits, X, ldx, partial, cs_partial, M, K2, nsplit, rows_per_split, st, xd, gd);
-  if (rc != CB_OK) return rc;
-  const int64_t n = 256 * K2;
-  hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)partial, nsplit, n, C);
-  CB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, (const float*)cs_partial, nsplit, (int64_t)256, colsum);
-  CB_LAUNCH_CHECK();
-  return CB_OK;
+  int rc = launch_tn_instage(g, mfold, x0_bits, X, ldx, partial, cs_partial, M, K2, nsplit, rows_per_split, st, xd, gd);
+  if (rc == CB_OK) rc = sum_partials(partial, nsplit, 256 * K2, C, st);
+  if (rc == CB_OK) rc = sum_partials(cs_partial, nsplit, 256, colsum, st);
+  return rc;
 }
 
 // C = act(rowscale * (dropout_{a_seed}(A) @ B) + addend + bias) with the dropout applied to A while it is staged (no dropped copy of A is
@@ -517,18 +522,10 @@ extern "C" int cb_gemm_tn_instage_f32(const float* g, const float* mfold, const 
 extern "C" int cb_gemm_nn_indrop_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                                      const float* rowscale, const float* addend, int64_t ld_add, const float* bias, int relu, float a_drop_p,
                                      uint64_t a_seed, const uint64_t* seed_dev, int64_t row0, uint64_t* relu_bits, void* stream) {
-  CB_CHECK_ARG(M >= 0 && N >= 0 && K >= 0 && a_drop_p > 0.f && a_drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_gemm_nn_indrop_f32: bad size or p");
-  CB_CHECK_ARG(!relu_bits || (N == 256 && relu && (uintptr_t)relu_bits % 8 == 0), CB_E_INVALID,
-               "cb_gemm_nn_indrop_f32: mask words of the ReLU exist for N == 256 with relu only");
-  CB_CHECK_ARG(N < (1 << 24) && K < (1 << 24) && (M + 63) / 64 < (1 << 24), CB_E_RANGE, "cb_gemm_nn_indrop_f32: size out of range");
-  if (M == 0 || N == 0) return CB_OK;
-  CB_CHECK_ARG(C && A && B && lda >= K && ldb >= N && ldc >= N && (!addend || ld_add >= N), CB_E_INVALID, "cb_gemm_nn_indrop_f32: null pointer or bad ld");
-  CB_CHECK_ARG(cb_gemm_nn_indrop_supported(A, lda, B, ldb, C, ldc, C, ldc, M, N, K) && (!addend || (aligned16(addend) && ld_add % 4 == 0)), CB_E_INVALID,
-               "cb_gemm_nn_indrop_f32: shape / alignment outside the fused form (cb_gemm_nn_indrop_supported)");
-  GemmEpilogue ep{rowscale, addend, ld_add, bias, relu, nullptr, 0, 0u, 1.f, 0ull, nullptr, 0, gemm_nt_store(M, N)};
-  ep.adrop = DropSpec{dropout_threshold(a_drop_p), 1.f / (1.f - a_drop_p), a_seed, seed_dev, row0, K};
-  ep.relu_bits_out = (unsigned long long*)relu_bits;
-  return launch_nn_limb3(A, lda, B, ldb, C, ldc, M, N, K, ep, false, (hipStream_t)stream, nullptr, 0);
+  CB_CHECK_ARG(active_drop(a_drop_p, row0), CB_E_INVALID, "cb_gemm_nn_indrop_f32: the dropout must be active (0 < p < 1)");
+  NnCall c = nn_call(A, lda, B, ldb, C, ldc, M, N, K, rowscale, addend, ld_add, bias, relu, nullptr, 0, stream);
+  c.a_drop_p = a_drop_p; c.a_seed = a_seed; c.seed_dev = seed_dev; c.row0 = row0; c.relu_bits = relu_bits;
+  return nn_entry("cb_gemm_nn_indrop_f32", c);
 }
 
 // C = dropout_{a_seed}(A)^T @ (rowscale * G): the weight gradient of the first GCNConv (autograd of GCN.py:225 behind the dropout of :110)
@@ -542,17 +539,7 @@ extern "C" int cb_gemm_tn_adrop_supported(const float* A, int64_t lda, const flo
 extern "C" int cb_gemm_tn_adrop_f32(const float* A, int64_t lda, const float* G, int64_t ldg, const float* rowscale, float* C, int64_t M, int64_t K1,
                                     int64_t K2, float a_drop_p, uint64_t a_seed, const uint64_t* seed_dev, int64_t row0, void* ws, size_t ws_bytes,
                                     void* stream) {
-  CB_CHECK_ARG(M >= 0 && K1 >= 0 && K2 >= 0 && a_drop_p > 0.f && a_drop_p < 1.f && row0 >= 0, CB_E_INVALID, "cb_gemm_tn_adrop_f32: bad size or p");
-  CB_CHECK_ARG(K1 < (1 << 20) && K2 < (1 << 20), CB_E_RANGE, "cb_gemm_tn_adrop_f32: size out of range");
-  if (K1 == 0 || K2 == 0) return CB_OK;
-  CB_CHECK_ARG(C && (M == 0 || (A && G)) && lda >= K1 && ldg >= K2, CB_E_INVALID, "cb_gemm_tn_adrop_f32: null pointer or bad ld");
-  hipStream_t st = (hipStream_t)stream;
-  if (M == 0) {
-    CB_HIP(hipMemsetAsync(C, 0, (size_t)K1 * K2 * sizeof(float), st));
-    return CB_OK;
-  }
-  CB_CHECK_ARG(cb_gemm_tn_adrop_supported(A, lda, G, ldg, K1, K2), CB_E_INVALID, "cb_gemm_tn_adrop_f32: operands outside the three-limb 128-row tile path");
-  CB_CHECK_ARG(ws && ws_bytes >= cb_gemm_tn_workspace_bytes(M, K1, K2), CB_E_WORKSPACE, "cb_gemm_tn_adrop_f32: workspace too small");
-  const DropSpec ad{dropout_threshold(a_drop_p), 1.f / (1.f - a_drop_p), a_seed, seed_dev, row0, K1};
-  return launch_tn<2, 2>(A, lda, G, ldg, rowscale, C, M, K1, K2, (float*)ws, st, nullptr, &ad);
+  CB_CHECK_ARG(active_drop(a_drop_p, row0), CB_E_INVALID, "cb_gemm_tn_adrop_f32: the dropout must be active (0 < p < 1)");
+  const DropSpec ad = make_drop_spec(a_drop_p, a_seed, seed_dev, row0, K1);
+  return tn_entry("cb_gemm_tn_adrop_f32", A, lda, G, ldg, rowscale, C, M, K1, K2, nullptr, &ad, ws, ws_bytes, stream);
 }

@@ -22,31 +22,53 @@ struct DropSpec {
   int64_t width;             // row length of the dropped matrix in elements (multiple of 4)
 };
 
+static inline DropSpec make_drop_spec(float p, uint64_t seed, const uint64_t* seed_dev, int64_t row0, int64_t width) {
+  return DropSpec{dropout_threshold(p), 1.f / (1.f - p), seed, seed_dev, row0, width};
+}
+
+// A kernel argument: the fields keep their order.  Host code fills it by name (epilogue(), set_dropped_copy() and assignments below the defaults), so a
+// new field is one line here and one where it is set.
 struct GemmEpilogue {
-  const float* rowscale;  // [M] or null
-  const float* addend;    // [M, ld_add] or null
-  int64_t ld_add;
-  const float* bias;      // [N] or null
-  int relu;
+  const float* rowscale = nullptr;  // [M] or null
+  const float* addend = nullptr;    // [M, ld_add] or null
+  int64_t ld_add = 0;
+  const float* bias = nullptr;      // [N] or null
+  int relu = 0;
   // EPI == 1 kernels only: second output C2 = dropout(C) (F.dropout of the value just stored, GCN.py:110 after :105-107); the
   // keep-mask is the one cb_dropout_f32 draws for (seed, flat index (row0 + m) * N + n) — N % 4 == 0
-  float* out2;
-  int64_t ld_out2;
-  uint32_t thresh;
-  float keep_scale;
-  uint64_t seed;
-  const uint64_t* seed_dev;
-  int64_t row0;
-  int nt_store;                     // fp32 C leaves with the streaming (nt) policy
-  DropSpec adrop;                   // ADROP kernels only: dropout of the A operand (thresh = 0: off)
-  unsigned long long* relu_bits_out;   // 256-column tiles only: [M][4] mask words of (C > 0) after the ReLU (word q, bit L <-> column 4 L + q:
+  float* out2 = nullptr;
+  int64_t ld_out2 = 0;
+  uint32_t thresh = 0u;
+  float keep_scale = 1.f;
+  uint64_t seed = 0ull;
+  const uint64_t* seed_dev = nullptr;
+  int64_t row0 = 0;
+  int nt_store = 0;                 // fp32 C leaves with the streaming (nt) policy
+  DropSpec adrop = {};              // ADROP kernels only: dropout of the A operand (thresh = 0: off)
+  unsigned long long* relu_bits_out = nullptr;   // 256-column tiles only: [M][4] mask words of (C > 0) after the ReLU (word q, bit L <-> column 4 L + q:
                                     // the layout of the aggregation's fused store) — the trunk's input stage reads them instead of C itself
   // EPI == 2 kernels only (N == 256): the trunk's store (cb_trunk_store.h) on the rows of a SUBSET of the node rows (cb_trunk_store_rows_f32's pass in
   // this epilogue): act = relu(rowscale * acc + addend + bias) -> st.out_act (optional); C = the store's value; the mask words st.bits and the dropout mask
   // are taken at the NODE row row_ids[m] (none of the EPI == 1 fields above is read)
-  const int64_t* row_ids;
-  TrunkStore st;
+  const int64_t* row_ids = nullptr;
+  TrunkStore st = {};
 };
+
+// fp32 outputs too large to stay cached (> 256 MiB: the Infinity Cache) leave with the streaming policy: measured -1.5 % per launch
+// on 10M x 256 outputs (7.96 -> 7.84 ms)
+static inline int gemm_nt_store(int64_t M, int64_t N) { return M * N * 4 > ((int64_t)256 << 20); }
+
+static inline GemmEpilogue epilogue(const float* rowscale, const float* addend, int64_t ld_add, const float* bias, int relu, int nt_store) {
+  GemmEpilogue ep;
+  ep.rowscale = rowscale; ep.addend = addend; ep.ld_add = ld_add; ep.bias = bias; ep.relu = relu; ep.nt_store = nt_store;
+  return ep;
+}
+
+// the second output C2 = dropout_p(C) of the EPI == 1 kernels
+static inline void set_dropped_copy(GemmEpilogue& ep, float* C2, int64_t ldc2, float p, uint64_t seed, const uint64_t* seed_dev, int64_t row0) {
+  ep.out2 = C2; ep.ld_out2 = ldc2; ep.thresh = dropout_threshold(p); ep.keep_scale = 1.f / (1.f - p);
+  ep.seed = seed; ep.seed_dev = seed_dev; ep.row0 = row0;
+}
 
 template <int WM, int WN, int BKT = BK, int WTN = 2>
 struct Tile {

@@ -65,8 +65,9 @@ def test_gemm_nn_asymmetric_identity_and_strides():
     torch.testing.assert_close(gemm.mm_nn(a, w).cpu().double(), a.cpu().double() @ w.cpu().double(), atol=3e-4, rtol=2e-5)
 
 
+# (the three 300-row shapes: the 64-, 256- and 128-row tile of the one TN dispatch, each on the three-limb kernels)
 @pytest.mark.parametrize('M,K1,K2', [(1, 1, 1), (77, 5, 9), (1000, 128, 256), (5000, 256, 256), (3001, 1433, 64), (20000, 40, 256),
-                                     (999, 130, 7)])
+                                     (999, 130, 7), (300, 40, 256), (300, 256, 40), (300, 132, 68)])
 def test_gemm_tn(M, K1, K2):
     from gnn_tail_generalization_amd import gemm
     a, g, rs = _rand(M, K1, seed=1), _rand(M, K2, seed=2), torch.rand(M) + 0.5
@@ -75,6 +76,30 @@ def test_gemm_tn(M, K1, K2):
     torch.testing.assert_close(out.cpu().double(), ref, atol=3e-5 * max(1, M ** 0.5), rtol=3e-5)
     out2 = gemm.mm_tn(a.to(DEV), g.to(DEV), rowscale=rs.to(DEV))
     assert torch.equal(out, out2)          # fixed reduction order
+
+
+@pytest.mark.parametrize('K1,K2', [(40, 256), (256, 40), (132, 68)])
+def test_gemm_tn_misaligned_leading_dimension(K1, K2):
+    """A column slice (odd leading dimension, start 4 bytes off a 16-byte boundary) keeps every tile shape on the fp32-input kernel's scalar loads."""
+    from gnn_tail_generalization_amd import gemm
+    M = 300
+    a, g, rs = _rand(M, K1 + 1, seed=1).to(DEV)[:, 1:], _rand(M, K2, seed=2).to(DEV), (torch.rand(M) + 0.5).to(DEV)
+    assert a.stride(0) == K1 + 1 and a.data_ptr() % 16 == 4
+    ref = a.double().t() @ (g.double() * rs.double().unsqueeze(1))
+    torch.testing.assert_close(gemm.mm_tn(a, g, rowscale=rs).double(), ref, atol=3e-5 * M ** 0.5, rtol=3e-5)
+    # the same kernel's vector loads: aligned rows whose length is no multiple of 4 (so not the three-limb kernels' either)
+    a = _rand(M, K1 + 4, seed=3).to(DEV)[:, :K1 - 1]
+    assert a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0
+    ref = a.double().t() @ (g.double() * rs.double().unsqueeze(1))
+    torch.testing.assert_close(gemm.mm_tn(a, g, rowscale=rs).double(), ref, atol=3e-5 * M ** 0.5, rtol=3e-5)
+
+
+def test_gemm_tn_without_rows_is_zero():
+    """M == 0: the [K1, K2] result is exactly zero (one memset, no kernel), from the plain form and from the two operand-dropout forms alike."""
+    from gnn_tail_generalization_amd import gemm
+    a, g = torch.empty(0, 8, device=DEV), torch.empty(0, 12, device=DEV)
+    for out in (gemm.mm_tn(a, g), gemm.mm_tn_gdrop(a, g, 0.5, 7), gemm.mm_tn_adrop(a, g, 0.5, 7)):
+        assert tuple(out.shape) == (8, 12) and out.dtype == torch.float32 and not out.any()
 
 
 def test_linear_autograd_matches_torch():
