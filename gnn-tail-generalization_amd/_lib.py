@@ -169,6 +169,9 @@ SIGNATURES = {
     'cb_spgemm_chunk_emit_f32': (ctypes.c_int, [_P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     'cb_csr_transpose_workspace_bytes': (_SZ, [_I64]),
     'cb_csr_transpose_f32': (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
+    # the radix sort on its own (cb_sort.hip; tests/test_gpu_index.py)
+    'cb_sort_u64_workspace_bytes': (_SZ, [_I64]),
+    'cb_sort_u64': (ctypes.c_int, [_P, _P, _I64, ctypes.c_int, _P, _SZ, _P]),
     # the cb_linkp_* samplers read rowptr / col / n_rows / n_edges of the view only (no hub plan, no workspace): their first argument is bound as a
     # plain pointer (ctypes.byref(view)); _G marks the aggregation entries, whose views carry a hub plan
     'cb_linkp_max_tries': (ctypes.c_int, []),

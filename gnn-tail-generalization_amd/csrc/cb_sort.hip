@@ -166,11 +166,13 @@ size_t sort_u64_temp_bytes(int64_t n) {
 }
 
 int sort_u64(void* temp, size_t temp_bytes, uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit, hipStream_t st) {
-  CB_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 32) && end_bit > 0 && end_bit <= 64, CB_E_RANGE, "sort_u64: bad size / bit range (n < 2^32: per-digit prefixes are 32 bit)");
+  // (the messages name the C-ABI entry of this function, cb_sort_u64 below: the library's callers check their sizes before they get here)
+  CB_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 32) && end_bit > 0 && end_bit <= 64, CB_E_RANGE,
+               "cb_sort_u64 (sort_u64): bad size / bit range (0 <= n < 2^32: per-digit prefixes are 32 bit; 0 < end_bit <= 64)");
   if (n == 0) return CB_OK;
-  CB_CHECK_ARG(temp && keys_in && keys_out && temp_bytes >= sort_u64_temp_bytes(n), CB_E_WORKSPACE, "sort_u64: scratch too small");
+  CB_CHECK_ARG(temp && keys_in && keys_out && temp_bytes >= sort_u64_temp_bytes(n), CB_E_WORKSPACE, "cb_sort_u64 (sort_u64): null buffer or scratch too small");
   const int64_t nb = sort_blocks(n);
-  CB_CHECK_ARG(nb < INT32_MAX, CB_E_RANGE, "sort_u64: too many blocks");
+  CB_CHECK_ARG(nb < INT32_MAX, CB_E_RANGE, "cb_sort_u64 (sort_u64): too many blocks");
   char* w = (char*)temp;
   const size_t hb = align_up((size_t)nb * 256 * sizeof(uint32_t), 256);
   uint32_t* hist = (uint32_t*)w;
@@ -197,3 +199,10 @@ int sort_u64(void* temp, size_t temp_bytes, uint64_t* keys_in, uint64_t* keys_ou
 }
 
 }  // namespace cb
+
+// The sort on its own through the C ABI (tests): argument passing only, every refusal is sort_u64's.
+extern "C" size_t cb_sort_u64_workspace_bytes(int64_t n) { return cb::sort_u64_temp_bytes(n); }
+
+extern "C" int cb_sort_u64(uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit, void* ws, size_t ws_bytes, void* stream) {
+  return cb::sort_u64(ws, ws_bytes, keys_in, keys_out, n, end_bit, (hipStream_t)stream);
+}

@@ -787,6 +787,15 @@ size_t cb_csr_transpose_workspace_bytes(int64_t nnz);
 int cb_csr_transpose_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t m, int64_t n, int64_t nnz, int32_t* rowptr_t,
                          int32_t* col_t, float* val_t, void* ws, size_t ws_bytes, void* stream);
 
+/* The library's radix sort on its own (tests; csrc/cb_sort.h — the sort behind the CSR ingest, the symmetrisation, the product sort and the
+ * transpose above, csrc/cb_pair_core.h, cb_lpx.hip and cb_heur.hip): keys_out [n] = keys_in sorted ascending by
+ * bits [0, end_bit), stable — keys equal on those bits keep their input order — and the bits at and above end_bit are moved with the key and
+ * never compared: a payload there rides along.  keys_in is the second buffer of the passes and is destroyed.  ws:
+ * cb_sort_u64_workspace_bytes(n).  CB_E_RANGE for n < 0, n >= 2^32, end_bit <= 0 or end_bit > 64; n == 0 succeeds without pointers;
+ * CB_E_WORKSPACE for a null buffer or short scratch.  No atomics: two calls give the same bits. */
+size_t cb_sort_u64_workspace_bytes(int64_t n);
+int cb_sort_u64(uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit, void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------
  * The teacher's edge-wise (link-prediction) term (trainer_node_classification.py:417-438, 507-563; utils.py:754-791; cb_linkp.hip): positive and
  * negative edge samplers on the by-dst CSR (row v lists the sources u of the edges u -> v, columns ascending), the DistMult scores, the
